@@ -15,68 +15,75 @@
 
 #include "stage1.h"
 
+// A device (Host: pinned host) allocation the context owns: grown on demand by grow() (first use of a larger size), released
+// with the context.  Converts to its pointer.
+template <class T, bool Host = false>
+struct Buf {
+    T* p = nullptr;
+    size_t bytes = 0;
+    Buf() = default;
+    Buf(const Buf&) = delete;
+    Buf& operator=(const Buf&) = delete;
+    ~Buf() { release(); }
+    operator T*() const { return p; }
+    T* operator->() const { return p; }
+    void release() {
+        if (p) (void)(Host ? hipHostFree(p) : hipFree(p));
+        p = nullptr;
+        bytes = 0;
+    }
+};
+template <class T> using DevBuf = Buf<T, false>;
+template <class T> using HostBuf = Buf<T, true>;
+
 struct sjmi_ctx {
     int device = 0;
     uint64_t capacity = 0;
     hipStream_t stream = nullptr;
     hipStream_t copy_stream = nullptr;       // sjmi_parse_document: downloads the string records while the walker runs
     hipEvent_t strings_ready = nullptr;
-    uint8_t* d_in = nullptr;      // capacity + padding
-    uint32_t* d_idx = nullptr;    // capacity + 1 entries (host-buffer path)
-    void* d_ws = nullptr;         // tile-state workspace
-    size_t ws_bytes = 0;
-    void* d_ws_dev = nullptr;     // workspace for the device-resident path: TWO halves used alternately (every launch
-    size_t ws_dev_bytes = 0;      // zeroes the half the next one will use), grown on demand
+    DevBuf<uint8_t> d_in;         // capacity + padding
+    DevBuf<uint32_t> d_idx;       // capacity + 1 entries (host-buffer path)
+    DevBuf<void> d_ws;            // tile-state workspace
+    DevBuf<void> d_ws_dev;        // workspace for the device-resident path: TWO halves used alternately (every launch
+                                  // zeroes the half the next one will use), grown on demand
     size_t ws_dev_clean[2] = {0, 0};  // bytes of each half known to be zero
     int ws_dev_next = 0;              // half the next launch uses
     void* ws_dev_last = nullptr;      // half the last launch used (debug read-back)
-    sjmi_stage1_result* h_res = nullptr;  // pinned
-    void* h_pack = nullptr;               // pinned: {error index, stage-1 record, string record} of sjmi_stage1_unescape
+    HostBuf<sjmi_stage1_result> h_res;
+    HostBuf<void> h_pack;                 // {error index, stage-1 record, string record} of sjmi_stage1_unescape
     uint8_t* staging = nullptr;           // sjmi_set_input_staging: the caller's page-locked copy of the input
     uint64_t staging_bytes = 0;
-    void* d_pack = nullptr;
-    void* d_res_tmp = nullptr;            // device stage-1 record of the same call
+    DevBuf<void> d_pack;
+    DevBuf<void> d_res_tmp;               // device stage-1 record of the same call
     uint64_t last_len = 0, last_count = 0;  // document of the last sjmi_stage1 call (still on the device)
     bool last_valid = false;
-    uint8_t* d_sb = nullptr;      // string buffer (host path), grown on demand
-    size_t sb_bytes = 0;
-    void* d_ws_strm = nullptr;    // workspace of the streaming string pass (strings.hip), grown on demand
-    size_t ws_strm_bytes = 0;
-    void* d_ws_par = nullptr;     // workspace of a parity-only stage-1 launch (strings of a document this context has not indexed)
-    size_t ws_par_bytes = 0;
-    unsigned long long* d_blkpar = nullptr;  // in-string parity of every 64-byte block, left by the last stage-1 launch
-    size_t blkpar_bytes = 0;                 // ... over (par_buf, par_len): what the string pass starts from
+    DevBuf<uint8_t> d_sb;         // string buffer (host path)
+    DevBuf<void> d_ws_strm;       // workspace of the streaming string pass (strings.hip)
+    DevBuf<void> d_ws_par;        // workspace of a parity-only stage-1 launch (strings of a document this context has not indexed)
+    DevBuf<unsigned long long> d_blkpar;  // in-string parity of every 64-byte block, left by the last stage-1 launch
+                                          // ... over (par_buf, par_len): what the string pass starts from
     const void* par_buf = nullptr;
     uint64_t par_len = 0;
     bool par_valid = false;
-    unsigned long long* d_err_index = nullptr;  // host forms: position in indexes[] of the first failing string
+    DevBuf<unsigned long long> d_err_index;  // host forms: position in indexes[] of the first failing string
     // what the cooperative walker takes from the string pass: offset of every record by string ordinal, the ordinal of the
     // first string at or behind every 64-byte block, the ordinal of every document's first string
-    uint32_t* d_soff = nullptr;
-    size_t soff_bytes = 0;
-    uint32_t* d_blk_ord = nullptr;
-    size_t blk_ord_bytes = 0;
-    unsigned long long* d_doc_ord = nullptr;
-    size_t doc_ord_bytes = 0;
+    DevBuf<uint32_t> d_soff;
+    DevBuf<uint32_t> d_blk_ord;
+    DevBuf<unsigned long long> d_doc_ord;
     const void* soff_idx = nullptr;  // the index array these belong to (the last batch string pass on this context)
-    sjmi_unescape_result* d_ures_walk = nullptr;  // ... and a copy of that pass's result record (for a walk queued later)
-    uint8_t* d_copy = nullptr;       // isolated batches: the sanitized copy the string pass runs on, and its block parities
-    size_t copy_bytes = 0;
-    unsigned long long* d_blkpar2 = nullptr;
-    size_t blkpar2_bytes = 0;
-    sjmi_unescape_result* d_ures = nullptr;
-    unsigned long long* d_docoff = nullptr;  // batch: document offsets + index offsets (+ statuses), grown on demand
-    uint32_t* d_doccnt = nullptr;            // isolated batch: per-document index counts
-    size_t doccnt_bytes = 0;
-    unsigned long long* d_docstr = nullptr;  // batch: per-document string-buffer offsets
-    size_t docstr_bytes = 0;
-    void* d_ws_walk = nullptr;               // batch walk: scratch tape, tape lengths, chunk sums
-    size_t ws_walk_bytes = 0;
-    void* d_masks = nullptr;                 // sjmi_stage1_masks: 6 x u64 per block + its workspace, grown on demand
-    size_t masks_bytes = 0;
-    void* d_ws_masks = nullptr;
-    size_t ws_masks_bytes = 0;
-    void* d_single = nullptr;                // sjmi_parse_document: delimiters, tape offsets, error and results of ONE document
+    DevBuf<sjmi_unescape_result> d_ures_walk;  // ... and a copy of that pass's result record (for a walk queued later)
+    DevBuf<uint8_t> d_copy;          // isolated batches: the sanitized copy the string pass runs on, and its block parities
+    DevBuf<unsigned long long> d_blkpar2;
+    DevBuf<sjmi_unescape_result> d_ures;
+    DevBuf<unsigned long long> d_docoff;  // batch: document offsets + index offsets (+ statuses)
+    DevBuf<uint32_t> d_doccnt;            // isolated batch: per-document index counts
+    DevBuf<unsigned long long> d_docstr;  // batch: per-document string-buffer offsets
+    DevBuf<void> d_ws_walk;               // batch walk: scratch tape, tape lengths, chunk sums
+    DevBuf<void> d_masks;                 // sjmi_stage1_masks: 6 x u64 per block + its workspace
+    DevBuf<void> d_ws_masks;
+    DevBuf<void> d_single;                // sjmi_parse_document: delimiters, tape offsets, error and results of ONE document
     struct HostView { const void* host = nullptr; void* dev = nullptr; };
     uint64_t pin_epoch = 0;                  // g_pin_epoch when the views below were taken (a (un)register anywhere drops them)
     HostView views[6];                       // device views of caller buffers that are page-locked and device-visible (zero-copy outputs)
@@ -85,28 +92,19 @@ struct sjmi_ctx {
     const void* idx_last_host = nullptr;     // ... the caller's array as the host sees it (nullptr: c->d_idx)
     void* h_res_dev = nullptr;               // h_res / h_pack as the device sees them
     void* h_pack_dev = nullptr;
-    void* s1_zero2 = nullptr;                // one-shot extras of the next stage1_device_impl call (sjmi_parse_document):
-    size_t s1_zero2_bytes = 0;               //   a second region its workers zero, the single-document setup its scanner writes
-    sjmi::Stage1Single s1_single;
-    bool s1_single_done = false;             // ... the last launch was FAST and did write it
     const void* zc_host = nullptr;           // sjmi_parse_document: the caller's tape if it is device-visible (registered / pinned)
     unsigned long long* zc_dev = nullptr;    // ... as the device sees it
     void* h_single_dev = nullptr;            // h_single as the device sees it
-    uint32_t* d_blkidx = nullptr;            // fused batch pipeline: k_stage1's per-block side outputs (stage1.h Stage1Extras)
-    size_t blkidx_bytes = 0;
-    uint16_t* d_blkw = nullptr;
-    size_t blkw_bytes = 0;
-    bool batch_side = false;                 // ... wanted from the next stage1_device_impl call
-    uint32_t* d_batch_flags = nullptr;       // the two words of a batch's optimistic plain stage-1 pass ([1] != 0: accepted)
+    DevBuf<uint32_t> d_blkidx;               // fused batch pipeline: k_stage1's per-block side outputs (stage1.h Stage1Extras)
+    DevBuf<uint16_t> d_blkw;
+    DevBuf<uint32_t> d_batch_flags;          // the two words of a batch's optimistic plain stage-1 pass ([1] != 0: accepted)
     const void* accept_buf = nullptr;        // ... which batch they belong to (the string pass of the same batch reads the flag)
     uint64_t accept_len = 0;
     bool accept_valid = false;
-    unsigned long long* d_tape = nullptr;    // ... and its tape, grown on demand
-    size_t tape_bytes = 0;
-    void* h_single = nullptr;                // pinned copy of the three result records
+    DevBuf<unsigned long long> d_tape;       // ... and its tape
+    HostBuf<void> h_single;                  // pinned copy of the three result records
     uint64_t last_ndocs = 0;                 // documents of the last batch call (their index offsets are still on the device)
     bool last_batch = false;
-    size_t docoff_bytes = 0;
     int forced_steps = 0;
     uint32_t dbg = 0;  // ablation flags (sjmi_debug_set_flags)
     bool ticket_mode = false;  // safe tile assignment (latched on after a look-back timeout in fast mode)
@@ -163,7 +161,111 @@ bool fail(sjmi_ctx* c, const char* what, hipError_t e) {
     c->err = b;
     return true;
 }
-
+template <class T, bool Host>
+bool grow(sjmi_ctx* c, Buf<T, Host>& b, size_t need, const char* what) {
+    if (need <= b.bytes) return true;
+    b.release();
+    void* p = nullptr;
+    if (fail(c, what, Host ? hipHostMalloc(&p, need) : hipMalloc(&p, need))) return false;
+    b.p = static_cast<T*>(p);
+    b.bytes = need;
+    return true;
+}
+// the stage-1 granule (4 KiB steps per workgroup) for `len` bytes: sjmi_set_tile_steps, else the library's choice
+int stage1_steps(const sjmi_ctx* c, uint64_t len) { return c->forced_steps ? c->forced_steps : sjmi::stage1_pick_steps(len); }
+// the index capacity of a host-form call on the device: the context's array holds capacity + 2 entries
+uint64_t dev_index_cap(const sjmi_ctx* c, uint64_t index_capacity) {
+    return c->capacity + 2 < index_capacity ? c->capacity + 2 : index_capacity;
+}
+// host forms: the document / batch has to fit the context's buffers
+bool too_large(sjmi_ctx* c, uint64_t len, const char* what) {
+    if (len <= c->capacity && len < (1ull << 32)) return false;
+    c->err = std::string(what) + " larger than the context capacity";
+    return true;
+}
+// a stage-1 record's status as a host entry point's return code
+int stage1_rc(sjmi_ctx* c, uint32_t status) {
+    if (status & SJMI_ST_INTERNAL) {
+        c->err = "look-back timeout";
+        return SJMI_ERR_INTERNAL;
+    }
+    if (status & SJMI_ST_CAPACITY) {
+        c->err = "index_capacity too small";
+        return SJMI_ERR_CAPACITY;
+    }
+    return SJMI_OK;
+}
+// what the two-call forms (sjmi_unescape / sjmi_unescape_batch) take from the last successful stage-1 call: where its indexes
+// are (idx_host: the caller's array as the host sees it, nullptr for c->d_idx), the document / batch and its structurals
+void note_last(sjmi_ctx* c, const uint32_t* idx, const void* idx_host, uint64_t len, uint64_t count, bool batch = false,
+               uint64_t n_docs = 0) {
+    c->idx_last = idx;
+    c->idx_last_host = idx_host;
+    c->last_len = len;
+    c->last_count = count;
+    c->last_valid = true;
+    c->last_batch = batch;
+    if (batch) c->last_ndocs = n_docs;
+}
+// sjmi_set_auto_safe's per-launch check switched off for the lifetime of the object (a call that re-runs in SAFE mode itself)
+struct AutoSafeOff {
+    sjmi_ctx* c;
+    bool keep;
+    explicit AutoSafeOff(sjmi_ctx* ctx) : c(ctx), keep(ctx->auto_safe) { ctx->auto_safe = false; }
+    ~AutoSafeOff() { c->auto_safe = keep; }
+};
+// The host forms' own retry: `attempt` queues the call's work and synchronises, after which `status` holds the stage-1 status.
+// On SJMI_ST_INTERNAL the fast-mode liveness assumption failed: the safe mode is latched and the attempt runs once more.
+template <class Attempt>
+int retry_in_safe_mode(sjmi_ctx* c, const uint32_t& status, Attempt attempt) {
+    const AutoSafeOff own_retry(c);
+    for (int i = 0; i < 2; ++i) {
+        const int rc = attempt();
+        if (rc != SJMI_OK) return rc;
+        if (!(status & SJMI_ST_INTERNAL) || c->ticket_mode) break;
+        c->ticket_mode = true;
+    }
+    return SJMI_OK;
+}
+// document offsets of a batch come across the public ABI: [0] == 0 (isolated mode), monotonic, [n] <= total_len
+bool bad_offsets(sjmi_ctx* c, const uint64_t* offs, uint64_t n_docs, uint64_t total_len, bool first_is_zero) {
+    bool bad = (first_is_zero && n_docs && offs[0] != 0) || offs[n_docs] > total_len;
+    for (uint64_t k = 0; k < n_docs && !bad; ++k) bad = offs[k + 1] < offs[k];
+    if (bad) c->err = "doc_offsets must be monotonic, start at 0 and end at or before total_len";
+    return bad;
+}
+// Where a plain stage-1 launch over (d_buf, len) leaves its block parities (null: the allocation failed -- the string pass
+// then makes its own).  Shards and the per-document passes of an isolated batch do not record any.
+void* parity_out(sjmi_ctx* c, const void* d_buf, uint64_t len) {
+    c->par_valid = false;
+    c->accept_valid = false;  // (another stage-1 launch: a batch's acceptance flag no longer describes the parities)
+    if (!grow(c, c->d_blkpar, sjmi::strings_parity_words(len) * sizeof(unsigned long long), "hipMalloc(blkpar)")) return nullptr;
+    c->par_buf = d_buf;
+    c->par_len = len;
+    c->par_valid = true;
+    return c->d_blkpar;
+}
+// a stage-1 launch over (d_buf, len) on the workspace c->d_ws_par that writes nothing but what `ex` asks for (no indexes, no
+// sentinel): the block parities of bytes this context has not indexed
+hipError_t parity_launch(sjmi_ctx* c, const uint8_t* d_buf, uint64_t len, hipStream_t st, const sjmi::Stage1Extras& ex) {
+    const hipError_t e = sjmi::stage1_launch(d_buf, len, nullptr, 0, c->d_ws_par, stage1_steps(c, len), st, nullptr, nullptr,
+                                             (launch_flags(c) & ~sjmi::DBG_NO_LOOKBACK) | sjmi::DBG_NO_WRITE, ex);
+    if (e == hipSuccess) note_launch(c, st);
+    return e;
+}
+// The block parities of (d_buf, len) for the string pass: those of the context's last stage-1 launch if it was over the same
+// bytes, else a parity-only launch queued on `st`.
+const unsigned long long* parity_for(sjmi_ctx* c, const void* d_buf, uint64_t len, hipStream_t st) {
+    if (c->par_valid && c->par_buf == d_buf && c->par_len == len) return c->d_blkpar;
+    if (!grow(c, c->d_ws_par, sjmi::stage1_workspace_bytes(len, stage1_steps(c, len)), "hipMalloc(ws_par)")) return nullptr;
+    sjmi::Stage1Extras ex;
+    ex.blkpar = parity_out(c, d_buf, len);
+    if (!ex.blkpar) return nullptr;
+    c->par_valid = false;  // (until the launch is queued)
+    if (fail(c, "parity launch", parity_launch(c, (const uint8_t*)d_buf, len, st, ex))) return nullptr;
+    c->par_valid = true;
+    return c->d_blkpar;
+}
 
 }  // namespace
 
@@ -182,13 +284,11 @@ int sjmi_create(sjmi_ctx** out, int device, uint64_t capacity_bytes) {
     c->device = device;
     c->capacity = capacity_bytes;
     const size_t in_bytes = ((capacity_bytes + 63) / 64) * 64 + 2 * SJMI_PADDING;
-    c->ws_bytes = sjmi::stage1_workspace_bytes(capacity_bytes, 1);
     if (fail(c, "hipSetDevice", hipSetDevice(device)) ||
         fail(c, "hipStreamCreate", hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking)) ||
-        fail(c, "hipMalloc(in)", hipMalloc((void**)&c->d_in, in_bytes)) ||
-        fail(c, "hipMalloc(idx)", hipMalloc((void**)&c->d_idx, (capacity_bytes + 2) * sizeof(uint32_t))) ||
-        fail(c, "hipMalloc(ws)", hipMalloc(&c->d_ws, c->ws_bytes)) ||
-        fail(c, "hipHostMalloc", hipHostMalloc((void**)&c->h_res, sizeof(sjmi_stage1_result)))) {
+        !grow(c, c->d_in, in_bytes, "hipMalloc(in)") || !grow(c, c->d_idx, (capacity_bytes + 2) * sizeof(uint32_t), "hipMalloc(idx)") ||
+        !grow(c, c->d_ws, sjmi::stage1_workspace_bytes(capacity_bytes, 1), "hipMalloc(ws)") ||
+        !grow(c, c->h_res, sizeof(sjmi_stage1_result), "hipHostMalloc")) {
         fprintf(stderr, "sjmi_create: %s\n", c->err.c_str());
         sjmi_destroy(c);
         return SJMI_ERR_HIP;
@@ -216,38 +316,6 @@ void sjmi_destroy(sjmi_ctx* c) {
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     if (c->busy_event) (void)hipEventDestroy(c->busy_event);
-    if (c->d_in) (void)hipFree(c->d_in);
-    if (c->d_idx) (void)hipFree(c->d_idx);
-    if (c->d_ws) (void)hipFree(c->d_ws);
-    if (c->d_ws_dev) (void)hipFree(c->d_ws_dev);
-    if (c->d_sb) (void)hipFree(c->d_sb);
-    if (c->d_ws_strm) (void)hipFree(c->d_ws_strm);
-    if (c->d_ws_par) (void)hipFree(c->d_ws_par);
-    if (c->d_blkpar) (void)hipFree(c->d_blkpar);
-    if (c->d_err_index) (void)hipFree(c->d_err_index);
-    if (c->d_soff) (void)hipFree(c->d_soff);
-    if (c->d_ures_walk) (void)hipFree(c->d_ures_walk);
-    if (c->d_blk_ord) (void)hipFree(c->d_blk_ord);
-    if (c->d_doc_ord) (void)hipFree(c->d_doc_ord);
-    if (c->d_copy) (void)hipFree(c->d_copy);
-    if (c->d_blkpar2) (void)hipFree(c->d_blkpar2);
-    if (c->d_ures) (void)hipFree(c->d_ures);
-    if (c->d_docoff) (void)hipFree(c->d_docoff);
-    if (c->d_doccnt) (void)hipFree(c->d_doccnt);
-    if (c->d_docstr) (void)hipFree(c->d_docstr);
-    if (c->d_ws_walk) (void)hipFree(c->d_ws_walk);
-    if (c->d_single) (void)hipFree(c->d_single);
-    if (c->d_batch_flags) (void)hipFree(c->d_batch_flags);
-    if (c->d_blkidx) (void)hipFree(c->d_blkidx);
-    if (c->d_blkw) (void)hipFree(c->d_blkw);
-    if (c->d_tape) (void)hipFree(c->d_tape);
-    if (c->h_single) (void)hipHostFree(c->h_single);
-    if (c->d_masks) (void)hipFree(c->d_masks);
-    if (c->d_ws_masks) (void)hipFree(c->d_ws_masks);
-    if (c->h_res) (void)hipHostFree(c->h_res);
-    if (c->h_pack) (void)hipHostFree(c->h_pack);
-    if (c->d_pack) (void)hipFree(c->d_pack);
-    if (c->d_res_tmp) (void)hipFree(c->d_res_tmp);
     for (auto& e : c->events) {
         (void)hipEventDestroy(e.first);
         (void)hipEventDestroy(e.second);
@@ -255,7 +323,7 @@ void sjmi_destroy(sjmi_ctx* c) {
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
     if (c->strings_ready) (void)hipEventDestroy(c->strings_ready);
     if (c->stream) (void)hipStreamDestroy(c->stream);
-    delete c;
+    delete c;  // (releases every buffer the context owns)
     g_live_contexts.fetch_sub(1);
 }
 
@@ -263,7 +331,7 @@ const char* sjmi_last_error(const sjmi_ctx* c) { return c ? c->err.c_str() : "nu
 
 #ifdef SJMI_TRACE
 extern "C" int sjmi_debug_read_ws(sjmi_ctx* c, void* dst, uint64_t offset, uint64_t bytes) {
-    if (!c || !c->ws_dev_last || offset + bytes > c->ws_dev_bytes / 2) return SJMI_ERR_ARG;
+    if (!c || !c->ws_dev_last || offset + bytes > c->d_ws_dev.bytes / 2) return SJMI_ERR_ARG;
     (void)hipDeviceSynchronize();
     return hipMemcpy(dst, (uint8_t*)c->ws_dev_last + offset, bytes, hipMemcpyDeviceToHost) == hipSuccess ? SJMI_OK : SJMI_ERR_HIP;
 }
@@ -273,10 +341,6 @@ int sjmi_set_tile_steps(sjmi_ctx* c, int steps) {
     if (!c || !(steps == 0 || steps == 1 || steps == 2 || steps == 4)) return SJMI_ERR_ARG;
     c->forced_steps = steps;
     return SJMI_OK;
-}
-
-namespace {
-void* parity_out(sjmi_ctx* c, const void* d_buf, uint64_t len);
 }
 
 int sjmi_set_input_staging(sjmi_ctx* c, void* pinned, uint64_t bytes) {
@@ -327,17 +391,10 @@ static bool upload_document(sjmi_ctx* c, const uint8_t* buf, uint64_t len) {
     }
     return !fail(c, "H2D", hipMemcpyAsync(c->d_in, buf, len, hipMemcpyHostToDevice, c->stream));
 }
-// sjmi_set_auto_safe's per-launch check switched off for the lifetime of the object (a call that re-runs in SAFE mode itself)
-struct AutoSafeOff {
-    sjmi_ctx* c;
-    bool keep;
-    explicit AutoSafeOff(sjmi_ctx* ctx) : c(ctx), keep(ctx->auto_safe) { ctx->auto_safe = false; }
-    ~AutoSafeOff() { c->auto_safe = keep; }
-};
 // The device's view of a caller buffer that is page-locked and device-visible (sjmi_host_register / hipHostMalloc), or nullptr
 // (pageable memory: the staged path).  The kernels then write their outputs straight into it over PCIe -- no download, and no
 // second host synchronisation whose only purpose was to learn how much to download.  Cached per pointer (a handful of buffers
-// per parser).  SJMI_ZERO_COPY=0 switches every zero-copy path off.
+// per parser).
 static std::atomic<uint64_t> g_pin_epoch{1};  // bumped by sjmi_host_register / sjmi_host_unregister: cached views are stale
 static void drop_stale_views(sjmi_ctx* c) {
     const uint64_t e = g_pin_epoch.load(std::memory_order_acquire);
@@ -360,9 +417,13 @@ static void drop_stale_views(sjmi_ctx* c) {
         }
     }
 }
-static void* device_view(sjmi_ctx* c, const void* host) {
+// SJMI_ZERO_COPY=0 switches every zero-copy path off
+static bool zero_copy_off() {
     static const bool off = getenv("SJMI_ZERO_COPY") && atoi(getenv("SJMI_ZERO_COPY")) == 0;
-    if (off || !host) return nullptr;
+    return off;
+}
+static void* device_view(sjmi_ctx* c, const void* host) {
+    if (zero_copy_off() || !host) return nullptr;
     drop_stale_views(c);
     for (const auto& v : c->views)
         if (v.host == host) return v.dev;
@@ -377,138 +438,138 @@ static void* device_view(sjmi_ctx* c, const void* host) {
     return dp;
 }
 
+// What a stage1_device_impl call does besides the plain launch
+struct Stage1Opts {
+    uint32_t shard_flags = 0;        // sjmi_stage1_shard_device2: halo / tail / entry-parity flags (no block parities recorded)
+    void* zero2 = nullptr;           // a second region its workers zero (sjmi_parse_document, the fused batch pipeline)
+    size_t zero2_bytes = 0;
+    sjmi::Stage1Single single;       // the single-document setup its scanner writes (sjmi_parse_document; FAST launches only)
+    bool side = false;               // the fused batch pipeline's per-block side outputs (c->d_blkidx, c->d_blkw)
+    bool single_done = false;        // out: the launch was FAST and did write `single`
+};
 static int stage1_device_impl(sjmi_ctx* c, const void* d_buf, uint64_t len, void* d_indexes, uint64_t index_capacity,
-                              void* d_result, void* stream, uint32_t shard_flags);
+                              void* d_result, void* stream, Stage1Opts* opts = nullptr) {
+    if (!c || !d_buf || !d_indexes || !d_result) return SJMI_ERR_ARG;
+    if (len >= (1ull << 32) || ((uintptr_t)d_buf & 15) || ((uintptr_t)d_indexes & 15)) return SJMI_ERR_ARG;
+    if (fail(c, "hipSetDevice", hipSetDevice(c->device))) return SJMI_ERR_HIP;
+    Stage1Opts none;
+    Stage1Opts& o = opts ? *opts : none;
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    const int steps = stage1_steps(c, len);
+    const size_t need = (sjmi::stage1_workspace_bytes(len, steps) + 255) & ~(size_t)255;
+    if (2 * need > c->d_ws_dev.bytes) {  // grown outside any timed loop on first use of a given size
+        if (!grow(c, c->d_ws_dev, 2 * need, "hipMalloc(ws_dev)")) return SJMI_ERR_HIP;
+        c->ws_dev_clean[0] = c->ws_dev_clean[1] = 0;
+    }
+    // Nothing but the kernel is queued once the context is warm: this launch finds its half of the workspace zeroed
+    // by the previous one, zeroes the other half for the next one, and its last wave writes *d_result.
+    // (One launch stream per context at a time: the halves are handed over in stream order.)
+    const size_t half = c->d_ws_dev.bytes / 2;
+    const int h = c->ws_dev_next;
+    uint8_t* ws = (uint8_t*)c->d_ws_dev.p + (size_t)h * half;
+    const bool fast = !(launch_flags(c) & (sjmi::FLAG_SAFE | sjmi::DBG_NO_LOOKBACK));  // (the scanner writes the result)
+    sjmi::Stage1Extras ex;
+    ex.workspace_is_zero = c->ws_dev_clean[h] >= need;
+    ex.zero_next = (uint8_t*)c->d_ws_dev.p + (size_t)(1 - h) * half;
+    ex.zero_bytes = need;
+    ex.result_out = fast ? d_result : nullptr;
+    ex.blkpar = o.shard_flags ? nullptr : parity_out(c, d_buf, len);
+    if (o.shard_flags) c->par_valid = false;
+    ex.zero2 = o.zero2;
+    ex.zero2_bytes = o.zero2_bytes;
+    if (fast) ex.single = o.single;
+    o.single_done = fast && o.single.index_offsets != nullptr;
+    if (o.side && !o.shard_flags) {  // (the fused batch pipeline's plain pass: per-block index positions and tape words)
+        const size_t entries = sjmi::stage1_block_entries(len);
+        if (!grow(c, c->d_blkidx, entries * sizeof(uint32_t), "hipMalloc(blkidx)") ||
+            !grow(c, c->d_blkw, entries * sizeof(uint16_t), "hipMalloc(blkw)"))
+            return SJMI_ERR_HIP;
+        ex.blkidx = c->d_blkidx;
+        ex.blkw = c->d_blkw;
+    }
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    if (c->profiling) {
+        if (c->events_used == c->events.size()) {
+            hipEvent_t a, b;
+            if (fail(c, "hipEventCreate", hipEventCreate(&a)) || fail(c, "hipEventCreate", hipEventCreate(&b)))
+                return SJMI_ERR_HIP;
+            c->events.emplace_back(a, b);
+        }
+        ev0 = c->events[c->events_used].first;
+        ev1 = c->events[c->events_used].second;
+        ++c->events_used;
+    }
+    if (fail(c, "launch", sjmi::stage1_launch((const uint8_t*)d_buf, len, (uint32_t*)d_indexes, index_capacity, ws, steps,
+                                              st, ev0, ev1, launch_flags(c) | o.shard_flags, ex)))
+        return SJMI_ERR_HIP;
+    note_launch(c, st);
+    if (!fast && fail(c, "D2D(result)", hipMemcpyAsync(d_result, ws + sjmi::WS_RESULT_OFFSET, sizeof(sjmi_stage1_result),
+                                                       hipMemcpyDeviceToDevice, st)))
+        return SJMI_ERR_HIP;
+    c->ws_dev_clean[h] = 0;
+    c->ws_dev_clean[1 - h] = need;
+    c->ws_dev_next = 1 - h;
+    c->ws_dev_last = ws;
+    if (c->auto_safe && !c->ticket_mode) {
+        // opt-in (sjmi_set_auto_safe): the FAST kernel's liveness rests on its whole grid being resident; a caller that
+        // shares the GPU with other kernels can ask for the check here -- one synchronisation per launch -- instead of
+        // finding SJMI_ST_INTERNAL in its result record: on a tripped spin bound SAFE mode is latched and the launch repeated
+        sjmi_stage1_result r;
+        if (fail(c, "D2H(result)", hipMemcpyAsync(&r, d_result, sizeof r, hipMemcpyDeviceToHost, st)) ||
+            fail(c, "sync", hipStreamSynchronize(st)))
+            return SJMI_ERR_HIP;
+        if (r.status & SJMI_ST_INTERNAL) {
+            c->ticket_mode = true;
+            return stage1_device_impl(c, d_buf, len, d_indexes, index_capacity, d_result, stream, opts);
+        }
+    }
+    return SJMI_OK;
+}
+
+
 int sjmi_stage1(sjmi_ctx* c, const uint8_t* buf, uint64_t len, uint32_t* indexes, uint64_t index_capacity,
                 uint64_t* count, uint32_t* status) {
     if (!c || (!buf && len) || !indexes || !count || !status) return SJMI_ERR_ARG;
-    if (len > c->capacity || len >= (1ull << 32)) {
-        c->err = "document larger than the context capacity";
-        return SJMI_ERR_CAPACITY;
-    }
+    if (too_large(c, len, "document")) return SJMI_ERR_CAPACITY;
     if (index_capacity < 1) return SJMI_ERR_CAPACITY;
     if (fail(c, "hipSetDevice", hipSetDevice(c->device))) return SJMI_ERR_HIP;
     // padIfNeeded (SimdJsonParser.java:42-48): only buf[0,len) is ever read from the caller
     if (!upload_document(c, buf, len)) return SJMI_ERR_HIP;
-    const uint64_t dev_cap = c->capacity + 2 < index_capacity ? c->capacity + 2 : index_capacity;
-    if (!c->d_res_tmp && fail(c, "hipMalloc(result)", hipMalloc((void**)&c->d_res_tmp, 64))) return SJMI_ERR_HIP;
+    const uint64_t dev_cap = dev_index_cap(c, index_capacity);
+    if (!grow(c, c->d_res_tmp, 64, "hipMalloc(result)")) return SJMI_ERR_HIP;
     const uint64_t spec_idx = len + 2 < dev_cap ? len + 2 : dev_cap;
     const bool small = len <= (4u << 10);
-    const AutoSafeOff own_retry(c);  // (the retry below is this call's own)
     // zero-copy: the caller's index array is device-visible -> the kernel writes indexes[0..count] there, the scanner the record
     // into the pinned result page: one synchronisation, no download
     uint32_t* const zc_idx = ((uintptr_t)indexes & 15) ? nullptr : (uint32_t*)device_view(c, indexes);
     if (!c->h_res_dev) c->h_res_dev = device_view(c, c->h_res);
-    if (zc_idx && c->h_res_dev) {
-        for (int attempt = 0; attempt < 2; ++attempt) {
-            const int rc = stage1_device_impl(c, c->d_in, len, zc_idx, dev_cap, c->h_res_dev, c->stream, 0);
-            if (rc != SJMI_OK) return rc;
-            if (fail(c, "sync", hipStreamSynchronize(c->stream))) return SJMI_ERR_HIP;
-            if (!(c->h_res->status & SJMI_ST_INTERNAL) || c->ticket_mode) break;
-            c->ticket_mode = true;
-        }
-        *status = c->h_res->status & 0xFFu;
-        *count = c->h_res->count;
-        if (c->h_res->status & SJMI_ST_INTERNAL) {
-            c->err = "look-back timeout";
-            return SJMI_ERR_INTERNAL;
-        }
-        if (c->h_res->status & SJMI_ST_CAPACITY) {
-            c->err = "index_capacity too small";
-            return SJMI_ERR_CAPACITY;
-        }
-        c->idx_last = zc_idx;
-        c->idx_last_host = indexes;
-        c->last_len = len;
-        c->last_count = c->h_res->count;
-        c->last_valid = true;
-        c->last_batch = false;
-        return SJMI_OK;
-    }
-    c->idx_last = c->d_idx;
-    c->idx_last_host = nullptr;
-    for (int attempt = 0; attempt < 2; ++attempt) {
+    const bool zero_copy = zc_idx && c->h_res_dev;
+    uint32_t* const idx_out = zero_copy ? zc_idx : c->d_idx;
+    int rc = retry_in_safe_mode(c, c->h_res->status, [&] {
         // (the device entry point: double-buffered workspace, nothing but the kernel is queued once the context is warm)
-        const int rc = stage1_device_impl(c, c->d_in, len, c->d_idx, dev_cap, c->d_res_tmp, c->stream, 0);
-        if (rc != SJMI_OK) return rc;
+        const int rc1 = stage1_device_impl(c, c->d_in, len, idx_out, dev_cap, zero_copy ? c->h_res_dev : c->d_res_tmp.p, c->stream);
+        if (rc1 != SJMI_OK) return rc1;
         // (a small document's indexes come back behind the same synchronisation, by their bound of one structural per byte)
-        if (fail(c, "D2H(result)", hipMemcpyAsync(c->h_res, c->d_res_tmp, sizeof(sjmi_stage1_result), hipMemcpyDeviceToHost, c->stream)) ||
-            (small && fail(c, "D2H(indexes)", hipMemcpyAsync(indexes, c->d_idx, spec_idx * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream))) ||
+        if ((!zero_copy &&
+             (fail(c, "D2H(result)", hipMemcpyAsync(c->h_res, c->d_res_tmp, sizeof(sjmi_stage1_result), hipMemcpyDeviceToHost, c->stream)) ||
+              (small && fail(c, "D2H(indexes)", hipMemcpyAsync(indexes, c->d_idx, spec_idx * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream))))) ||
             fail(c, "sync", hipStreamSynchronize(c->stream)))
             return SJMI_ERR_HIP;
-        if (!(c->h_res->status & SJMI_ST_INTERNAL) || c->ticket_mode) break;
-        c->ticket_mode = true;  // fast-mode liveness assumption failed: latch the safe mode and run again
-    }
+        return SJMI_OK;
+    });
+    if (rc != SJMI_OK) return rc;
     *status = c->h_res->status & 0xFFu;
     *count = c->h_res->count;
-    if (c->h_res->status & SJMI_ST_INTERNAL) {
-        c->err = "look-back timeout";
-        return SJMI_ERR_INTERNAL;
-    }
-    if (c->h_res->status & SJMI_ST_CAPACITY) {
-        c->err = "index_capacity too small";
-        return SJMI_ERR_CAPACITY;
-    }
-    if (!(small && c->h_res->count + 1 <= spec_idx) &&
+    if ((rc = stage1_rc(c, c->h_res->status)) != SJMI_OK) return rc;
+    if (!zero_copy && !(small && c->h_res->count + 1 <= spec_idx) &&
         (fail(c, "D2H(indexes)",
               hipMemcpyAsync(indexes, c->d_idx, (c->h_res->count + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost,
                              c->stream)) ||
          fail(c, "sync", hipStreamSynchronize(c->stream))))
         return SJMI_ERR_HIP;
-    c->last_len = len;
-    c->last_count = c->h_res->count;
-    c->last_valid = true;
-    c->last_batch = false;
+    note_last(c, idx_out, zero_copy ? indexes : nullptr, len, c->h_res->count);
     return SJMI_OK;
 }
-
-namespace {
-// document offsets of a batch come across the public ABI: [0] == 0 (isolated mode), monotonic, [n] <= total_len
-bool bad_offsets(sjmi_ctx* c, const uint64_t* offs, uint64_t n_docs, uint64_t total_len, bool first_is_zero) {
-    bool bad = (first_is_zero && n_docs && offs[0] != 0) || offs[n_docs] > total_len;
-    for (uint64_t k = 0; k < n_docs && !bad; ++k) bad = offs[k + 1] < offs[k];
-    if (bad) c->err = "doc_offsets must be monotonic, start at 0 and end at or before total_len";
-    return bad;
-}
-bool grow(sjmi_ctx* c, void** p, size_t* have, size_t need, const char* what) {
-    if (need <= *have) return true;
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-    *have = 0;
-    if (fail(c, what, hipMalloc(p, need))) return false;
-    *have = need;
-    return true;
-}
-// Where a plain stage-1 launch over (d_buf, len) leaves its block parities (null: the allocation failed -- the string pass
-// then makes its own).  Shards and the per-document passes of an isolated batch do not record any.
-void* parity_out(sjmi_ctx* c, const void* d_buf, uint64_t len) {
-    c->par_valid = false;
-    c->accept_valid = false;  // (another stage-1 launch: a batch's acceptance flag no longer describes the parities)
-    if (!grow(c, (void**)&c->d_blkpar, &c->blkpar_bytes, sjmi::strings_parity_words(len) * sizeof(unsigned long long), "hipMalloc(blkpar)"))
-        return nullptr;
-    c->par_buf = d_buf;
-    c->par_len = len;
-    c->par_valid = true;
-    return c->d_blkpar;
-}
-// The block parities of (d_buf, len) for the string pass: those of the context's last stage-1 launch if it was over the same
-// bytes, else a stage-1 launch that writes nothing but them (no indexes, no sentinel), queued on `st`.
-const unsigned long long* parity_for(sjmi_ctx* c, const void* d_buf, uint64_t len, hipStream_t st) {
-    if (c->par_valid && c->par_buf == d_buf && c->par_len == len) return c->d_blkpar;
-    const int steps = c->forced_steps ? c->forced_steps : sjmi::stage1_pick_steps(len);
-    if (!grow(c, &c->d_ws_par, &c->ws_par_bytes, sjmi::stage1_workspace_bytes(len, steps), "hipMalloc(ws_par)")) return nullptr;
-    sjmi::Stage1Extras ex;
-    ex.blkpar = parity_out(c, d_buf, len);
-    if (!ex.blkpar) return nullptr;
-    c->par_valid = false;  // (until the launch is queued)
-    if (fail(c, "parity launch", sjmi::stage1_launch((const uint8_t*)d_buf, len, nullptr, 0, c->d_ws_par, steps, st, nullptr, nullptr,
-                                                     (launch_flags(c) & ~sjmi::DBG_NO_LOOKBACK) | sjmi::DBG_NO_WRITE, ex)))
-        return nullptr;
-    note_launch(c, st);
-    c->par_valid = true;
-    return c->d_blkpar;
-}
-}  // namespace
 
 // the streaming string pass over (d_buf, len); optional: record offsets by ordinal / ordinals by block
 // d_result == nullptr: the record inside the pass's workspace (zeroed with it: no memset of its own), returned in *used
@@ -517,7 +578,7 @@ static int strings_device_impl(sjmi_ctx* c, const void* d_buf, uint64_t len, voi
                                sjmi::UnescapeResult** used = nullptr, bool ws_is_zero = false) {
     const unsigned long long* par = parity_for(c, d_buf, len, st);
     if (!par) return SJMI_ERR_HIP;
-    if (!grow(c, &c->d_ws_strm, &c->ws_strm_bytes, sjmi::strings_workspace_bytes(len), "hipMalloc(ws_strm)")) return SJMI_ERR_HIP;
+    if (!grow(c, c->d_ws_strm, sjmi::strings_workspace_bytes(len), "hipMalloc(ws_strm)")) return SJMI_ERR_HIP;
     const bool own = d_result == nullptr;
     if (own) d_result = sjmi::strings_workspace_result(c->d_ws_strm);
     if (used) *used = (sjmi::UnescapeResult*)d_result;
@@ -541,10 +602,10 @@ static int strings_batch_impl(sjmi_ctx* c, const void* d_buf, uint64_t total_len
                               const uint32_t* d_accept, void* d_string_buffer, uint64_t string_capacity, void* d_doc_str_offsets,
                               void* d_result, hipStream_t st) {
     const uint64_t soff_cap = count_bound + 64;
-    if (!grow(c, (void**)&c->d_soff, &c->soff_bytes, soff_cap * sizeof(uint32_t), "hipMalloc(soff)") ||
-        !grow(c, (void**)&c->d_blk_ord, &c->blk_ord_bytes, (total_len / 64 + 2) * sizeof(uint32_t), "hipMalloc(blk_ord)") ||
-        !grow(c, (void**)&c->d_doc_ord, &c->doc_ord_bytes, (n_docs + 2) * sizeof(unsigned long long), "hipMalloc(doc_ord)") ||
-        !grow(c, &c->d_ws_strm, &c->ws_strm_bytes, sjmi::strings_workspace_bytes(total_len), "hipMalloc(ws_strm)"))
+    if (!grow(c, c->d_soff, soff_cap * sizeof(uint32_t), "hipMalloc(soff)") ||
+        !grow(c, c->d_blk_ord, (total_len / 64 + 2) * sizeof(uint32_t), "hipMalloc(blk_ord)") ||
+        !grow(c, c->d_doc_ord, (n_docs + 2) * sizeof(unsigned long long), "hipMalloc(doc_ord)") ||
+        !grow(c, c->d_ws_strm, sjmi::strings_workspace_bytes(total_len), "hipMalloc(ws_strm)"))
         return SJMI_ERR_HIP;
     c->soff_idx = nullptr;
     const uint8_t* buf0 = (const uint8_t*)d_buf;
@@ -558,20 +619,17 @@ static int strings_batch_impl(sjmi_ctx* c, const void* d_buf, uint64_t total_len
         par0 = c->d_blkpar;
     }
     if (!plain || d_accept) {
-        const int steps = c->forced_steps ? c->forced_steps : sjmi::stage1_pick_steps(total_len);
-        if (!grow(c, (void**)&c->d_copy, &c->copy_bytes, total_len + 2 * SJMI_PADDING + 64, "hipMalloc(copy)") ||
-            !grow(c, (void**)&c->d_blkpar2, &c->blkpar2_bytes, sjmi::strings_parity_words(total_len) * sizeof(unsigned long long), "hipMalloc(blkpar2)") ||
-            !grow(c, &c->d_ws_par, &c->ws_par_bytes, sjmi::stage1_workspace_bytes(total_len, steps), "hipMalloc(ws_par)"))
+        if (!grow(c, c->d_copy, total_len + 2 * SJMI_PADDING + 64, "hipMalloc(copy)") ||
+            !grow(c, c->d_blkpar2, sjmi::strings_parity_words(total_len) * sizeof(unsigned long long), "hipMalloc(blkpar2)") ||
+            !grow(c, c->d_ws_par, sjmi::stage1_workspace_bytes(total_len, stage1_steps(c, total_len)), "hipMalloc(ws_par)"))
             return SJMI_ERR_HIP;
         sjmi::Stage1Extras ex;
         ex.blkpar = c->d_blkpar2;
         ex.skip = d_accept;
         if (fail(c, "sanitize", sjmi::strings_sanitize_launch((const uint8_t*)d_buf, total_len, (const unsigned long long*)d_doc_offsets,
                                                               (const unsigned long long*)d_index_offsets, n_docs, c->d_copy, d_accept, st)) ||
-            fail(c, "parity launch", sjmi::stage1_launch(c->d_copy, total_len, nullptr, 0, c->d_ws_par, steps, st, nullptr, nullptr,
-                                                         (launch_flags(c) & ~sjmi::DBG_NO_LOOKBACK) | sjmi::DBG_NO_WRITE, ex)))
+            fail(c, "parity launch", parity_launch(c, c->d_copy, total_len, st, ex)))
             return SJMI_ERR_HIP;
-        note_launch(c, st);
         if (d_accept) {
             alt.d_sel = d_accept;
             alt.d_buf = c->d_copy;
@@ -590,7 +648,7 @@ static int strings_batch_impl(sjmi_ctx* c, const void* d_buf, uint64_t total_len
                                                c->d_soff, (const sjmi::UnescapeResult*)d_result, c->d_doc_ord,
                                                (unsigned long long*)d_doc_str_offsets, st, nullptr)))
         return SJMI_ERR_HIP;
-    if (!c->d_ures_walk && fail(c, "hipMalloc(ures_walk)", hipMalloc((void**)&c->d_ures_walk, sizeof(sjmi_unescape_result)))) return SJMI_ERR_HIP;
+    if (!grow(c, c->d_ures_walk, sizeof(sjmi_unescape_result), "hipMalloc(ures_walk)")) return SJMI_ERR_HIP;
     if (fail(c, "D2D(ures)", hipMemcpyAsync(c->d_ures_walk, d_result, sizeof(sjmi_unescape_result), hipMemcpyDeviceToDevice, st))) return SJMI_ERR_HIP;
     c->soff_idx = d_indexes;
     return SJMI_OK;
@@ -635,53 +693,12 @@ int sjmi_unescape_batch_device(sjmi_ctx* c, const void* d_buf, uint64_t total_le
     return unescape_device_impl(c, d_buf, total_len, d_indexes, count, d_string_buffer, string_capacity, d_result, stream, batch);
 }
 
-// host forms: the document / batch of the last stage-1 call on this context
-static int unescape_host(sjmi_ctx* c, uint8_t* string_buffer, uint64_t string_capacity, uint64_t* doc_string_offsets,
-                         uint64_t* total_bytes, uint64_t* first_error_index, uint32_t* first_error_code) {
-    if (fail(c, "hipSetDevice", hipSetDevice(c->device))) return SJMI_ERR_HIP;
-    const uint64_t n_docs = c->last_ndocs;
-    const size_t need_sb = (size_t)c->last_len + 4 * (size_t)c->last_count + 64;  // sum(4+len_k) <= len + 4*#strings
-    const size_t ob = (n_docs + 1) * sizeof(unsigned long long);
-    if (!grow(c, (void**)&c->d_sb, &c->sb_bytes, need_sb, "hipMalloc(sb)")) return SJMI_ERR_HIP;
-    if (doc_string_offsets && !grow(c, (void**)&c->d_docstr, &c->docstr_bytes, ob + 64, "hipMalloc(docstr)")) return SJMI_ERR_HIP;
-    if (!c->d_ures && fail(c, "hipMalloc(ures)", hipMalloc((void**)&c->d_ures, sizeof(sjmi_unescape_result))))
-        return SJMI_ERR_HIP;
-    sjmi::UnescapeBatch batch;
-    if (c->last_batch) {  // (also for a plain sjmi_unescape after a batch call: its strings end inside their documents)
-        batch.d_doc_offsets = c->d_docoff;
-        batch.d_index_offsets = c->d_docoff + (n_docs + 1);  // written by the batch call
-        batch.n_docs = n_docs;
-        batch.d_doc_str_offsets = doc_string_offsets ? c->d_docstr : nullptr;
-    }
-    const uint32_t* const idx_dev = c->idx_last ? c->idx_last : c->d_idx;
-    const int rc = unescape_device_impl(c, c->d_in, c->last_len, idx_dev, c->last_count, c->d_sb, c->sb_bytes, c->d_ures,
-                                        c->stream, batch);
-    if (rc != SJMI_OK) return rc;
-    sjmi_unescape_result r;
-    unsigned long long err_index = ~0ull;
-    const bool streamed = true;  // (the string pass reports the error's byte position: turn it into the string's index)
-    if (streamed) {
-        if (!c->d_err_index && fail(c, "hipMalloc(err_index)", hipMalloc((void**)&c->d_err_index, sizeof(unsigned long long))))
-            return SJMI_ERR_HIP;
-        if (fail(c, "error index", sjmi::strings_error_index_launch(idx_dev, c->last_count, nullptr, (const sjmi::UnescapeResult*)c->d_ures,
-                                                                    c->d_err_index, c->stream)) ||
-            fail(c, "D2H(err_index)", hipMemcpyAsync(&err_index, c->d_err_index, sizeof err_index, hipMemcpyDeviceToHost, c->stream)))
-            return SJMI_ERR_HIP;
-    }
-    if (fail(c, "D2H(ures)", hipMemcpyAsync(&r, c->d_ures, sizeof r, hipMemcpyDeviceToHost, c->stream)) ||
-        (doc_string_offsets &&
-         fail(c, "D2H(docstr)", hipMemcpyAsync(doc_string_offsets, c->d_docstr, ob, hipMemcpyDeviceToHost, c->stream))) ||
-        fail(c, "sync", hipStreamSynchronize(c->stream)))
-        return SJMI_ERR_HIP;
+// the string pass's record as the host forms report it (err_index: the failing string's position in indexes[])
+static int strings_rc(sjmi_ctx* c, const sjmi_unescape_result& r, unsigned long long err_index, uint64_t string_capacity,
+                      uint64_t* total_bytes, uint64_t* first_error_index, uint32_t* first_error_code) {
     *total_bytes = r.total_bytes;
-    if (r.first_error_inv) {
-        const uint64_t v = ~r.first_error_inv;
-        *first_error_index = streamed ? err_index : v >> 8;
-        *first_error_code = (uint32_t)(v & 0xFF);
-    } else {
-        *first_error_index = ~0ull;
-        *first_error_code = 0;
-    }
+    *first_error_index = r.first_error_inv ? err_index : ~0ull;
+    *first_error_code = r.first_error_inv ? (uint32_t)(~r.first_error_inv & 0xFF) : 0;
     if (r.flags & 0xCu) {
         c->err = "string pass: engine fault";
         return SJMI_ERR_INTERNAL;
@@ -690,6 +707,44 @@ static int unescape_host(sjmi_ctx* c, uint8_t* string_buffer, uint64_t string_ca
         c->err = "string_capacity too small";
         return SJMI_ERR_CAPACITY;
     }
+    return SJMI_OK;
+}
+
+// host forms: the document / batch of the last stage-1 call on this context
+static int unescape_host(sjmi_ctx* c, uint8_t* string_buffer, uint64_t string_capacity, uint64_t* doc_string_offsets,
+                         uint64_t* total_bytes, uint64_t* first_error_index, uint32_t* first_error_code) {
+    if (fail(c, "hipSetDevice", hipSetDevice(c->device))) return SJMI_ERR_HIP;
+    const uint64_t n_docs = c->last_ndocs;
+    const size_t need_sb = (size_t)c->last_len + 4 * (size_t)c->last_count + 64;  // sum(4+len_k) <= len + 4*#strings
+    const size_t ob = (n_docs + 1) * sizeof(unsigned long long);
+    if (!grow(c, c->d_sb, need_sb, "hipMalloc(sb)")) return SJMI_ERR_HIP;
+    if (doc_string_offsets && !grow(c, c->d_docstr, ob + 64, "hipMalloc(docstr)")) return SJMI_ERR_HIP;
+    if (!grow(c, c->d_ures, sizeof(sjmi_unescape_result), "hipMalloc(ures)")) return SJMI_ERR_HIP;
+    sjmi::UnescapeBatch batch;
+    if (c->last_batch) {  // (also for a plain sjmi_unescape after a batch call: its strings end inside their documents)
+        batch.d_doc_offsets = c->d_docoff;
+        batch.d_index_offsets = c->d_docoff + (n_docs + 1);  // written by the batch call
+        batch.n_docs = n_docs;
+        batch.d_doc_str_offsets = doc_string_offsets ? c->d_docstr : nullptr;
+    }
+    const uint32_t* const idx_dev = c->idx_last ? c->idx_last : c->d_idx;
+    const int rc = unescape_device_impl(c, c->d_in, c->last_len, idx_dev, c->last_count, c->d_sb, c->d_sb.bytes, c->d_ures,
+                                        c->stream, batch);
+    if (rc != SJMI_OK) return rc;
+    sjmi_unescape_result r;
+    unsigned long long err_index = ~0ull;
+    // (the string pass reports the error's byte position: turn it into the string's index)
+    if (!grow(c, c->d_err_index, sizeof(unsigned long long), "hipMalloc(err_index)") ||
+        fail(c, "error index", sjmi::strings_error_index_launch(idx_dev, c->last_count, nullptr, (const sjmi::UnescapeResult*)c->d_ures.p,
+                                                                c->d_err_index, c->stream)) ||
+        fail(c, "D2H(err_index)", hipMemcpyAsync(&err_index, c->d_err_index, sizeof err_index, hipMemcpyDeviceToHost, c->stream)) ||
+        fail(c, "D2H(ures)", hipMemcpyAsync(&r, c->d_ures, sizeof r, hipMemcpyDeviceToHost, c->stream)) ||
+        (doc_string_offsets &&
+         fail(c, "D2H(docstr)", hipMemcpyAsync(doc_string_offsets, c->d_docstr, ob, hipMemcpyDeviceToHost, c->stream))) ||
+        fail(c, "sync", hipStreamSynchronize(c->stream)))
+        return SJMI_ERR_HIP;
+    const int src = strings_rc(c, r, err_index, string_capacity, total_bytes, first_error_index, first_error_code);
+    if (src != SJMI_OK) return src;
     if (r.total_bytes &&
         (fail(c, "D2H(sb)", hipMemcpyAsync(string_buffer, c->d_sb, r.total_bytes, hipMemcpyDeviceToHost, c->stream)) ||
          fail(c, "sync", hipStreamSynchronize(c->stream))))
@@ -726,24 +781,16 @@ int sjmi_stage1_unescape(sjmi_ctx* c, const uint8_t* buf, uint64_t len, uint32_t
     if (!c || (!buf && len) || !indexes || !count || !status || !string_buffer || !total_bytes || !first_error_index ||
         !first_error_code)
         return SJMI_ERR_ARG;
-    if (len > c->capacity || len >= (1ull << 32)) {
-        c->err = "document larger than the context capacity";
-        return SJMI_ERR_CAPACITY;
-    }
+    if (too_large(c, len, "document")) return SJMI_ERR_CAPACITY;
     if (index_capacity < 1) return SJMI_ERR_CAPACITY;
     if (fail(c, "hipSetDevice", hipSetDevice(c->device))) return SJMI_ERR_HIP;
     // everything is queued before the first synchronisation: the unescape kernels take the structural count from the
     // stage-1 result on the device; grids and workspace are sized for the bound "one structural per byte"
-    const uint64_t bound = len + 1;
     const size_t need_sb = (size_t)len + 4 * ((size_t)len / 2 + 2) + 64;  // sum(4+len_k): every string takes >= 2 source bytes
-    (void)bound;
-    if (!grow(c, (void**)&c->d_sb, &c->sb_bytes, need_sb, "hipMalloc(sb)")) return SJMI_ERR_HIP;
-    if (!c->d_ures && fail(c, "hipMalloc(ures)", hipMalloc((void**)&c->d_ures, sizeof(sjmi_unescape_result))))
+    if (!grow(c, c->d_sb, need_sb, "hipMalloc(sb)") || !grow(c, c->d_ures, sizeof(sjmi_unescape_result), "hipMalloc(ures)"))
         return SJMI_ERR_HIP;
     if (!upload_document(c, buf, len)) return SJMI_ERR_HIP;
-    const int steps = c->forced_steps ? c->forced_steps : sjmi::stage1_pick_steps(len);
-    const uint64_t dev_cap = c->capacity + 2 < index_capacity ? c->capacity + 2 : index_capacity;
-    const sjmi::Stage1Result* d_res1 = (const sjmi::Stage1Result*)((uint8_t*)c->d_ws + sjmi::WS_RESULT_OFFSET);
+    const uint64_t dev_cap = dev_index_cap(c, index_capacity);
     // Latency path of the drop-in call: besides the two kernels only what cannot be avoided is queued -- stage 1 through the
     // device entry point (double-buffered workspace: no memset, the scanner writes the record), the string pass's record
     // inside its own workspace (zeroed with it), one 48-byte D2H of {error index, both records} instead of three copies.
@@ -756,14 +803,13 @@ int sjmi_stage1_unescape(sjmi_ctx* c, const uint8_t* buf, uint64_t len, uint32_t
     };
     static_assert(sizeof(Pack) == 48, "ParsePack layout");
     if (sjmi::strings_parse_pack_bytes() != sizeof(Pack)) return SJMI_ERR_INTERNAL;
-    if (!c->d_pack && fail(c, "hipMalloc(pack)", hipMalloc(&c->d_pack, 64))) return SJMI_ERR_HIP;
-    if (!c->h_pack && fail(c, "hipHostMalloc(pack)", hipHostMalloc(&c->h_pack, 64))) return SJMI_ERR_HIP;
-    if (!c->d_res_tmp && fail(c, "hipMalloc(result)", hipMalloc((void**)&c->d_res_tmp, 64))) return SJMI_ERR_HIP;
+    if (!grow(c, c->d_pack, 64, "hipMalloc(pack)") || !grow(c, c->h_pack, 64, "hipHostMalloc(pack)") ||
+        !grow(c, c->d_res_tmp, 64, "hipMalloc(result)"))
+        return SJMI_ERR_HIP;
     const uint64_t spec_idx = len + 2 < dev_cap ? len + 2 : dev_cap;
     const uint64_t sb_bound = len + 4 * (len / 2 + 2);
     const uint64_t spec_sb = string_buffer ? (sb_bound < string_capacity ? sb_bound : string_capacity) : 0;
     const bool small = len <= (4u << 10);
-    const AutoSafeOff own_retry(c);  // (the retry below is this call's own)
     // ZERO-COPY (both output arrays device-visible: a parser with page-locked buffers): stage 1 writes the indexes, the string
     // pass the records and the last small kernel the packed result records straight into the caller's / the context's pinned
     // memory -- no download, ONE host synchronisation (twitter.json: two copies of 221 + 440 KB and a round trip less)
@@ -772,19 +818,17 @@ int sjmi_stage1_unescape(sjmi_ctx* c, const uint8_t* buf, uint64_t len, uint32_t
     if (!c->h_pack_dev) c->h_pack_dev = device_view(c, c->h_pack);
     const bool zero_copy = zc_idx && zc_sb && c->h_pack_dev;
     uint32_t* const idx_out = zero_copy ? zc_idx : c->d_idx;
-    c->idx_last = idx_out;
-    c->idx_last_host = zero_copy ? indexes : nullptr;
-    for (int attempt = 0; attempt < 2; ++attempt) {
-        const int s1rc = stage1_device_impl(c, c->d_in, len, idx_out, dev_cap, c->d_res_tmp, c->stream, 0);
+    int rc = retry_in_safe_mode(c, c->h_res->status, [&] {
+        const int s1rc = stage1_device_impl(c, c->d_in, len, idx_out, dev_cap, c->d_res_tmp, c->stream);
         if (s1rc != SJMI_OK) return s1rc;
-        if (!grow(c, &c->d_ws_strm, &c->ws_strm_bytes, sjmi::strings_workspace_bytes(len), "hipMalloc(ws_strm)")) return SJMI_ERR_HIP;
+        if (!grow(c, c->d_ws_strm, sjmi::strings_workspace_bytes(len), "hipMalloc(ws_strm)")) return SJMI_ERR_HIP;
         const unsigned long long* par = parity_for(c, c->d_in, len, c->stream);
         if (!par) return SJMI_ERR_HIP;
         sjmi::UnescapeResult* d_u = sjmi::strings_workspace_result(c->d_ws_strm);
-        if (fail(c, "strings launch", sjmi::strings_launch(c->d_in, len, par, zero_copy ? zc_sb : c->d_sb, zero_copy ? string_capacity : c->sb_bytes,
+        if (fail(c, "strings launch", sjmi::strings_launch(c->d_in, len, par, zero_copy ? zc_sb : c->d_sb.p, zero_copy ? string_capacity : c->d_sb.bytes,
                                                            nullptr, 0, nullptr, c->d_ws_strm, d_u, c->stream)) ||
-            fail(c, "error index", sjmi::strings_error_index_pack_launch(idx_out, (const sjmi::Stage1Result*)c->d_res_tmp, d_u,
-                                                                         zero_copy ? c->h_pack_dev : c->d_pack, c->stream)) ||
+            fail(c, "error index", sjmi::strings_error_index_pack_launch(idx_out, (const sjmi::Stage1Result*)c->d_res_tmp.p, d_u,
+                                                                         zero_copy ? c->h_pack_dev : c->d_pack.p, c->stream)) ||
             (!zero_copy && fail(c, "D2H(results)", hipMemcpyAsync(c->h_pack, c->d_pack, sizeof(Pack), hipMemcpyDeviceToHost, c->stream))))
             return SJMI_ERR_HIP;
         // A SMALL document's outputs are downloaded speculatively, by their bounds (one structural per byte; 3 record bytes per
@@ -794,48 +838,23 @@ int sjmi_stage1_unescape(sjmi_ctx* c, const uint8_t* buf, uint64_t len, uint32_t
              (spec_sb && fail(c, "D2H(sb)", hipMemcpyAsync(string_buffer, c->d_sb, spec_sb, hipMemcpyDeviceToHost, c->stream)))))
             return SJMI_ERR_HIP;
         if (fail(c, "sync", hipStreamSynchronize(c->stream))) return SJMI_ERR_HIP;
-        const Pack* hp = static_cast<const Pack*>(c->h_pack);
+        const Pack* hp = static_cast<const Pack*>(c->h_pack.p);
         *c->h_res = hp->s1;
         r = hp->u;
         err_index = hp->err_index;
-        if (!(c->h_res->status & SJMI_ST_INTERNAL) || c->ticket_mode) break;
-        c->ticket_mode = true;  // fast-mode liveness assumption failed: latch the safe mode and run again
-    }
-    (void)d_res1;
+        return SJMI_OK;
+    });
+    if (rc != SJMI_OK) return rc;
     *status = c->h_res->status & 0xFFu;
     *count = c->h_res->count;
     *total_bytes = 0;
     *first_error_index = ~0ull;
     *first_error_code = 0;
-    if (c->h_res->status & SJMI_ST_INTERNAL) {
-        c->err = "look-back timeout";
-        return SJMI_ERR_INTERNAL;
-    }
-    if (c->h_res->status & SJMI_ST_CAPACITY) {
-        c->err = "index_capacity too small";
-        return SJMI_ERR_CAPACITY;
-    }
-    c->last_len = len;
-    c->last_count = c->h_res->count;
-    c->last_valid = true;
-    c->last_batch = false;
+    if ((rc = stage1_rc(c, c->h_res->status)) != SJMI_OK) return rc;
+    note_last(c, idx_out, zero_copy ? indexes : nullptr, len, c->h_res->count);
     const bool strings_ok = *status == 0;  // (a document that fails stage 1 has no meaningful strings: the caller throws)
-    if (strings_ok) {
-        *total_bytes = r.total_bytes;
-        if (r.first_error_inv) {
-            const uint64_t v = ~r.first_error_inv;
-            *first_error_index = err_index;
-            *first_error_code = (uint32_t)(v & 0xFF);
-        }
-        if (r.flags & 0xCu) {
-            c->err = "string pass: engine fault";
-            return SJMI_ERR_INTERNAL;
-        }
-        if (r.total_bytes > string_capacity || (r.flags & 1u)) {
-            c->err = "string_capacity too small";
-            return SJMI_ERR_CAPACITY;
-        }
-    }
+    if (strings_ok && (rc = strings_rc(c, r, err_index, string_capacity, total_bytes, first_error_index, first_error_code)) != SJMI_OK)
+        return rc;
     if (zero_copy) return SJMI_OK;  // (indexes and records are in the caller's arrays already)
     if (small && c->h_res->count + 1 <= spec_idx && (!strings_ok || r.total_bytes <= spec_sb)) return SJMI_OK;  // (already here)
     if (fail(c, "D2H(indexes)",
@@ -856,8 +875,7 @@ int sjmi_walk_batch_device(sjmi_ctx* c, const void* d_buf, const void* d_doc_off
         !d_doc_string_offsets || !d_tape || !d_tape_offsets || !d_doc_errors || !d_result || max_depth < 1)
         return SJMI_ERR_ARG;
     if (fail(c, "hipSetDevice", hipSetDevice(c->device))) return SJMI_ERR_HIP;
-    if (!grow(c, &c->d_ws_walk, &c->ws_walk_bytes, sjmi::walk_workspace_bytes(count, n_docs), "hipMalloc(ws_walk)"))
-        return SJMI_ERR_HIP;
+    if (!grow(c, c->d_ws_walk, sjmi::walk_workspace_bytes(count, n_docs), "hipMalloc(ws_walk)")) return SJMI_ERR_HIP;
     hipStream_t st = stream ? (hipStream_t)stream : c->stream;
     // The cooperative walker takes the offsets of the string records from the record table the string pass of THESE indexes
     // left on this context (sjmi_unescape_batch_device), and the ordinal of every document's first string with it.
@@ -865,27 +883,34 @@ int sjmi_walk_batch_device(sjmi_ctx* c, const void* d_buf, const void* d_doc_off
         c->err = "sjmi_walk_batch_device needs the sjmi_unescape_batch_device call of the same indexes on this context";
         return SJMI_ERR_ARG;
     }
-    if (fail(c, "walk launch",
-             sjmi::walk_launch((const uint8_t*)d_buf, (const unsigned long long*)d_doc_offsets, n_docs, (const uint32_t*)d_indexes,
-                               count, (const unsigned long long*)d_index_offsets, (const uint32_t*)d_doc_status,
-                               (const uint8_t*)d_string_buffer, c->d_doc_ord, string_base,
-                               max_depth, (unsigned long long*)d_tape, tape_capacity, (unsigned long long*)d_tape_offsets,
-                               (int32_t*)d_doc_errors, c->d_ws_walk, (sjmi::WalkResult*)d_result, st, nullptr,
-                               (const sjmi::UnescapeResult*)c->d_ures_walk, c->d_soff)))
-        return SJMI_ERR_HIP;
-    return SJMI_OK;
+    sjmi::WalkLaunch w;
+    w.d_buf = (const uint8_t*)d_buf;
+    w.d_doc_offsets = (const unsigned long long*)d_doc_offsets;
+    w.n_docs = n_docs;
+    w.d_idx = (const uint32_t*)d_indexes;
+    w.count = count;
+    w.d_index_offsets = (const unsigned long long*)d_index_offsets;
+    w.d_doc_status = (const uint32_t*)d_doc_status;
+    w.d_sb = (const uint8_t*)d_string_buffer;
+    w.d_doc_str_ordinals = c->d_doc_ord;
+    w.string_base = string_base;
+    w.max_depth = max_depth;
+    w.d_tape = (unsigned long long*)d_tape;
+    w.tape_capacity = tape_capacity;
+    w.d_tape_offsets = (unsigned long long*)d_tape_offsets;
+    w.d_doc_errors = (int32_t*)d_doc_errors;
+    w.d_ws = c->d_ws_walk;
+    w.d_res = (sjmi::WalkResult*)d_result;
+    w.dev_strings = (const sjmi::UnescapeResult*)c->d_ures_walk.p;
+    w.d_soff = c->d_soff;
+    return fail(c, "walk launch", sjmi::walk_launch(w, st)) ? SJMI_ERR_HIP : SJMI_OK;
 }
-
-static int stage1_device_impl(sjmi_ctx* c, const void* d_buf, uint64_t len, void* d_indexes, uint64_t index_capacity,
-                              void* d_result, void* stream, uint32_t shard_flags);
 
 int sjmi_stage1_device(sjmi_ctx* c, const void* d_buf, uint64_t len, void* d_indexes, uint64_t index_capacity,
                        void* d_result, void* stream) {
-    return stage1_device_impl(c, d_buf, len, d_indexes, index_capacity, d_result, stream, 0);
+    return stage1_device_impl(c, d_buf, len, d_indexes, index_capacity, d_result, stream);
 }
 
-int sjmi_stage1_shard_device2(sjmi_ctx* c, const void* d_buf, uint64_t len, uint64_t halo_bytes, int halo_from_document_start,
-                              int is_last, int entry_parity, void* d_indexes, uint64_t index_capacity, void* d_result, void* stream);
 int sjmi_stage1_shard_device(sjmi_ctx* c, const void* d_buf, uint64_t len, uint64_t halo_bytes, int is_last, int entry_parity,
                              void* d_indexes, uint64_t index_capacity, void* d_result, void* stream) {
     return sjmi_stage1_shard_device2(c, d_buf, len, halo_bytes, 0, is_last, entry_parity, d_indexes, index_capacity, d_result, stream);
@@ -896,90 +921,10 @@ int sjmi_stage1_shard_device2(sjmi_ctx* c, const void* d_buf, uint64_t len, uint
     // a shard that is not the last one ends on a block boundary (its successor owns what straddles it); the halo is
     // whole blocks so that the shard itself stays 16-byte aligned
     if ((halo_bytes & 63) || halo_bytes > 65535ull * 64 || (!is_last && (len & 63)) || (!is_last && len == 0)) return SJMI_ERR_ARG;
-    const uint32_t flags = ((uint32_t)(halo_bytes / 64) << 16) | (is_last ? 0u : sjmi::FLAG_NO_TAIL) |
-                           (entry_parity ? sjmi::FLAG_ENTRY_PARITY : 0u) | (halo_from_document_start ? sjmi::FLAG_HALO_FROM_START : 0u);
-    return stage1_device_impl(c, d_buf, len, d_indexes, index_capacity, d_result, stream, flags);
-}
-
-static int stage1_device_impl(sjmi_ctx* c, const void* d_buf, uint64_t len, void* d_indexes, uint64_t index_capacity,
-                              void* d_result, void* stream, uint32_t shard_flags) {
-    if (!c || !d_buf || !d_indexes || !d_result) return SJMI_ERR_ARG;
-    if (len >= (1ull << 32) || ((uintptr_t)d_buf & 15) || ((uintptr_t)d_indexes & 15)) return SJMI_ERR_ARG;
-    if (fail(c, "hipSetDevice", hipSetDevice(c->device))) return SJMI_ERR_HIP;
-    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
-    const int steps = c->forced_steps ? c->forced_steps : sjmi::stage1_pick_steps(len);
-    const size_t need = (sjmi::stage1_workspace_bytes(len, steps) + 255) & ~(size_t)255;
-    if (2 * need > c->ws_dev_bytes) {  // grown outside any timed loop on first use of a given size
-        if (c->d_ws_dev) (void)hipFree(c->d_ws_dev);
-        c->d_ws_dev = nullptr;
-        c->ws_dev_bytes = 0;
-        if (fail(c, "hipMalloc(ws_dev)", hipMalloc(&c->d_ws_dev, 2 * need))) return SJMI_ERR_HIP;
-        c->ws_dev_bytes = 2 * need;
-        c->ws_dev_clean[0] = c->ws_dev_clean[1] = 0;
-    }
-    // Nothing but the kernel is queued once the context is warm: this launch finds its half of the workspace zeroed
-    // by the previous one, zeroes the other half for the next one, and its last wave writes *d_result.
-    // (One launch stream per context at a time: the halves are handed over in stream order.)
-    const size_t half = c->ws_dev_bytes / 2;
-    const int h = c->ws_dev_next;
-    uint8_t* ws = (uint8_t*)c->d_ws_dev + (size_t)h * half;
-    const bool fast = !(launch_flags(c) & (sjmi::FLAG_SAFE | sjmi::DBG_NO_LOOKBACK));  // (the scanner writes the result)
-    sjmi::Stage1Extras ex;
-    ex.workspace_is_zero = c->ws_dev_clean[h] >= need;
-    ex.zero_next = (uint8_t*)c->d_ws_dev + (size_t)(1 - h) * half;
-    ex.zero_bytes = need;
-    ex.result_out = fast ? d_result : nullptr;
-    ex.blkpar = shard_flags ? nullptr : parity_out(c, d_buf, len);
-    if (shard_flags) c->par_valid = false;
-    ex.zero2 = c->s1_zero2;
-    ex.zero2_bytes = c->s1_zero2_bytes;
-    if (fast) ex.single = c->s1_single;
-    c->s1_single_done = fast && c->s1_single.index_offsets != nullptr;
-    if (c->batch_side && !shard_flags) {  // (the fused batch pipeline's plain pass: per-block index positions and tape words)
-        const size_t entries = sjmi::stage1_block_entries(len);
-        if (!grow(c, (void**)&c->d_blkidx, &c->blkidx_bytes, entries * sizeof(uint32_t), "hipMalloc(blkidx)") ||
-            !grow(c, (void**)&c->d_blkw, &c->blkw_bytes, entries * sizeof(uint16_t), "hipMalloc(blkw)"))
-            return SJMI_ERR_HIP;
-        ex.blkidx = c->d_blkidx;
-        ex.blkw = c->d_blkw;
-    }
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    if (c->profiling) {
-        if (c->events_used == c->events.size()) {
-            hipEvent_t a, b;
-            if (fail(c, "hipEventCreate", hipEventCreate(&a)) || fail(c, "hipEventCreate", hipEventCreate(&b)))
-                return SJMI_ERR_HIP;
-            c->events.emplace_back(a, b);
-        }
-        ev0 = c->events[c->events_used].first;
-        ev1 = c->events[c->events_used].second;
-        ++c->events_used;
-    }
-    if (fail(c, "launch", sjmi::stage1_launch((const uint8_t*)d_buf, len, (uint32_t*)d_indexes, index_capacity, ws, steps,
-                                              st, ev0, ev1, launch_flags(c) | shard_flags, ex)))
-        return SJMI_ERR_HIP;
-    note_launch(c, st);
-    if (!fast && fail(c, "D2D(result)", hipMemcpyAsync(d_result, ws + sjmi::WS_RESULT_OFFSET, sizeof(sjmi_stage1_result),
-                                                       hipMemcpyDeviceToDevice, st)))
-        return SJMI_ERR_HIP;
-    c->ws_dev_clean[h] = 0;
-    c->ws_dev_clean[1 - h] = need;
-    c->ws_dev_next = 1 - h;
-    c->ws_dev_last = ws;
-    if (c->auto_safe && !c->ticket_mode) {
-        // opt-in (sjmi_set_auto_safe): the FAST kernel's liveness rests on its whole grid being resident; a caller that
-        // shares the GPU with other kernels can ask for the check here -- one synchronisation per launch -- instead of
-        // finding SJMI_ST_INTERNAL in its result record: on a tripped spin bound SAFE mode is latched and the launch repeated
-        sjmi_stage1_result r;
-        if (fail(c, "D2H(result)", hipMemcpyAsync(&r, d_result, sizeof r, hipMemcpyDeviceToHost, st)) ||
-            fail(c, "sync", hipStreamSynchronize(st)))
-            return SJMI_ERR_HIP;
-        if (r.status & SJMI_ST_INTERNAL) {
-            c->ticket_mode = true;
-            return stage1_device_impl(c, d_buf, len, d_indexes, index_capacity, d_result, stream, shard_flags);
-        }
-    }
-    return SJMI_OK;
+    Stage1Opts o;
+    o.shard_flags = ((uint32_t)(halo_bytes / 64) << 16) | (is_last ? 0u : sjmi::FLAG_NO_TAIL) |
+                    (entry_parity ? sjmi::FLAG_ENTRY_PARITY : 0u) | (halo_from_document_start ? sjmi::FLAG_HALO_FROM_START : 0u);
+    return stage1_device_impl(c, d_buf, len, d_indexes, index_capacity, d_result, stream, &o);
 }
 
 int sjmi_stage1_masks_device(sjmi_ctx* c, const void* d_buf, uint64_t len, void* d_masks, uint64_t mask_capacity_blocks,
@@ -987,7 +932,7 @@ int sjmi_stage1_masks_device(sjmi_ctx* c, const void* d_buf, uint64_t len, void*
     if (!c || !d_buf || !d_masks || len >= (1ull << 32) || ((uintptr_t)d_buf & 15) || ((uintptr_t)d_masks & 7)) return SJMI_ERR_ARG;
     if (mask_capacity_blocks < len / 64 + 1) return SJMI_ERR_CAPACITY;
     if (fail(c, "hipSetDevice", hipSetDevice(c->device))) return SJMI_ERR_HIP;
-    if (!grow(c, &c->d_ws_masks, &c->ws_masks_bytes, sjmi::masks_workspace_bytes(len), "hipMalloc(ws_masks)")) return SJMI_ERR_HIP;
+    if (!grow(c, c->d_ws_masks, sjmi::masks_workspace_bytes(len), "hipMalloc(ws_masks)")) return SJMI_ERR_HIP;
     hipStream_t st = stream ? (hipStream_t)stream : c->stream;
     if (fail(c, "masks launch", sjmi::masks_launch((const uint8_t*)d_buf, len, (unsigned long long*)d_masks, c->d_ws_masks, st)))
         return SJMI_ERR_HIP;
@@ -997,14 +942,11 @@ int sjmi_stage1_masks_device(sjmi_ctx* c, const void* d_buf, uint64_t len, void*
 int sjmi_stage1_masks(sjmi_ctx* c, const uint8_t* buf, uint64_t len, uint64_t* masks, uint64_t mask_capacity_blocks,
                       uint64_t* n_blocks) {
     if (!c || (!buf && len) || !masks || !n_blocks) return SJMI_ERR_ARG;
-    if (len > c->capacity || len >= (1ull << 32)) {
-        c->err = "document larger than the context capacity";
-        return SJMI_ERR_CAPACITY;
-    }
+    if (too_large(c, len, "document")) return SJMI_ERR_CAPACITY;
     const uint64_t nblocks = len / 64 + 1;
     if (mask_capacity_blocks < nblocks) return SJMI_ERR_CAPACITY;
     if (fail(c, "hipSetDevice", hipSetDevice(c->device))) return SJMI_ERR_HIP;
-    if (!grow(c, &c->d_masks, &c->masks_bytes, (size_t)nblocks * 48, "hipMalloc(masks)")) return SJMI_ERR_HIP;
+    if (!grow(c, c->d_masks, (size_t)nblocks * 48, "hipMalloc(masks)")) return SJMI_ERR_HIP;
     if (len && fail(c, "H2D", hipMemcpyAsync(c->d_in, buf, len, hipMemcpyHostToDevice, c->stream))) return SJMI_ERR_HIP;
     c->last_valid = false;  // (the context's document buffer now holds this document, without indexes)
     c->par_valid = false;   // (... and without block parities: new bytes under the same pointer)
@@ -1037,59 +979,66 @@ int sjmi_stage1_batch(sjmi_ctx* c, const uint8_t* buf, uint64_t total_len, const
                       uint32_t* indexes, uint64_t index_capacity, uint64_t* index_offsets, uint64_t* count,
                       uint32_t* status) {
     if (!c || (!buf && total_len) || !doc_offsets || !indexes || !index_offsets || !count || !status) return SJMI_ERR_ARG;
-    if (total_len > c->capacity || total_len >= (1ull << 32)) {
-        c->err = "batch larger than the context capacity";
-        return SJMI_ERR_CAPACITY;
-    }
+    if (too_large(c, total_len, "batch")) return SJMI_ERR_CAPACITY;
     if (bad_offsets(c, doc_offsets, n_docs, total_len, false)) return SJMI_ERR_ARG;
     if (fail(c, "hipSetDevice", hipSetDevice(c->device))) return SJMI_ERR_HIP;
     const size_t ob = (n_docs + 1) * sizeof(unsigned long long);
-    if (!grow(c, (void**)&c->d_docoff, &c->docoff_bytes, 2 * ob + 64, "hipMalloc(docoff)")) return SJMI_ERR_HIP;
+    if (!grow(c, c->d_docoff, 2 * ob + 64, "hipMalloc(docoff)")) return SJMI_ERR_HIP;
     unsigned long long* d_io = c->d_docoff + (n_docs + 1);
-    void* d_res = (uint8_t*)c->d_ws + sjmi::WS_RESULT_OFFSET;
+    void* d_res = (uint8_t*)c->d_ws.p + sjmi::WS_RESULT_OFFSET;
     if ((total_len && fail(c, "H2D", hipMemcpyAsync(c->d_in, buf, total_len, hipMemcpyHostToDevice, c->stream))) ||
         fail(c, "H2D(offsets)", hipMemcpyAsync(c->d_docoff, doc_offsets, ob, hipMemcpyHostToDevice, c->stream)))
         return SJMI_ERR_HIP;
-    const int steps = c->forced_steps ? c->forced_steps : sjmi::stage1_pick_steps(total_len);
-    const uint64_t dev_cap = c->capacity + 2 < index_capacity ? c->capacity + 2 : index_capacity;
+    const uint64_t dev_cap = dev_index_cap(c, index_capacity);
     sjmi::Stage1Extras ex1;
     ex1.blkpar = parity_out(c, c->d_in, total_len);
-    for (int attempt = 0; attempt < 2; ++attempt) {
-        if (fail(c, "launch", sjmi::stage1_launch(c->d_in, total_len, c->d_idx, dev_cap, c->d_ws, steps, c->stream, nullptr,
-                                                  nullptr, launch_flags(c), ex1)) ||
+    int rc = retry_in_safe_mode(c, c->h_res->status, [&] {
+        if (fail(c, "launch", sjmi::stage1_launch(c->d_in, total_len, c->d_idx, dev_cap, c->d_ws, stage1_steps(c, total_len), c->stream,
+                                                  nullptr, nullptr, launch_flags(c), ex1)) ||
             fail(c, "split", sjmi::split_docs_launch(c->d_idx, (const sjmi::Stage1Result*)d_res, c->d_docoff, n_docs, d_io,
                                                      c->stream)) ||
             fail(c, "D2H(result)", hipMemcpyAsync(c->h_res, d_res, sizeof(sjmi_stage1_result), hipMemcpyDeviceToHost, c->stream)) ||
             fail(c, "D2H(io)", hipMemcpyAsync(index_offsets, d_io, ob, hipMemcpyDeviceToHost, c->stream)) ||
             fail(c, "sync", hipStreamSynchronize(c->stream)))
             return SJMI_ERR_HIP;
-        if (!(c->h_res->status & SJMI_ST_INTERNAL) || c->ticket_mode) break;
-        c->ticket_mode = true;  // fast-mode liveness assumption failed: latch the safe mode and run again
-    }
+        return SJMI_OK;
+    });
+    if (rc != SJMI_OK) return rc;
     *status = c->h_res->status & 0xFFu;
     *count = c->h_res->count;
-    if (c->h_res->status & SJMI_ST_INTERNAL) return SJMI_ERR_INTERNAL;
-    if (c->h_res->status & SJMI_ST_CAPACITY) return SJMI_ERR_CAPACITY;
+    if ((rc = stage1_rc(c, c->h_res->status)) != SJMI_OK) return rc;
     if (fail(c, "D2H(indexes)", hipMemcpyAsync(indexes, c->d_idx, (c->h_res->count + 1) * sizeof(uint32_t),
                                                hipMemcpyDeviceToHost, c->stream)) ||
         fail(c, "sync", hipStreamSynchronize(c->stream)))
         return SJMI_ERR_HIP;
-    c->idx_last = c->d_idx;  // (a batch call's indexes are always in the context's own array, never in a caller's zero-copy view)
-    c->idx_last_host = nullptr;
-    c->last_len = total_len;
-    c->last_count = c->h_res->count;
-    c->last_valid = true;
-    c->last_ndocs = n_docs;
-    c->last_batch = true;
+    // (a batch call's indexes are always in the context's own array, never in a caller's zero-copy view)
+    note_last(c, c->d_idx, nullptr, total_len, c->h_res->count, true, n_docs);
     return SJMI_OK;
 }
 
 static int stage1_batch_isolated_device_impl(sjmi_ctx* c, const void* d_buf, uint64_t total_len, const void* d_doc_offsets,
                                              uint64_t n_docs, void* d_indexes, uint64_t index_capacity, void* d_index_offsets,
-                                             void* d_doc_status, void* d_result, void* stream, const uint32_t* d_skip);
-static int stage1_batch_isolated_device_impl(sjmi_ctx* c, const void* d_buf, uint64_t total_len, const void* d_doc_offsets,
-                                             uint64_t n_docs, void* d_indexes, uint64_t index_capacity, void* d_index_offsets,
-                                             void* d_doc_status, void* d_result, void* stream, const uint32_t* d_skip);
+                                             void* d_doc_status, void* d_result, void* stream, const uint32_t* d_skip) {
+    if (!c || !d_buf || !d_doc_offsets || !d_indexes || !d_index_offsets || !d_doc_status || !d_result) return SJMI_ERR_ARG;
+    if (total_len >= (1ull << 32)) return SJMI_ERR_ARG;
+    if (fail(c, "hipSetDevice", hipSetDevice(c->device))) return SJMI_ERR_HIP;
+    if (!grow(c, c->d_doccnt, sjmi::batch_isolated_workspace_bytes(n_docs), "hipMalloc(doccnt)")) return SJMI_ERR_HIP;
+    if (!d_skip) {
+        // no plain pass in front of these per-document passes (switched off, misaligned buffers, an empty batch): block
+        // parities / an acceptance flag recorded for the same pointer and length by an EARLIER launch describe other bytes;
+        // the string pass of this batch must take the sanitized copy, not them
+        c->par_valid = false;
+        c->accept_valid = false;
+    }
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    if (fail(c, "isolated batch launch",
+             sjmi::batch_isolated_launch((const uint8_t*)d_buf, (const unsigned long long*)d_doc_offsets, n_docs,
+                                         (uint32_t*)d_indexes, index_capacity, (unsigned long long*)d_index_offsets,
+                                         (uint32_t*)d_doc_status, c->d_doccnt, (sjmi::Stage1Result*)d_result, st, total_len, d_skip)))
+        return SJMI_ERR_HIP;
+    return SJMI_OK;
+}
+
 // Stage 1 of a batch with per-document verdicts.  Optimistic: ONE plain k_stage1 launch over the packed batch, accepted on the
 // device when every document ends in a control-character separator, the documents cover the buffer exactly and the global
 // verdict is clean (batch.hip: then it is exactly what the per-document passes give); the per-document passes are queued behind
@@ -1107,20 +1056,20 @@ static int stage1_batch_optimistic(sjmi_ctx* c, const void* d_buf, uint64_t tota
     c->accept_valid = false;
     if (optimistic && n_docs && total_len && index_capacity >= 1 && !((uintptr_t)d_buf & 15) && !((uintptr_t)d_indexes & 15)) {
         if (fail(c, "hipSetDevice", hipSetDevice(c->device))) return SJMI_ERR_HIP;
-        if (!c->d_batch_flags && fail(c, "hipMalloc(batch flags)", hipMalloc((void**)&c->d_batch_flags, 64))) return SJMI_ERR_HIP;
+        if (!grow(c, c->d_batch_flags, 64, "hipMalloc(batch flags)")) return SJMI_ERR_HIP;
         if (fail(c, "separator check", sjmi::batch_plain_check_launch((const uint8_t*)d_buf, (const unsigned long long*)d_doc_offsets,
                                                                       n_docs, total_len, c->d_batch_flags, st0)))
             return SJMI_ERR_HIP;
         int rc0;
         {
             const AutoSafeOff plain_only(c);  // (a tripped liveness bound only rejects the plain pass: the per-document passes take over)
-            rc0 = stage1_device_impl(c, d_buf, total_len, d_indexes, index_capacity, d_result, stream, 0);
+            rc0 = stage1_device_impl(c, d_buf, total_len, d_indexes, index_capacity, d_result, stream);
         }
         if (rc0 != SJMI_OK) return rc0;
         // (a FAST launch leaves the scanner's per-granule prefixes in its half of the workspace: the split starts from them)
         sjmi::Stage1Prefixes hint;
         if (!(launch_flags(c) & (sjmi::FLAG_SAFE | sjmi::DBG_NO_LOOKBACK)) && c->ws_dev_last)
-            hint = sjmi::stage1_prefixes(c->ws_dev_last, total_len, c->forced_steps ? c->forced_steps : sjmi::stage1_pick_steps(total_len));
+            hint = sjmi::stage1_prefixes(c->ws_dev_last, total_len, stage1_steps(c, total_len));
         if (fail(c, "plain accept", sjmi::batch_plain_accept_launch((const uint32_t*)d_indexes, (const sjmi::Stage1Result*)d_result,
                                                                     (const unsigned long long*)d_doc_offsets, n_docs,
                                                                     (unsigned long long*)d_index_offsets, (uint32_t*)d_doc_status,
@@ -1147,54 +1096,25 @@ int sjmi_stage1_batch_isolated_device(sjmi_ctx* c, const void* d_buf, uint64_t t
     return stage1_batch_optimistic(c, d_buf, total_len, d_doc_offsets, n_docs, d_indexes, index_capacity, d_index_offsets, d_doc_status,
                                    d_result, stream, &d_skip);
 }
-static int stage1_batch_isolated_device_impl(sjmi_ctx* c, const void* d_buf, uint64_t total_len, const void* d_doc_offsets,
-                                             uint64_t n_docs, void* d_indexes, uint64_t index_capacity, void* d_index_offsets,
-                                             void* d_doc_status, void* d_result, void* stream, const uint32_t* d_skip) {
-    if (!c || !d_buf || !d_doc_offsets || !d_indexes || !d_index_offsets || !d_doc_status || !d_result) return SJMI_ERR_ARG;
-    if (total_len >= (1ull << 32)) return SJMI_ERR_ARG;
-    if (fail(c, "hipSetDevice", hipSetDevice(c->device))) return SJMI_ERR_HIP;
-    if (!grow(c, (void**)&c->d_doccnt, &c->doccnt_bytes, sjmi::batch_isolated_workspace_bytes(n_docs), "hipMalloc(doccnt)"))
-        return SJMI_ERR_HIP;
-    if (!d_skip) {
-        // no plain pass in front of these per-document passes (switched off, misaligned buffers, an empty batch): block
-        // parities / an acceptance flag recorded for the same pointer and length by an EARLIER launch describe other bytes;
-        // the string pass of this batch must take the sanitized copy, not them
-        c->par_valid = false;
-        c->accept_valid = false;
-    }
-    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
-    if (fail(c, "isolated batch launch",
-             sjmi::batch_isolated_launch((const uint8_t*)d_buf, (const unsigned long long*)d_doc_offsets, n_docs,
-                                         (uint32_t*)d_indexes, index_capacity, (unsigned long long*)d_index_offsets,
-                                         (uint32_t*)d_doc_status, c->d_doccnt, (sjmi::Stage1Result*)d_result, st, total_len, d_skip)))
-        return SJMI_ERR_HIP;
-    return SJMI_OK;
-}
-
 int sjmi_stage1_batch_isolated(sjmi_ctx* c, const uint8_t* buf, uint64_t total_len, const uint64_t* doc_offsets,
                                uint64_t n_docs, uint32_t* indexes, uint64_t index_capacity, uint64_t* index_offsets,
                                uint32_t* doc_status, uint64_t* count, uint32_t* status) {
     if (!c || (!buf && total_len) || !doc_offsets || !indexes || !index_offsets || !doc_status || !count || !status)
         return SJMI_ERR_ARG;
-    if (total_len > c->capacity || total_len >= (1ull << 32)) {
-        c->err = "batch larger than the context capacity";
-        return SJMI_ERR_CAPACITY;
-    }
+    if (too_large(c, total_len, "batch")) return SJMI_ERR_CAPACITY;
     if (bad_offsets(c, doc_offsets, n_docs, total_len, false)) return SJMI_ERR_ARG;
     if (fail(c, "hipSetDevice", hipSetDevice(c->device))) return SJMI_ERR_HIP;
     const size_t ob = (n_docs + 1) * sizeof(unsigned long long);
     // document offsets | index offsets | document statuses
-    if (!grow(c, (void**)&c->d_docoff, &c->docoff_bytes, 2 * ob + (n_docs + 16) * sizeof(uint32_t) + 64, "hipMalloc(docoff)"))
-        return SJMI_ERR_HIP;
+    if (!grow(c, c->d_docoff, 2 * ob + (n_docs + 16) * sizeof(uint32_t) + 64, "hipMalloc(docoff)")) return SJMI_ERR_HIP;
     unsigned long long* d_io = c->d_docoff + (n_docs + 1);
     uint32_t* d_st = reinterpret_cast<uint32_t*>(c->d_docoff + 2 * (n_docs + 1));
-    void* d_res = (uint8_t*)c->d_ws + sjmi::WS_RESULT_OFFSET;
+    void* d_res = (uint8_t*)c->d_ws.p + sjmi::WS_RESULT_OFFSET;
     if ((total_len && fail(c, "H2D", hipMemcpyAsync(c->d_in, buf, total_len, hipMemcpyHostToDevice, c->stream))) ||
         fail(c, "H2D(offsets)", hipMemcpyAsync(c->d_docoff, doc_offsets, ob, hipMemcpyHostToDevice, c->stream)))
         return SJMI_ERR_HIP;
-    const uint64_t dev_cap = c->capacity + 2 < index_capacity ? c->capacity + 2 : index_capacity;
-    const int rc = sjmi_stage1_batch_isolated_device(c, c->d_in, total_len, c->d_docoff, n_docs, c->d_idx, dev_cap, d_io, d_st,
-                                                     d_res, c->stream);
+    int rc = sjmi_stage1_batch_isolated_device(c, c->d_in, total_len, c->d_docoff, n_docs, c->d_idx, dev_index_cap(c, index_capacity),
+                                               d_io, d_st, d_res, c->stream);
     if (rc != SJMI_OK) return rc;
     if (fail(c, "D2H(result)", hipMemcpyAsync(c->h_res, d_res, sizeof(sjmi_stage1_result), hipMemcpyDeviceToHost, c->stream)) ||
         fail(c, "D2H(io)", hipMemcpyAsync(index_offsets, d_io, ob, hipMemcpyDeviceToHost, c->stream)) ||
@@ -1203,18 +1123,13 @@ int sjmi_stage1_batch_isolated(sjmi_ctx* c, const uint8_t* buf, uint64_t total_l
         return SJMI_ERR_HIP;
     *status = c->h_res->status & 0xFFu;
     *count = c->h_res->count;
-    if (c->h_res->status & SJMI_ST_CAPACITY) return SJMI_ERR_CAPACITY;
+    // (SJMI_ST_INTERNAL here is a document's verdict -- an offset range the per-document passes clip -- not a look-back timeout)
+    if ((rc = stage1_rc(c, c->h_res->status & ~SJMI_ST_INTERNAL)) != SJMI_OK) return rc;
     if (fail(c, "D2H(indexes)", hipMemcpyAsync(indexes, c->d_idx, (c->h_res->count + 1) * sizeof(uint32_t),
                                                hipMemcpyDeviceToHost, c->stream)) ||
         fail(c, "sync", hipStreamSynchronize(c->stream)))
         return SJMI_ERR_HIP;
-    c->idx_last = c->d_idx;  // (a batch call's indexes are always in the context's own array, never in a caller's zero-copy view)
-    c->idx_last_host = nullptr;
-    c->last_len = total_len;
-    c->last_count = c->h_res->count;
-    c->last_valid = true;
-    c->last_ndocs = n_docs;
-    c->last_batch = true;
+    note_last(c, c->d_idx, nullptr, total_len, c->h_res->count, true, n_docs);
     return SJMI_OK;
 }
 
@@ -1269,8 +1184,26 @@ static int parse_batch_pipeline(sjmi_ctx* c, const void* d_buf, uint64_t total_l
     // on across a boundary without a separator, a document ending in a backslash) comes back with SJMI_ST_REJECTED once more and is
     // the exact call's -- stage C's ~20 queue entries (100 us of kernels that leave at once) stay off the repaired batch's path
     const bool repair_only = mode == PIPE_REJECTED && try_repair;
-    if (!grow(c, &c->d_ws_walk, &c->ws_walk_bytes, sjmi::walk_workspace_bytes(bound, n_docs), "hipMalloc(ws_walk)")) return SJMI_ERR_HIP;
+    if (!grow(c, c->d_ws_walk, sjmi::walk_workspace_bytes(bound, n_docs), "hipMalloc(ws_walk)")) return SJMI_ERR_HIP;
     c->accept_valid = false;
+    sjmi::WalkLaunch w;
+    w.d_buf = (const uint8_t*)d_buf;
+    w.d_doc_offsets = (const unsigned long long*)d_doc_offsets;
+    w.n_docs = n_docs;
+    w.d_idx = (const uint32_t*)d_indexes;
+    w.count = bound;
+    w.d_index_offsets = (const unsigned long long*)d_index_offsets;
+    w.d_doc_status = (const uint32_t*)d_doc_status;
+    w.d_sb = (const uint8_t*)d_string_buffer;
+    w.max_depth = max_depth;
+    w.d_tape = (unsigned long long*)d_tape;
+    w.tape_capacity = tape_capacity;
+    w.d_tape_offsets = (unsigned long long*)d_tape_offsets;
+    w.d_doc_errors = (int32_t*)d_doc_errors;
+    w.d_ws = c->d_ws_walk;
+    w.d_res = (sjmi::WalkResult*)&r->walk;
+    w.dev_count = (const sjmi::Stage1Result*)&r->stage1;
+    w.dev_strings = (const sjmi::UnescapeResult*)&r->strings;
     if (!try_plain && !try_repair) {
         if (optimistic_only) {  // (nothing the optimistic pipeline could run on: say so in the record)
             if (fail(c, "reject", sjmi::batch_reject_launch((sjmi::Stage1Result*)&r->stage1, st))) return SJMI_ERR_HIP;
@@ -1283,22 +1216,16 @@ static int parse_batch_pipeline(sjmi_ctx* c, const void* d_buf, uint64_t total_l
         rc = strings_batch_impl(c, d_buf, total_len, d_indexes, bound, d_doc_offsets, d_index_offsets, n_docs, false, nullptr, d_string_buffer,
                                 string_capacity, d_doc_string_offsets, &r->strings, st);
         if (rc != SJMI_OK) return rc;
-        if (fail(c, "walk launch",
-                 sjmi::walk_launch((const uint8_t*)d_buf, (const unsigned long long*)d_doc_offsets, n_docs, (const uint32_t*)d_indexes,
-                                   bound, (const unsigned long long*)d_index_offsets, (const uint32_t*)d_doc_status,
-                                   (const uint8_t*)d_string_buffer, c->d_doc_ord, 0, max_depth, (unsigned long long*)d_tape, tape_capacity,
-                                   (unsigned long long*)d_tape_offsets, (int32_t*)d_doc_errors, c->d_ws_walk, (sjmi::WalkResult*)&r->walk, st,
-                                   (const sjmi::Stage1Result*)&r->stage1, (const sjmi::UnescapeResult*)&r->strings, c->d_soff)))
-            return SJMI_ERR_HIP;
-        return SJMI_OK;
+        w.d_doc_str_ordinals = c->d_doc_ord;
+        w.d_soff = c->d_soff;
+        return fail(c, "walk launch", sjmi::walk_launch(w, st)) ? SJMI_ERR_HIP : SJMI_OK;
     }
     const size_t strm_bytes = (sjmi::strings_workspace_bytes(total_len) + 15) & ~(size_t)15;
-    if (!grow(c, (void**)&c->d_soff, &c->soff_bytes, soff_cap * sizeof(uint32_t), "hipMalloc(soff)") ||
-        !grow(c, (void**)&c->d_blk_ord, &c->blk_ord_bytes, (total_len / 64 + 2) * sizeof(uint32_t), "hipMalloc(blk_ord)") ||
-        !grow(c, (void**)&c->d_doc_ord, &c->doc_ord_bytes, (n_docs + 2) * sizeof(unsigned long long), "hipMalloc(doc_ord)") ||
-        !grow(c, &c->d_ws_strm, &c->ws_strm_bytes, strm_bytes, "hipMalloc(ws_strm)"))
+    if (!grow(c, c->d_soff, soff_cap * sizeof(uint32_t), "hipMalloc(soff)") ||
+        !grow(c, c->d_blk_ord, (total_len / 64 + 2) * sizeof(uint32_t), "hipMalloc(blk_ord)") ||
+        !grow(c, c->d_doc_ord, (n_docs + 2) * sizeof(unsigned long long), "hipMalloc(doc_ord)") ||
+        !grow(c, c->d_ws_strm, strm_bytes, "hipMalloc(ws_strm)") || !grow(c, c->d_batch_flags, 64, "hipMalloc(batch flags)"))
         return SJMI_ERR_HIP;
-    if (!c->d_batch_flags && fail(c, "hipMalloc(batch flags)", hipMalloc((void**)&c->d_batch_flags, 64))) return SJMI_ERR_HIP;
     // the pipeline's stage flags: pf[0] != 0 = stage A accepted, pf[1] != 0 = A or B accepted (the tapes are laid out in advance)
     uint32_t* const pf = c->d_batch_flags + 8;
     c->soff_idx = nullptr;
@@ -1338,18 +1265,11 @@ static int parse_batch_pipeline(sjmi_ctx* c, const void* d_buf, uint64_t total_l
         int rc0;
         {
             const AutoSafeOff plain_only(c);  // (a tripped liveness bound only rejects the plain pass)
-            c->batch_side = true;
-            c->s1_zero2 = c->d_ws_strm;
-            c->s1_zero2_bytes = strm_bytes;
-            // (experiments: SJMI_BATCH_STEPS = granule of the pipeline's plain pass in units of 4 KiB)
-            static const int batch_steps = getenv("SJMI_BATCH_STEPS") ? atoi(getenv("SJMI_BATCH_STEPS")) : 0;
-            const int keep_steps = c->forced_steps;
-            if (batch_steps == 1 || batch_steps == 2 || batch_steps == 4) c->forced_steps = batch_steps;
-            rc0 = stage1_device_impl(c, d_buf, total_len, d_indexes, index_capacity, &r->stage1, stream, 0);
-            c->forced_steps = keep_steps;
-            c->batch_side = false;
-            c->s1_zero2 = nullptr;
-            c->s1_zero2_bytes = 0;
+            Stage1Opts o;
+            o.side = true;
+            o.zero2 = c->d_ws_strm;
+            o.zero2_bytes = strm_bytes;
+            rc0 = stage1_device_impl(c, d_buf, total_len, d_indexes, index_capacity, &r->stage1, stream, &o);
         }
         if (rc0 != SJMI_OK) return rc0;
         if (!(c->par_valid && c->par_buf == d_buf && c->par_len == total_len) || !c->ws_dev_last) {
@@ -1379,11 +1299,11 @@ static int parse_batch_pipeline(sjmi_ctx* c, const void* d_buf, uint64_t total_l
         return SJMI_ERR_HIP;
     }
     if (!optimistic_only) {
-        const int steps = c->forced_steps ? c->forced_steps : sjmi::stage1_pick_steps(total_len);
-        if (!grow(c, (void**)&c->d_doccnt, &c->doccnt_bytes, sjmi::batch_isolated_workspace_bytes(n_docs), "hipMalloc(doccnt)") ||
-            !grow(c, (void**)&c->d_copy, &c->copy_bytes, total_len + 2 * SJMI_PADDING + 64, "hipMalloc(copy)") ||
-            !grow(c, (void**)&c->d_blkpar2, &c->blkpar2_bytes, sjmi::strings_parity_words(total_len) * sizeof(unsigned long long), "hipMalloc(blkpar2)") ||
-            !grow(c, &c->d_ws_par, &c->ws_par_bytes, sjmi::stage1_workspace_bytes(total_len, steps), "hipMalloc(ws_par)"))
+        const int steps = stage1_steps(c, total_len);
+        if (!grow(c, c->d_doccnt, sjmi::batch_isolated_workspace_bytes(n_docs), "hipMalloc(doccnt)") ||
+            !grow(c, c->d_copy, total_len + 2 * SJMI_PADDING + 64, "hipMalloc(copy)") ||
+            !grow(c, c->d_blkpar2, sjmi::strings_parity_words(total_len) * sizeof(unsigned long long), "hipMalloc(blkpar2)") ||
+            !grow(c, c->d_ws_par, sjmi::stage1_workspace_bytes(total_len, steps), "hipMalloc(ws_par)"))
             return SJMI_ERR_HIP;
         const uint32_t* const skip_b = pf;      // stages B and the verdicts: not behind an accepted A
         const uint32_t* const skip_c = pf + 1;  // stage C: not behind an accepted A or B
@@ -1398,8 +1318,8 @@ static int parse_batch_pipeline(sjmi_ctx* c, const void* d_buf, uint64_t total_l
         if (try_repair) {
             // ---- stage B: the plain pipeline over the copy.  Its stage-1 launch has a workspace of its own (a launch that may
             //      leave at once cannot take part in the context's two alternating halves) and its string pass a zeroed one ----
-            if (!grow(c, (void**)&c->d_blkidx, &c->blkidx_bytes, sjmi::stage1_block_entries(total_len) * sizeof(uint32_t), "hipMalloc(blkidx)") ||
-                !grow(c, (void**)&c->d_blkw, &c->blkw_bytes, sjmi::stage1_block_entries(total_len) * sizeof(uint16_t), "hipMalloc(blkw)"))
+            if (!grow(c, c->d_blkidx, sjmi::stage1_block_entries(total_len) * sizeof(uint32_t), "hipMalloc(blkidx)") ||
+                !grow(c, c->d_blkw, sjmi::stage1_block_entries(total_len) * sizeof(uint16_t), "hipMalloc(blkw)"))
                 return SJMI_ERR_HIP;
             sjmi::Stage1Extras ex;
             ex.blkpar = c->d_blkpar2;
@@ -1407,12 +1327,11 @@ static int parse_batch_pipeline(sjmi_ctx* c, const void* d_buf, uint64_t total_l
             ex.blkidx = c->d_blkidx;
             ex.blkw = c->d_blkw;
             ex.result_out = &r->stage1;
-            const uint64_t dev_cap = index_capacity;
-            if (fail(c, "repair: plain pass", sjmi::stage1_launch(c->d_copy, total_len, (uint32_t*)d_indexes, dev_cap, c->d_ws_par, steps, st,
+            if (fail(c, "repair: plain pass", sjmi::stage1_launch(c->d_copy, total_len, (uint32_t*)d_indexes, index_capacity, c->d_ws_par, steps, st,
                                                                   nullptr, nullptr, launch_flags(c), ex)))
                 return SJMI_ERR_HIP;
             note_launch(c, st);
-            uint32_t* const flags_b = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(c->d_ws_par) + sjmi::WS_BATCH_FLAGS_OFFSET);
+            uint32_t* const flags_b = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(c->d_ws_par.p) + sjmi::WS_BATCH_FLAGS_OFFSET);
             if (fail(c, "repair: strings launch",
                      sjmi::strings_launch(c->d_copy, total_len, c->d_blkpar2, (uint8_t*)d_string_buffer, string_capacity, c->d_soff, soff_cap,
                                           c->d_blk_ord, c->d_ws_strm, d_u, st, nullptr, nullptr, sjmi::StringsAlt(), false, skip_b)))
@@ -1447,10 +1366,8 @@ static int parse_batch_pipeline(sjmi_ctx* c, const void* d_buf, uint64_t total_l
             ex.skip = skip_c;
             if (fail(c, "sanitize", sjmi::strings_sanitize_launch((const uint8_t*)d_buf, total_len, (const unsigned long long*)d_doc_offsets,
                                                                   nullptr, n_docs, c->d_copy, skip_c, st, (const uint32_t*)d_doc_status)) ||
-                fail(c, "parity launch", sjmi::stage1_launch(c->d_copy, total_len, nullptr, 0, c->d_ws_par, steps, st, nullptr, nullptr,
-                                                             (launch_flags(c) & ~sjmi::DBG_NO_LOOKBACK) | sjmi::DBG_NO_WRITE, ex)))
+                fail(c, "parity launch", parity_launch(c, c->d_copy, total_len, st, ex)))
                 return SJMI_ERR_HIP;
-            note_launch(c, st);
         }
         //      ... the per-document index arrays, the string pass over the copy (fills the record k_batch_layout zeroed), ordinals
         if (!repair_only &&
@@ -1469,17 +1386,12 @@ static int parse_batch_pipeline(sjmi_ctx* c, const void* d_buf, uint64_t total_l
                                                    (unsigned long long*)d_doc_string_offsets, st, skip_c))))
             return SJMI_ERR_HIP;
     }
-    const bool layout_done = try_plain || try_repair;
-    if (fail(c, "walk launch",
-             sjmi::walk_launch((const uint8_t*)d_buf, (const unsigned long long*)d_doc_offsets, n_docs, (const uint32_t*)d_indexes,
-                               bound, (const unsigned long long*)d_index_offsets, (const uint32_t*)d_doc_status,
-                               (const uint8_t*)d_string_buffer, c->d_doc_ord, 0, max_depth,
-                               (unsigned long long*)d_tape, tape_capacity, (unsigned long long*)d_tape_offsets,
-                               (int32_t*)d_doc_errors, c->d_ws_walk, (sjmi::WalkResult*)&r->walk, st,
-                               (const sjmi::Stage1Result*)&r->stage1, (const sjmi::UnescapeResult*)&r->strings, c->d_soff, false, false,
-                               sjmi::SingleDocTail(), layout_done ? d_laid_out : nullptr, layout_done, optimistic_only || repair_only)))
-        return SJMI_ERR_HIP;
-    return SJMI_OK;
+    w.d_doc_str_ordinals = c->d_doc_ord;
+    w.d_soff = c->d_soff;
+    w.d_prepared = d_laid_out;  // (try_plain || try_repair: the layout is done)
+    w.layout_done = true;
+    w.optimistic_only = optimistic_only || repair_only;
+    return fail(c, "walk launch", sjmi::walk_launch(w, st)) ? SJMI_ERR_HIP : SJMI_OK;
 }
 
 int sjmi_parse_batch_device(sjmi_ctx* c, const void* d_buf, uint64_t total_len, const void* d_doc_offsets, uint64_t n_docs,
@@ -1525,102 +1437,106 @@ int sjmi_parse_document(sjmi_ctx* c, const uint8_t* buf, uint64_t len, int max_d
                         int32_t* error, uint32_t* stage1_status) {
     if (!c || (!buf && len) || !tape || !tape_len || !string_buffer || !strings_len || !error || !stage1_status || max_depth < 1)
         return SJMI_ERR_ARG;
-    if (len > c->capacity || len >= (1ull << 32)) {
-        c->err = "document larger than the context capacity";
-        return SJMI_ERR_CAPACITY;
-    }
+    if (too_large(c, len, "document")) return SJMI_ERR_CAPACITY;
     if (fail(c, "hipSetDevice", hipSetDevice(c->device))) return SJMI_ERR_HIP;
     const uint64_t bound = len + 1;  // structurals: at most one per byte
     const size_t need_sb = (size_t)len + 4 * ((size_t)len / 2 + 2) + 64;
-    if (!grow(c, (void**)&c->d_sb, &c->sb_bytes, need_sb, "hipMalloc(sb)") ||
-        !grow(c, (void**)&c->d_soff, &c->soff_bytes, ((size_t)len / 2 + 66) * sizeof(uint32_t), "hipMalloc(soff)") ||
-        !grow(c, &c->d_ws_walk, &c->ws_walk_bytes, sjmi::walk_workspace_bytes(bound, 1), "hipMalloc(ws_walk)") ||
-        !grow(c, (void**)&c->d_tape, &c->tape_bytes, (2 * (size_t)bound + 16) * sizeof(unsigned long long), "hipMalloc(tape)"))
+    if (!grow(c, c->d_sb, need_sb, "hipMalloc(sb)") ||
+        !grow(c, c->d_soff, ((size_t)len / 2 + 66) * sizeof(uint32_t), "hipMalloc(soff)") ||
+        !grow(c, c->d_ws_walk, sjmi::walk_workspace_bytes(bound, 1), "hipMalloc(ws_walk)") ||
+        !grow(c, c->d_tape, (2 * (size_t)bound + 16) * sizeof(unsigned long long), "hipMalloc(tape)") ||
+        !grow(c, c->d_single, 512, "hipMalloc(single)") || !grow(c, c->h_single, 512, "hipHostMalloc(single)"))
         return SJMI_ERR_HIP;
-    if (!c->d_single && fail(c, "hipMalloc(single)", hipMalloc(&c->d_single, 512))) return SJMI_ERR_HIP;
-    if (!c->h_single && fail(c, "hipHostMalloc(single)", hipHostMalloc(&c->h_single, 512))) return SJMI_ERR_HIP;
     if (!c->copy_stream && (fail(c, "hipStreamCreate", hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking)) ||
                             fail(c, "hipEventCreate", hipEventCreateWithFlags(&c->strings_ready, hipEventDisableTiming))))
         return SJMI_ERR_HIP;
     // layout of d_single: doc_offsets[2] | index_offsets[2] | doc_str_offsets[2] | tape_offsets[2] | status | error | results
-    unsigned long long* d64 = (unsigned long long*)c->d_single;
+    unsigned long long* d64 = (unsigned long long*)c->d_single.p;
     unsigned long long *d_doc = d64, *d_io = d64 + 2, *d_dso = d64 + 4, *d_to = d64 + 6;
     uint32_t* d_st = (uint32_t*)(d64 + 8);
     int32_t* d_err = (int32_t*)(d64 + 9);
     sjmi::UnescapeResult* d_ures = nullptr;  // (inside the string pass's workspace, zeroed with it)
     sjmi::WalkResult* d_wres = (sjmi::WalkResult*)(d64 + 13);
     sjmi::Stage1Result* d_res1 = (sjmi::Stage1Result*)(d64 + 20);
-    SingleDocResults* h = (SingleDocResults*)c->h_single;
+    void* const slow_header = sjmi::walk_slow_header(c->d_ws_walk, bound, 1);
+    SingleDocResults* h = (SingleDocResults*)c->h_single.p;
     // ZERO-COPY OUTPUTS: a tape that lives in page-locked, device-visible host memory (sjmi_host_register / hipHostMalloc: what
     // SimdJsonParser does with its buffers) is written by the walkers directly, over PCIe, and the packed result records land in
     // the context's pinned page the same way -- no download of either, ONE host synchronisation instead of two (twitter.json:
     // 0.147 -> ~0.12 ms).  A pageable tape takes the staged path below.
-    static const bool zero_copy_off = getenv("SJMI_ZERO_COPY") && atoi(getenv("SJMI_ZERO_COPY")) == 0;
     drop_stale_views(c);
     if (c->zc_host != tape) {
         c->zc_host = tape;
         c->zc_dev = nullptr;
         void* dp = nullptr;
-        if (!zero_copy_off && tape_capacity >= 16 && hipHostGetDevicePointer(&dp, tape, 0) == hipSuccess && dp) c->zc_dev = (unsigned long long*)dp;
+        if (!zero_copy_off() && tape_capacity >= 16 && hipHostGetDevicePointer(&dp, tape, 0) == hipSuccess && dp) c->zc_dev = (unsigned long long*)dp;
         else (void)hipGetLastError();  // (not device-visible: not an error)
     }
-    if (!c->h_single_dev) {
-        void* dp = nullptr;
-        if (hipHostGetDevicePointer(&dp, c->h_single, 0) == hipSuccess && dp) c->h_single_dev = dp;
-        else (void)hipGetLastError();
-    }
+    if (!c->h_single_dev) c->h_single_dev = device_view(c, c->h_single);
     const bool zero_copy = c->zc_dev != nullptr && c->h_single_dev != nullptr;
-    const int steps = c->forced_steps ? c->forced_steps : sjmi::stage1_pick_steps(len);
     if (!upload_document(c, buf, len)) return SJMI_ERR_HIP;
     c->soff_idx = nullptr;
     // The string records are complete long before the tape: their download runs on a second stream while the walker works
     // (a large document: a tenth of the call).  The size comes from the unescape result, fetched on that stream too.
-    sjmi_unescape_result* h_u_early = (sjmi_unescape_result*)((uint8_t*)c->h_single + 256);
+    sjmi_unescape_result* h_u_early = (sjmi_unescape_result*)((uint8_t*)c->h_single.p + 256);
     bool strings_in_flight = false;
     const bool early_strings = len >= (256u << 10);  // (below that the second stream's synchronisation costs more than it hides)
     // Latency: besides the kernels only ONE memset is queued (the string pass's workspace, which also holds its record) --
     // stage 1 through the device entry point (double-buffered workspace, the scanner writes the record), the walk's record and
     // list header zeroed by the setup kernel.
-    (void)steps;
-    const AutoSafeOff own_retry(c);  // (the retry below is this call's own)
     // (the string pass's workspace is zeroed by the stage-1 workers on their way out, and the delimiters / zeroed records the walk
     //  needs are written by the stage-1 scanner together with the result record: a memset and a launch less in the chain)
     const size_t strm_bytes = (sjmi::strings_workspace_bytes(len) + 15) & ~(size_t)15;
-    if (!grow(c, &c->d_ws_strm, &c->ws_strm_bytes, strm_bytes, "hipMalloc(ws_strm)")) return SJMI_ERR_HIP;
-    for (int attempt = 0; attempt < 2; ++attempt) {
+    if (!grow(c, c->d_ws_strm, strm_bytes, "hipMalloc(ws_strm)")) return SJMI_ERR_HIP;
+    sjmi::WalkLaunch w;
+    w.d_buf = c->d_in;
+    w.d_doc_offsets = d_doc;
+    w.n_docs = 1;
+    w.d_idx = c->d_idx;
+    w.count = bound;
+    w.d_index_offsets = d_io;
+    w.d_doc_status = d_st;
+    w.d_sb = c->d_sb;
+    w.d_doc_str_ordinals = d_dso;
+    w.max_depth = max_depth;
+    w.d_tape = zero_copy ? c->zc_dev : c->d_tape.p;
+    w.tape_capacity = zero_copy ? tape_capacity : 2 * bound + 8;
+    w.d_tape_offsets = d_to;
+    w.d_doc_errors = d_err;
+    w.d_ws = c->d_ws_walk;
+    w.d_res = d_wres;
+    w.dev_count = d_res1;
+    w.d_soff = c->d_soff;
+    w.index_from_zero = true;
+    w.results_zeroed = true;
+    w.tail.s1 = d_res1;
+    w.tail.pack = zero_copy ? (sjmi::SingleDocPack*)c->h_single_dev : (sjmi::SingleDocPack*)((uint8_t*)c->d_single.p + 256);
+    w.tail.in_place_cap = zero_copy ? tape_capacity : 0;
+    // the walk (behind the single-document setup if stage 1 did not write it) and the download of the result records
+    auto queue_walk = [&](bool setup) {
+        return (setup && fail(c, "setup", sjmi::single_doc_setup_launch(d_res1, len, d_doc, d_io, d_st, d_dso, c->stream, d_wres, slow_header))) ||
+               fail(c, "walk launch", sjmi::walk_launch(w, c->stream)) ||
+               (!zero_copy && fail(c, "D2H", hipMemcpyAsync(h, w.tail.pack, sizeof *h, hipMemcpyDeviceToHost, c->stream)));
+    };
+    int rc = retry_in_safe_mode(c, h->s1.status, [&] {
         strings_in_flight = false;
-        c->s1_zero2 = c->d_ws_strm;
-        c->s1_zero2_bytes = strm_bytes;
-        c->s1_single.doc_offsets = d_doc;
-        c->s1_single.index_offsets = d_io;
-        c->s1_single.doc_status = d_st;
-        c->s1_single.doc_str_offsets = d_dso;
-        c->s1_single.walk_result = reinterpret_cast<uint32_t*>(d_wres);
-        c->s1_single.slow_header = static_cast<uint32_t*>(sjmi::walk_slow_header(c->d_ws_walk, bound, 1));
-        const int s1rc = stage1_device_impl(c, c->d_in, len, c->d_idx, c->capacity + 2, d_res1, c->stream, 0);
-        c->s1_zero2 = nullptr;
-        c->s1_zero2_bytes = 0;
-        c->s1_single = sjmi::Stage1Single();
-        const bool setup_done = c->s1_single_done;
-        c->s1_single_done = false;
+        Stage1Opts o;
+        o.zero2 = c->d_ws_strm;
+        o.zero2_bytes = strm_bytes;
+        o.single.doc_offsets = d_doc;
+        o.single.index_offsets = d_io;
+        o.single.doc_status = d_st;
+        o.single.doc_str_offsets = d_dso;
+        o.single.walk_result = reinterpret_cast<uint32_t*>(d_wres);
+        o.single.slow_header = static_cast<uint32_t*>(slow_header);
+        const int s1rc = stage1_device_impl(c, c->d_in, len, c->d_idx, c->capacity + 2, d_res1, c->stream, &o);
         if (s1rc != SJMI_OK) return s1rc;
-        const int src = strings_device_impl(c, c->d_in, len, c->d_sb, c->sb_bytes, c->d_soff, (size_t)len / 2 + 2, nullptr, nullptr, c->stream, &d_ures, true);
+        const int src = strings_device_impl(c, c->d_in, len, c->d_sb, c->d_sb.bytes, c->d_soff, (size_t)len / 2 + 2, nullptr, nullptr, c->stream, &d_ures, true);
         if (src != SJMI_OK) return src;
-        sjmi::SingleDocTail tail;
-        tail.s1 = d_res1;
-        tail.u = d_ures;
-        tail.pack = zero_copy ? (sjmi::SingleDocPack*)c->h_single_dev : (sjmi::SingleDocPack*)((uint8_t*)c->d_single + 256);
-        tail.in_place_cap = zero_copy ? tape_capacity : 0;
-        unsigned long long* const walk_tape = zero_copy ? c->zc_dev : c->d_tape;
-        const uint64_t walk_cap = zero_copy ? tape_capacity : 2 * bound + 8;
-        tail.optimistic = true;  // (a large document's chunk path ends in k_chunk_finish: a document it declines comes back flagged)
-        if ((early_strings && fail(c, "event", hipEventRecord(c->strings_ready, c->stream))) ||
-            (!setup_done && fail(c, "setup", sjmi::single_doc_setup_launch(d_res1, len, d_doc, d_io, d_st, d_dso, c->stream, d_wres,
-                                                                           sjmi::walk_slow_header(c->d_ws_walk, bound, 1)))) ||
-            fail(c, "walk launch",
-                 sjmi::walk_launch(c->d_in, d_doc, 1, c->d_idx, bound, d_io, d_st, c->d_sb, d_dso, 0, max_depth, walk_tape,
-                                   walk_cap, d_to, d_err, c->d_ws_walk, d_wres, c->stream, d_res1, d_ures, c->d_soff, true, true, tail)) ||
-            (!zero_copy && fail(c, "D2H", hipMemcpyAsync(h, tail.pack, sizeof *h, hipMemcpyDeviceToHost, c->stream))))
+        w.dev_strings = w.tail.u = d_ures;
+        w.tail.optimistic = true;  // (a large document's chunk path ends in k_chunk_finish: a document it declines comes back flagged)
+        w.tail.no_chunks = false;
+        if ((early_strings && fail(c, "event", hipEventRecord(c->strings_ready, c->stream))) || queue_walk(!o.single_done))
             return SJMI_ERR_HIP;
         // (everything of the main stream is queued: now the early look at the string records)
         if (early_strings) {
@@ -1638,32 +1554,21 @@ int sjmi_parse_document(sjmi_ctx* c, const uint8_t* buf, uint64_t len, int max_d
         if (h->fallback && !(h->s1.status & SJMI_ST_INTERNAL)) {
             // (rare) the chunk path declined the document (a depth swing beyond its relative levels, more than 64 levels): the
             // single-wave sweep, queued only now
-            tail.optimistic = false;
-            tail.no_chunks = true;
-            if (fail(c, "setup", sjmi::single_doc_setup_launch(d_res1, len, d_doc, d_io, d_st, d_dso, c->stream, d_wres,
-                                                               sjmi::walk_slow_header(c->d_ws_walk, bound, 1))) ||
-                fail(c, "walk launch",
-                     sjmi::walk_launch(c->d_in, d_doc, 1, c->d_idx, bound, d_io, d_st, c->d_sb, d_dso, 0, max_depth, walk_tape,
-                                       walk_cap, d_to, d_err, c->d_ws_walk, d_wres, c->stream, d_res1, d_ures, c->d_soff, true, true, tail)) ||
-                (!zero_copy && fail(c, "D2H", hipMemcpyAsync(h, tail.pack, sizeof *h, hipMemcpyDeviceToHost, c->stream))) ||
-                fail(c, "sync", hipStreamSynchronize(c->stream)))
-                return SJMI_ERR_HIP;
+            w.tail.optimistic = false;
+            w.tail.no_chunks = true;
+            if (queue_walk(true) || fail(c, "sync", hipStreamSynchronize(c->stream))) return SJMI_ERR_HIP;
         }
-        if (!(h->s1.status & SJMI_ST_INTERNAL) || c->ticket_mode) break;
+        // (the early string download finishes before the next attempt or the return)
         if (strings_in_flight && fail(c, "sync", hipStreamSynchronize(c->copy_stream))) return SJMI_ERR_HIP;
-        c->ticket_mode = true;  // fast-mode liveness assumption failed: latch the safe mode and run again
-    }
-    if (strings_in_flight && fail(c, "sync", hipStreamSynchronize(c->copy_stream))) return SJMI_ERR_HIP;
+        return SJMI_OK;
+    });
+    if (rc != SJMI_OK) return rc;
     c->last_valid = false;
     *stage1_status = h->s1.status & 0xFFu;
     *tape_len = 0;
     *strings_len = 0;
     *error = h->err;
-    if (h->s1.status & SJMI_ST_INTERNAL) {
-        c->err = "look-back timeout";
-        return SJMI_ERR_INTERNAL;
-    }
-    if (h->s1.status & SJMI_ST_CAPACITY) return SJMI_ERR_CAPACITY;
+    if ((rc = stage1_rc(c, h->s1.status)) != SJMI_OK) return rc;
     if (h->err != 0) return SJMI_OK;  // a JSON error or SJMI_WALK_NEEDS_HOST: no tape
     const uint64_t words = h->to[1] - h->to[0];
     if (words > tape_capacity || h->u.total_bytes > string_capacity || (h->u.flags & 1u)) {
@@ -1743,9 +1648,9 @@ int sjmi_kernel_time(sjmi_ctx* c, double* sum_ms, uint32_t* launches) {
 // (the reference has one byte[] per parse and no counterpart)
 struct sjmi_stream {
     sjmi_ctx* c = nullptr;
-    uint8_t* d_buf = nullptr;       // [keep bytes of the stream in front of the chunk | the chunk | padding]
-    uint32_t* d_idx = nullptr;
-    sjmi_stage1_result* d_res = nullptr;
+    DevBuf<uint8_t> d_buf;          // [keep bytes of the stream in front of the chunk | the chunk | padding]
+    DevBuf<uint32_t> d_idx;
+    DevBuf<sjmi_stage1_result> d_res;
     uint64_t max_chunk = 0, keep = 0, halo = 0;
     uint64_t have = 0;              // bytes of the stream kept in front of the next chunk (<= keep, the END of [0, keep))
     uint64_t offset = 0;            // stream offset of the next chunk
@@ -1764,9 +1669,9 @@ int sjmi_stream_open(sjmi_ctx* c, uint64_t max_chunk_bytes, uint64_t halo_bytes,
     s->max_chunk = (max_chunk_bytes + 63) / 64 * 64;
     s->halo = halo_bytes ? halo_bytes : 64;
     s->keep = s->halo > 4096 ? s->halo : 4096;  // what a chunk can be repeated with when its halo proves too short
-    if (fail(c, "hipMalloc(stream)", hipMalloc((void**)&s->d_buf, s->keep + s->max_chunk + 2 * SJMI_PADDING)) ||
-        fail(c, "hipMalloc(stream idx)", hipMalloc((void**)&s->d_idx, (s->max_chunk + 66) * sizeof(uint32_t) + s->keep)) ||
-        fail(c, "hipMalloc(stream res)", hipMalloc((void**)&s->d_res, sizeof(sjmi_stage1_result)))) {
+    if (!grow(c, s->d_buf, s->keep + s->max_chunk + 2 * SJMI_PADDING, "hipMalloc(stream)") ||
+        !grow(c, s->d_idx, (s->max_chunk + 66) * sizeof(uint32_t) + s->keep, "hipMalloc(stream idx)") ||
+        !grow(c, s->d_res, sizeof(sjmi_stage1_result), "hipMalloc(stream res)")) {
         sjmi_stream_close(s);
         return SJMI_ERR_HIP;
     }
@@ -1778,10 +1683,7 @@ void sjmi_stream_close(sjmi_stream* s) {
     if (!s) return;
     (void)hipSetDevice(s->c->device);
     (void)hipStreamSynchronize(s->c->stream);
-    if (s->d_buf) (void)hipFree(s->d_buf);
-    if (s->d_idx) (void)hipFree(s->d_idx);
-    if (s->d_res) (void)hipFree(s->d_res);
-    delete s;
+    delete s;  // (releases its buffers)
 }
 
 int sjmi_stream_push(sjmi_stream* s, const uint8_t* chunk, uint64_t len, int is_last, uint32_t* indexes, uint64_t index_capacity,
@@ -1814,8 +1716,8 @@ int sjmi_stream_push(sjmi_stream* s, const uint8_t* chunk, uint64_t len, int is_
         }
         want *= 4;
     }
-    if (r.status & SJMI_ST_INTERNAL) return SJMI_ERR_INTERNAL;
-    if (r.status & SJMI_ST_CAPACITY) return SJMI_ERR_CAPACITY;
+    const int rc = stage1_rc(c, r.status);
+    if (rc != SJMI_OK) return rc;
     if (r.count + 1 > index_capacity) return SJMI_ERR_CAPACITY;
     if (fail(c, "D2H(indexes)", hipMemcpyAsync(indexes, s->d_idx, (r.count + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream)))
         return SJMI_ERR_HIP;
@@ -1861,7 +1763,7 @@ struct sjmi_split {
     uint64_t len = 0, halo = 0, index_capacity = 0;
     int halo_from_start = 0, is_last = 0, entry = 0, scans = 0;
     void* d_indexes = nullptr;
-    sjmi_stage1_result* d_res = nullptr;
+    DevBuf<sjmi_stage1_result> d_res;
     sjmi_stage1_result r{};
 };
 
@@ -1871,7 +1773,7 @@ int sjmi_split_open(sjmi_ctx* c, const void* d_shard, uint64_t len, uint64_t hal
     *out = nullptr;
     sjmi_split* s = new (std::nothrow) sjmi_split();
     if (!s) return SJMI_ERR_ARG;
-    if (fail(c, "hipSetDevice", hipSetDevice(c->device)) || fail(c, "hipMalloc(split res)", hipMalloc((void**)&s->d_res, sizeof(sjmi_stage1_result)))) {
+    if (fail(c, "hipSetDevice", hipSetDevice(c->device)) || !grow(c, s->d_res, sizeof(sjmi_stage1_result), "hipMalloc(split res)")) {
         delete s;
         return SJMI_ERR_HIP;
     }
@@ -1889,8 +1791,7 @@ int sjmi_split_open(sjmi_ctx* c, const void* d_shard, uint64_t len, uint64_t hal
 void sjmi_split_close(sjmi_split* s) {
     if (!s) return;
     (void)hipSetDevice(s->c->device);
-    if (s->d_res) (void)hipFree(s->d_res);
-    delete s;
+    delete s;  // (releases its record)
 }
 static int split_scan(sjmi_split* s, int entry_parity, void* stream) {
     sjmi_ctx* c = s->c;
@@ -1902,9 +1803,7 @@ static int split_scan(sjmi_split* s, int entry_parity, void* stream) {
         return SJMI_ERR_HIP;
     s->entry = entry_parity;
     ++s->scans;
-    if (s->r.status & SJMI_ST_INTERNAL) return SJMI_ERR_INTERNAL;
-    if (s->r.status & SJMI_ST_CAPACITY) return SJMI_ERR_CAPACITY;
-    return SJMI_OK;
+    return stage1_rc(c, s->r.status);
 }
 int sjmi_split_scan(sjmi_split* s, void* stream, int* flips_parity, uint32_t* status) {
     if (!s || !flips_parity || !status) return SJMI_ERR_ARG;

@@ -239,20 +239,41 @@ hipError_t batch_layout_launch(const BatchLayout& a, void* d_ws, uint64_t count,
 // walk.hip: stage 2 of every document of a batch (the cooperative walker + packing of the tapes); d_doc_str_ordinals[k] =
 // ordinal of document k's first string in the record table d_soff of the string pass (strings.hip)
 size_t walk_workspace_bytes(uint64_t count, uint64_t n_docs);
-hipError_t walk_launch(const uint8_t* d_buf, const unsigned long long* d_doc_offsets, uint64_t n_docs, const uint32_t* d_idx,
-                       uint64_t count, const unsigned long long* d_index_offsets, const uint32_t* d_doc_status,
-                       const uint8_t* d_sb, const unsigned long long* d_doc_str_ordinals, uint64_t string_base, int max_depth,
-                       unsigned long long* d_tape, uint64_t tape_capacity, unsigned long long* d_tape_offsets,
-                       int32_t* d_doc_errors, void* d_ws, WalkResult* d_res, hipStream_t stream,
-                       const Stage1Result* dev_count, const UnescapeResult* dev_strings, const uint32_t* d_soff,
-                       bool index_from_zero = false, bool results_zeroed = false, const SingleDocTail& tail = SingleDocTail(),
-                       const uint32_t* d_prepared = nullptr, bool layout_done = false, bool optimistic_only = false);
-// layout_done: batch_layout_launch ran (the tapes ARE laid out when *d_prepared != 0, the result record and list headers are
-// zeroed): nothing of that is queued again.  optimistic_only: only the kernels of the accepted path are queued.
-// d_prepared (the fused batch pipeline): device flag, != 0 = batch.hip k_doc_prepare ran (the accepted plain pass) and left
-// every document's DocMeta / predicted tape length in the walk workspace (walk_prepared): the tapes are laid out before the
-// walk and written at their final addresses -- there a document that fails keeps its (unused) slot: tape_offsets[k + 1] -
-// tape_offsets[k] is its PREDICTED length, the words are unspecified, doc_errors[k] says so.
+struct WalkLaunch {
+    const uint8_t* d_buf = nullptr;
+    const unsigned long long* d_doc_offsets = nullptr;
+    uint64_t n_docs = 0;
+    const uint32_t* d_idx = nullptr;
+    uint64_t count = 0;
+    const unsigned long long* d_index_offsets = nullptr;
+    const uint32_t* d_doc_status = nullptr;
+    const uint8_t* d_sb = nullptr;
+    const unsigned long long* d_doc_str_ordinals = nullptr;
+    uint64_t string_base = 0;
+    int max_depth = 0;
+    unsigned long long* d_tape = nullptr;
+    uint64_t tape_capacity = 0;
+    unsigned long long* d_tape_offsets = nullptr;
+    int32_t* d_doc_errors = nullptr;
+    void* d_ws = nullptr;
+    WalkResult* d_res = nullptr;
+    const Stage1Result* dev_count = nullptr;
+    const UnescapeResult* dev_strings = nullptr;
+    const uint32_t* d_soff = nullptr;
+    bool index_from_zero = false;
+    bool results_zeroed = false;
+    SingleDocTail tail;
+    // d_prepared (the fused batch pipeline): device flag, != 0 = batch.hip k_doc_prepare ran (the accepted plain pass) and left
+    // every document's DocMeta / predicted tape length in the walk workspace (walk_prepared): the tapes are laid out before the
+    // walk and written at their final addresses -- there a document that fails keeps its (unused) slot: tape_offsets[k + 1] -
+    // tape_offsets[k] is its PREDICTED length, the words are unspecified, doc_errors[k] says so.
+    const uint32_t* d_prepared = nullptr;
+    // layout_done: batch_layout_launch ran (the tapes ARE laid out when *d_prepared != 0, the result record and list headers are
+    // zeroed): nothing of that is queued again.  optimistic_only: only the kernels of the accepted path are queued.
+    bool layout_done = false;
+    bool optimistic_only = false;
+};
+hipError_t walk_launch(const WalkLaunch& w, hipStream_t stream);
 struct WalkPrepared {
     DocMeta* metas;
     uint32_t* lens;

@@ -263,93 +263,87 @@ hipError_t batch_layout_launch(const BatchLayout& a0, void* d_ws, uint64_t count
     return hipGetLastError();
 }
 
-hipError_t walk_launch(const uint8_t* d_buf, const unsigned long long* d_doc_offsets, uint64_t n_docs, const uint32_t* d_idx,
-                       uint64_t count, const unsigned long long* d_index_offsets, const uint32_t* d_doc_status,
-                       const uint8_t* d_sb, const unsigned long long* d_doc_str_ordinals, uint64_t string_base, int max_depth,
-                       unsigned long long* d_tape, uint64_t tape_capacity, unsigned long long* d_tape_offsets,
-                       int32_t* d_doc_errors, void* d_ws, WalkResult* d_res, hipStream_t stream, const Stage1Result* dev_count,
-                       const UnescapeResult* dev_strings, const uint32_t* d_soff, bool index_from_zero, bool results_zeroed,
-                       const SingleDocTail& tail, const uint32_t* d_prepared, bool layout_done, bool optimistic_only) {
-    if (!d_soff) return hipErrorInvalidValue;  // (the record table of the string pass: strings.hip)
-    if (optimistic_only && !(layout_done && d_prepared && n_docs > 1)) return hipErrorInvalidValue;
-    uint8_t* ws = static_cast<uint8_t*>(d_ws);
+hipError_t walk_launch(const WalkLaunch& w, hipStream_t stream) {
+    if (!w.d_soff) return hipErrorInvalidValue;  // (the record table of the string pass: strings.hip)
+    if (w.optimistic_only && !(w.layout_done && w.d_prepared && w.n_docs > 1)) return hipErrorInvalidValue;
+    uint8_t* ws = static_cast<uint8_t*>(w.d_ws);
     unsigned long long* scratch = reinterpret_cast<unsigned long long*>(ws);
     // one document whose index range starts at 0 (only sjmi_parse_document knows that: the walker's slot for document 0 is
     // T = tape + 2 * index_offsets[0]) and room for two words per structural: the walker writes the tape in place
-    const bool direct = index_from_zero && n_docs == 1 && (tape_capacity >= 2 * count + 2 || tail.in_place_cap != 0);
-    if (direct) scratch = d_tape;
-    uint32_t* lens = reinterpret_cast<uint32_t*>(ws + walk_lens_offset(count, n_docs));
-    unsigned long long* sums = reinterpret_cast<unsigned long long*>(ws + walk_sums_offset(count, n_docs));
-    hipError_t e = (results_zeroed || layout_done) ? hipSuccess : hipMemsetAsync(d_res, 0, sizeof(WalkResult), stream);
+    const bool direct = w.index_from_zero && w.n_docs == 1 && (w.tape_capacity >= 2 * w.count + 2 || w.tail.in_place_cap != 0);
+    if (direct) scratch = w.d_tape;
+    uint32_t* lens = reinterpret_cast<uint32_t*>(ws + walk_lens_offset(w.count, w.n_docs));
+    unsigned long long* sums = reinterpret_cast<unsigned long long*>(ws + walk_sums_offset(w.count, w.n_docs));
+    hipError_t e = (w.results_zeroed || w.layout_done) ? hipSuccess : hipMemsetAsync(w.d_res, 0, sizeof(WalkResult), stream);
     if (e != hipSuccess) return e;
-    const uint64_t nchunks = (n_docs + PACK_DOCS - 1) / PACK_DOCS;
+    const uint64_t nchunks = (w.n_docs + PACK_DOCS - 1) / PACK_DOCS;
     static const bool tokens_off = getenv("SJMI_TOKEN_WALK") && atoi(getenv("SJMI_TOKEN_WALK")) == 0;
     const uint32_t* packed_skip = nullptr;  // device flag != 0: the tapes were laid out before the walk, nothing is packed behind it
-    if (n_docs > 1 && (!tokens_off || optimistic_only)) {
+    if (w.n_docs > 1 && (!tokens_off || w.optimistic_only)) {
         // ---- a batch: the token walker (coop_walk.hip k_tok_stream) with the exact walker behind it for what it declines ----
-        const WalkPrepared wp = walk_prepared(d_ws, count, n_docs);
-        uint32_t* list = reinterpret_cast<uint32_t*>(ws + walk_list_offset(count, n_docs));
-        if (d_prepared && !layout_done) {
+        const WalkPrepared wp = walk_prepared(w.d_ws, w.count, w.n_docs);
+        uint32_t* list = reinterpret_cast<uint32_t*>(ws + walk_list_offset(w.count, w.n_docs));
+        if (w.d_prepared && !w.layout_done) {
             // the fused pipeline's accepted plain pass (*d_prepared != 0): batch.hip k_doc_prepare left the predicted lengths, so
             // the tapes are laid out NOW and the walkers store at the final addresses
-            const uint64_t pchunks = (n_docs + PREP_DOCS - 1) / PREP_DOCS;
-            hipLaunchKernelGGL(k_tape_chunk_scan, dim3(1), dim3(1024), 0, stream, wp.chunk_sums, pchunks, n_docs, tape_capacity,
-                               d_tape_offsets, d_res, d_prepared, 1u);
-            hipLaunchKernelGGL(k_tape_offsets, dim3((unsigned)((n_docs + 1 + PREP_DOCS - 1) / PREP_DOCS)), dim3(PREP_DOCS), 0, stream,
-                               (const uint32_t*)wp.lens, (const unsigned long long*)wp.chunk_sums, n_docs, tape_capacity, d_tape_offsets,
-                               wp.metas, list, d_prepared, d_doc_errors);
+            const uint64_t pchunks = (w.n_docs + PREP_DOCS - 1) / PREP_DOCS;
+            hipLaunchKernelGGL(k_tape_chunk_scan, dim3(1), dim3(1024), 0, stream, wp.chunk_sums, pchunks, w.n_docs, w.tape_capacity,
+                               w.d_tape_offsets, w.d_res, w.d_prepared, 1u);
+            hipLaunchKernelGGL(k_tape_offsets, dim3((unsigned)((w.n_docs + 1 + PREP_DOCS - 1) / PREP_DOCS)), dim3(PREP_DOCS), 0, stream,
+                               (const uint32_t*)wp.lens, (const unsigned long long*)wp.chunk_sums, w.n_docs, w.tape_capacity, w.d_tape_offsets,
+                               wp.metas, list, w.d_prepared, w.d_doc_errors);
         }
-        if (d_prepared) packed_skip = d_prepared;
-        if (!optimistic_only)
-            hipLaunchKernelGGL(k_doc_meta, dim3((unsigned)((n_docs + 1 + 255) / 256)), dim3(256), 0, stream, d_doc_offsets, d_index_offsets,
-                           d_doc_status, d_doc_str_ordinals, n_docs, wp.metas, list, packed_skip, d_doc_errors);
+        if (w.d_prepared) packed_skip = w.d_prepared;
+        if (!w.optimistic_only)
+            hipLaunchKernelGGL(k_doc_meta, dim3((unsigned)((w.n_docs + 1 + 255) / 256)), dim3(256), 0, stream, w.d_doc_offsets, w.d_index_offsets,
+                           w.d_doc_status, w.d_doc_str_ordinals, w.n_docs, wp.metas, list, packed_skip, w.d_doc_errors);
         TokLaunch t;
-        t.d_buf = d_buf;
-        t.d_idx = d_idx;
+        t.d_buf = w.d_buf;
+        t.d_idx = w.d_idx;
         t.d_metas = wp.metas;
-        t.n_docs = n_docs;
-        t.d_doc_offsets = d_doc_offsets;
-        t.d_index_offsets = d_index_offsets;
-        t.d_doc_status = d_doc_status;
-        t.d_doc_str_ordinals = d_doc_str_ordinals;
-        t.d_soff = d_soff;
-        t.d_sb = d_sb;
-        t.string_base = string_base;
-        t.max_depth = max_depth;
-        t.d_tape = d_prepared ? d_tape : scratch;
-        t.d_scratch = optimistic_only ? nullptr : scratch;
-        t.header_zeroed = layout_done;
-        t.d_sel = d_prepared;
-        t.d_tape_lens = optimistic_only ? nullptr : lens;  // (read by the passes that pack scratch tapes: none of them behind tapes laid out in advance)
-        t.d_doc_errors = d_doc_errors;
+        t.n_docs = w.n_docs;
+        t.d_doc_offsets = w.d_doc_offsets;
+        t.d_index_offsets = w.d_index_offsets;
+        t.d_doc_status = w.d_doc_status;
+        t.d_doc_str_ordinals = w.d_doc_str_ordinals;
+        t.d_soff = w.d_soff;
+        t.d_sb = w.d_sb;
+        t.string_base = w.string_base;
+        t.max_depth = w.max_depth;
+        t.d_tape = w.d_prepared ? w.d_tape : scratch;
+        t.d_scratch = w.optimistic_only ? nullptr : scratch;
+        t.header_zeroed = w.layout_done;
+        t.d_sel = w.d_prepared;
+        t.d_tape_lens = w.optimistic_only ? nullptr : lens;  // (read by the passes that pack scratch tapes: none of them behind tapes laid out in advance)
+        t.d_doc_errors = w.d_doc_errors;
         t.d_list = list;
-        t.dev_count = dev_count;
-        t.dev_strings = dev_strings;
-        t.d_res = d_res;
-        t.d_deep_ws = ws + walk_deep_offset(count, n_docs);
+        t.dev_count = w.dev_count;
+        t.dev_strings = w.dev_strings;
+        t.d_res = w.d_res;
+        t.d_deep_ws = ws + walk_deep_offset(w.count, w.n_docs);
         e = tok_walk_launch(t, stream);
         if (e != hipSuccess) return e;
-        if (optimistic_only) return hipGetLastError();  // (nothing is packed behind tapes that were laid out before the walk)
-        hipLaunchKernelGGL(k_tape_chunk_sums, dim3((unsigned)nchunks), dim3(1024), 0, stream, lens, d_doc_errors, n_docs, sums, d_res, packed_skip);
-    } else if (n_docs) {
+        if (w.optimistic_only) return hipGetLastError();  // (nothing is packed behind tapes that were laid out before the walk)
+        hipLaunchKernelGGL(k_tape_chunk_sums, dim3((unsigned)nchunks), dim3(1024), 0, stream, lens, w.d_doc_errors, w.n_docs, sums, w.d_res, packed_skip);
+    } else if (w.n_docs) {
         // the cooperative walker (coop_walk.hip): a wave per document; STRING payloads from the string pass's record table
         // (direct = one document written in place: the walker's last launch also decides the listed literals and writes the
         //  tape offsets and counters -- three small launches fewer on the single-document latency path)
-        e = coop_walk_launch(d_buf, d_doc_offsets, n_docs, d_idx, d_index_offsets, d_doc_status, d_soff, d_sb,
-                             d_doc_str_ordinals, string_base, max_depth, scratch, lens, d_doc_errors, dev_count, dev_strings, d_res,
-                             stream, n_docs == 1 ? ws + walk_chunks_offset(count, n_docs) : nullptr, count,
-                             ws + walk_deep_offset(count, n_docs), direct ? d_tape_offsets : nullptr, tape_capacity, results_zeroed,
-                             direct ? tail : SingleDocTail());
+        e = coop_walk_launch(w.d_buf, w.d_doc_offsets, w.n_docs, w.d_idx, w.d_index_offsets, w.d_doc_status, w.d_soff, w.d_sb,
+                             w.d_doc_str_ordinals, w.string_base, w.max_depth, scratch, lens, w.d_doc_errors, w.dev_count, w.dev_strings, w.d_res,
+                             stream, w.n_docs == 1 ? ws + walk_chunks_offset(w.count, w.n_docs) : nullptr, w.count,
+                             ws + walk_deep_offset(w.count, w.n_docs), direct ? w.d_tape_offsets : nullptr, w.tape_capacity, w.results_zeroed,
+                             direct ? w.tail : SingleDocTail());
         if (e != hipSuccess) return e;
         if (direct) return hipGetLastError();
-        hipLaunchKernelGGL(k_tape_chunk_sums, dim3((unsigned)nchunks), dim3(1024), 0, stream, lens, d_doc_errors, n_docs, sums, d_res,
+        hipLaunchKernelGGL(k_tape_chunk_sums, dim3((unsigned)nchunks), dim3(1024), 0, stream, lens, w.d_doc_errors, w.n_docs, sums, w.d_res,
                            (const uint32_t*)nullptr);
     }
-    hipLaunchKernelGGL(k_tape_chunk_scan, dim3(1), dim3(1024), 0, stream, sums, nchunks, n_docs, tape_capacity, d_tape_offsets, d_res,
+    hipLaunchKernelGGL(k_tape_chunk_scan, dim3(1), dim3(1024), 0, stream, sums, nchunks, w.n_docs, w.tape_capacity, w.d_tape_offsets, w.d_res,
                        packed_skip, 0u);
-    if (n_docs && !direct)
-        hipLaunchKernelGGL(k_tape_compact, dim3((unsigned)nchunks), dim3(1024), 0, stream, scratch, lens, d_index_offsets, n_docs,
-                           sums, d_tape, tape_capacity, d_tape_offsets, packed_skip);
+    if (w.n_docs && !direct)
+        hipLaunchKernelGGL(k_tape_compact, dim3((unsigned)nchunks), dim3(1024), 0, stream, scratch, lens, w.d_index_offsets, w.n_docs,
+                           sums, w.d_tape, w.tape_capacity, w.d_tape_offsets, packed_skip);
     return hipGetLastError();
 }
 
