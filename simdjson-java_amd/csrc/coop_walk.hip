@@ -953,6 +953,8 @@ __device__ __forceinline__ uint32_t cw_bit(unsigned long long m, uint32_t i) { r
 #define SJMI_TS_RUN 16   // (measured: 8 -> 1.183 ms, 16 -> 1.126, 32 -> 1.147 per 1 M documents)
 #endif
 constexpr uint32_t TS_RUN = SJMI_TS_RUN;    // documents per run (their records live in LDS; a run is ~1,800 tokens = ~28 token steps)
+// (a run-local document number masks with TS_RUN - 1, is a bit of the 64-bit failed mask and sits below the 0xFF "no document" mark)
+static_assert(TS_RUN >= 1u && (TS_RUN & (TS_RUN - 1u)) == 0u && TS_RUN <= 64u, "SJMI_TS_RUN: a power of two, at most 64");
 constexpr uint32_t TS_RING = 128u;  // tokens between the ingest and the token steps
 struct __attribute__((aligned(8))) TsRing {
     uint2 e[TS_RING];  // .x = position, .y = the token | run-local document << 24
@@ -1222,7 +1224,15 @@ k_tok_stream(TokArgs a_by_value) {
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
             __builtin_amdgcn_wave_barrier();
             const uint32_t opener = tpos | ((tk - 1u) & 0x80000000u);  // is-array << 31 (TK_OPEN_A = 0)
-            if (cw_lanes(REG & ~EO & ~cw_ballot((int32_t)own < 0))) lv.stk[(uint32_t)h & 63u] = make_uint2(opener, own);
+            // Only the step's last document can continue into the next step, so only its brackets are pushed.  An earlier document's
+            // bracket left open at the same level (one that fails at the next document's first token, NC, in this very step) would
+            // otherwise store to the same slot in the same instruction, and which lane wins a same-address store is not specified.
+            // (No other plain LDS store of this kernel puts two lanes on one address: ring.e and pq.e take consecutive slots -- the
+            //  tail plus the lane's rank among the storing lanes, at most 64 of them and fewer than 128 in flight; run.rec / dso / from
+            //  the rank of a non-empty document; run.dyn the first token of a document, one per document and step; lv.open / lv.cnt
+            //  their own lane's word.)
+            const uint32_t dj_last = (uint32_t)__builtin_amdgcn_readlane((int)dj, (int)(nv - 1u));
+            if (cw_lanes(REG & ~EO & ~cw_ballot((int32_t)own < 0) & cw_ballot(dj == dj_last))) lv.stk[(uint32_t)h & 63u] = make_uint2(opener, own);
             const uint32_t from_step = (uint32_t)__shfl((int)opener, (int)par_lane);
             const uint32_t par = cw_lanes(IN_STEP) ? from_step : se_x;
             const uint32_t par_tpos = par & 0x7FFFFFFFu;

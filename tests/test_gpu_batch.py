@@ -7,6 +7,7 @@ import pytest
 
 from oracle import oracle as O
 from tests.conftest import load_fixture
+from tests.walk_common import assert_tape_equal
 
 pytestmark = pytest.mark.gpu
 
@@ -113,6 +114,7 @@ def test_parse_batch_trees_and_errors():
                 n_bad += 1
                 continue
             got = O.Parsed(tapes[k], strings, 0, 0, 0)
+            assert_tape_equal(tapes[k], strings, want, (k, d))
             assert got.to_python() == want.to_python(), (k, d)
         assert n_bad >= len(bad)
     finally:
@@ -125,12 +127,14 @@ def test_twitter_batch_end_to_end(twitter):
     reps = 8
     docs = [twitter.rstrip()] * reps
     buf, offs = _pack(docs)
-    want = O.parse(twitter).to_python()
+    want_parsed = O.parse(twitter)
+    want = want_parsed.to_python()
     p = S.SimdJsonParser(capacity=len(buf) + 64)
     try:
         tapes, strings, errors = p.parse_batch(buf, offs)
         assert not errors.any()
         for k in range(reps):
+            assert_tape_equal(tapes[k], strings, want_parsed, k)
             assert O.Parsed(tapes[k], strings, 0, 0, 0).to_python() == want
     finally:
         p.close()
@@ -230,11 +234,12 @@ def test_parse_batch_on_many_host_threads(monkeypatch):
     tapes1, strings1, errors1 = results[("1", "1")]
     assert int((errors1 != 0).sum()) >= 200
     sample = rng.sample(range(len(docs)), 600) + [7]
-    want = {}
+    want, want_parsed = {}, {}
     for k in sample:
         w = O.parse(docs[k] + b"\n")
         assert int(errors1[k]) == w.error, (k, docs[k])
         want[k] = None if w.error else w.to_python()
+        want_parsed[k] = w
     for (threads, pipeline), (tapes, strings, errors) in results.items():
         assert np.array_equal(errors, errors1), (threads, pipeline)
         if pipeline == "1":  # same string-buffer layout: the tapes are equal word for word
@@ -243,6 +248,7 @@ def test_parse_batch_on_many_host_threads(monkeypatch):
                 assert (a is None and b is None) or np.array_equal(a, b)
         for k in sample:
             if want[k] is not None:
+                assert_tape_equal(tapes[k], strings, want_parsed[k], (threads, pipeline, k))
                 assert O.Parsed(tapes[k], strings, 0, 0, 0).to_python() == want[k], (threads, pipeline, k)
 
 
@@ -265,6 +271,7 @@ def test_parse_batch_odd_shapes(monkeypatch):
                     want = O.parse(d + b"\n")
                     assert int(errors[k]) == want.error, (pipeline, k, d[:20])
                     if not want.error:
+                        assert_tape_equal(tapes[k], strings, want, (pipeline, k))
                         assert O.Parsed(tapes[k], strings, 0, 0, 0).to_python() == want.to_python(), (pipeline, k)
         finally:
             p.close()

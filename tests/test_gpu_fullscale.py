@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 from oracle import oracle as O
+from tests.walk_common import assert_tape_equal
 from tests.conftest import ROOT
 
 sys.path.insert(0, os.path.join(ROOT, "tools"))
@@ -88,6 +89,7 @@ def test_twitter_x1024_as_1024_documents_gives_1024_trees(twitter):
     try:
         tapes, strings, errors = p.parse_batch(buf, offs)
         assert not errors.any() and len(tapes) == reps
+        assert_tape_equal(tapes[0], strings, want)
         assert O.Parsed(tapes[0], strings, 0, 0, 0).to_python() == want.to_python()
         t0 = tapes[0]
         is_str = (t0 >> np.uint64(56)) == np.uint64(ord('"'))
@@ -184,6 +186,7 @@ def test_128k_document_batch_full_device_pipeline():
             assert np.array_equal(got, w_idx.astype(np.int64)), k
             want = O.parse(d + b"\n")
             assert want.error == 0
+            assert_tape_equal(tape0[int(to[k]):int(to[k + 1])], sb0, want, k)
             assert O.Parsed(tape0[int(to[k]):int(to[k + 1])], sb0, 0, 0, 0).to_python() == want.to_python(), k
         # ---- every repetition against repetition 0, on the device ----
         assert count == s0 * reps and int(d_wres[0].item()) == t0n * reps and int(d_ures[0].item()) == sb_len0 * reps

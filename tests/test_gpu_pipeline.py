@@ -9,6 +9,7 @@ import pytest
 from oracle import oracle as O
 from tests.test_gpu_batch import _pack, _small_docs
 from tests.test_gpu_walk import gpu_walk
+from tests.walk_common import assert_tape_equal
 
 pytestmark = pytest.mark.gpu
 
@@ -20,6 +21,35 @@ def _docs():
         docs.insert(rng.randrange(len(docs)), [b"[1 1]", b'["abc', b"", b"[-]", b'"', b"nul", b'{"a":1,}', b'["\\q"]',
                                                bytes([0x5B, 0x22, 0xC3, 0x22, 0x5D]), b'"root \\t string"'][i % 10])
     return docs
+
+
+def tapes_laid_out(rejected, docs, errors, to):
+    """Which stage took the batch: were the tapes laid out before the walk (the accepted plain pass, the repair stage) or packed
+    behind the per-document passes?  rejected: the optimistic step's SJMI_ST_REJECTED bit (None: not known, the exact entry).  A
+    document that fails stage 1 tells: two words laid out, none packed.  -> True / False / None (cannot tell)"""
+    s1 = [k for k in range(len(docs)) if 1 <= int(errors[k]) <= 3]
+    if s1:
+        sizes = {int(to[k + 1] - to[k]) for k in s1}
+        assert sizes in ({0}, {2}), sizes
+        assert rejected is not False  # (a batch with a document that fails stage 1 is never the plain pass's)
+        return sizes == {2}
+    return True if rejected is False else None  # (rejected for its format: the repair stage's, or the exact call's if it declined)
+
+
+def assert_failing_slots(docs, errors, to, laid_out):
+    """The slot of a failing document: empty when the tapes are packed behind the walk; when they were laid out in advance, two words
+    for a document that fails stage 1 and its predicted length (2 + 1 per token + 1 more per number) for one that fails stage 2"""
+    from tests.tok_stream_layouts import predicted_length
+    for k, d in enumerate(docs):
+        if int(errors[k]) == 0:
+            continue
+        size = int(to[k + 1] - to[k])
+        want = [0] if laid_out is False else []
+        if laid_out is not False:
+            want.append(2 if 1 <= int(errors[k]) <= 3 else predicted_length(d))
+        if laid_out is None:
+            want.append(0)
+        assert size in want, (k, d[:40], int(errors[k]), size, want, laid_out)
 
 
 def test_fused_pipeline_equals_the_three_calls_and_the_oracle():
@@ -34,6 +64,7 @@ def test_fused_pipeline_equals_the_three_calls_and_the_oracle():
         for _ in range(2):  # (twice: the second call reuses every workspace)
             shard.step(torch.cuda.current_stream().cuda_stream)
             torch.cuda.synchronize()
+        rejected = bool(int(shard.result.cpu().numpy()[1]) & 0x800)  # (the optimistic step's own record, before check() acts on it)
         c = shard.check()
         tapes, strings, errors = gpu_walk(ctx, docs)
         to = shard.tape_offsets.cpu().numpy()
@@ -41,18 +72,22 @@ def test_fused_pipeline_equals_the_three_calls_and_the_oracle():
         err = shard.doc_errors.cpu().numpy()[:len(docs)]
         assert np.array_equal(err, errors)
         assert bytes(shard.sb[:c["string_bytes"]].cpu().numpy()) == strings
+        # (a failing document has no tape.  Its slot holds unspecified words of its PREDICTED length when the tapes were laid out
+        #  before the walk -- the accepted plain pass, and the repair pass that takes this batch with its documents that fail
+        #  stage 1: two words for those -- and is empty when the tapes are packed behind the walk)
+        laid_out = tapes_laid_out(rejected, docs, err, to)
+        assert rejected and laid_out  # (this batch: documents that fail stage 1, taken by the repair stage)
+        assert_failing_slots(docs, err, to, laid_out)
         n_bad = 0
         for k, d in enumerate(docs):
             got = tape[int(to[k]):int(to[k + 1])]
             if errors[k] != 0:
-                # (a failing document has no tape.  Its slot holds unspecified words of its PREDICTED length when the tapes were
-                #  laid out before the walk -- the accepted plain pass, and since round 6 the repair pass that takes this batch with
-                #  its documents that fail stage 1: two words for those -- and is empty when the tapes are packed behind the walk)
-                assert got.size == 0 or int(shard.doc_status.cpu().numpy()[k]) == 0 or got.size == 2
                 n_bad += 1
                 continue
             assert np.array_equal(got, tapes[k]), k
             want = O.parse(d + b"\n")
+            assert want.error == 0
+            assert_tape_equal(got, strings, want, k)
             assert want.error == 0 and O.Parsed(got, strings, 0, 0, 0).to_python() == want.to_python(), k
         assert c["failed_documents"] == n_bad >= 50 and c["documents"] == len(docs)
         g = sharding.sharded_step(shard, torch.cuda.current_stream().cuda_stream)
@@ -155,6 +190,7 @@ def test_optimistic_plain_pass_and_its_rejections(separator, exact, monkeypatch)
                 if want.error:
                     n_bad += 1  # (no tape; the slot's size says nothing: see include/sjmi.h, sjmi_parse_batch_device)
                 else:
+                    assert_tape_equal(got, strings, want, (name, k))
                     assert O.Parsed(got, strings, 0, 0, 0).to_python() == want.to_python(), (name, k)
             assert c["failed_documents"] == n_bad, name
     finally:
@@ -177,6 +213,7 @@ def test_a_batch_of_one_document(exact):
             assert int(err[0]) == want.error, (d, int(err[0]), want.error)
             assert c["failed_documents"] == (1 if want.error else 0) and c["host_documents"] == 0
             if not want.error:
+                assert_tape_equal(tape[int(to[0]):int(to[1])], strings, want, d)
                 assert O.Parsed(tape[int(to[0]):int(to[1])], strings, 0, 0, 0).to_python() == want.to_python(), d
     finally:
         ctx.close()
@@ -208,6 +245,7 @@ def test_accepted_batch_with_strings_that_are_not_structurals():
             if want.error:
                 n_bad += 1
             else:
+                assert_tape_equal(tape[int(to[k]):int(to[k + 1])], strings, want, (k, d))
                 assert O.Parsed(tape[int(to[k]):int(to[k + 1])], strings, 0, 0, 0).to_python() == want.to_python(), (k, d)
         assert n_bad >= 400 and c["failed_documents"] == n_bad
     finally:
@@ -235,6 +273,7 @@ def test_accepted_batch_with_a_large_and_a_deep_document(twitter):
             want = O.parse(d + b"\n")
             assert int(err[k]) == want.error, (k, d[:40], int(err[k]), want.error)
             if want.error == 0:
+                assert_tape_equal(tape[int(to[k]):int(to[k + 1])], strings, want, (k, d[:40]))
                 assert O.Parsed(tape[int(to[k]):int(to[k + 1])], strings, 0, 0, 0).to_python() == want.to_python(), (k, d[:40])
         assert c["failed_documents"] == 1 and c["host_documents"] == 0  # (the 1,100-level document: maxDepth 1024)
     finally:
@@ -279,6 +318,7 @@ def test_repaired_batch_with_documents_of_every_size(twitter, sep):
             else:
                 got_idx = idx[int(io[k]):int(io[k + 1])].astype(np.int64) - int(offs[k])
                 assert np.array_equal(got_idx, O.stage1(d)[0].astype(np.int64)), (k, len(d))
+                assert_tape_equal(tape[int(to[k]):int(to[k + 1])], strings, want, (k, len(d)))
                 assert O.Parsed(tape[int(to[k]):int(to[k + 1])], strings, 0, 0, 0).to_python() == want.to_python(), (k, len(d))
         assert c["failed_documents"] == n_bad >= 40
     finally:
@@ -399,6 +439,7 @@ import simdjson_java_amd as S
 from simdjson_java_amd import sharding
 from oracle import oracle as O
 from tests.test_gpu_batch import _small_docs
+from tests.walk_common import assert_tape_equal
 rng = random.Random(31)
 docs = _small_docs(rng, 1500) + [b"[1 1]", b'{"a":tru}', b'["\\q"]', b"[" * 70 + b"]" * 70, b"7"]
 rng.shuffle(docs)
@@ -419,6 +460,7 @@ for k, d in enumerate(docs):
     if want.error:
         bad += 1
     else:
+        assert_tape_equal(tape[int(to[k]):int(to[k + 1])], strings, want, k)
         assert O.Parsed(tape[int(to[k]):int(to[k + 1])], strings, 0, 0, 0).to_python() == want.to_python(), k
 assert c["failed_documents"] == bad == 3, (c, bad)
 ctx.close()
@@ -448,6 +490,7 @@ import simdjson_java_amd as S
 from simdjson_java_amd import sharding
 from oracle import oracle as O
 from tests.test_gpu_batch import _small_docs
+from tests.walk_common import assert_tape_equal
 rng = random.Random(33)
 docs = _small_docs(rng, 1500) + [b"[1 1]", b'["abc', bytes([0x5B, 0x22, 0xC3, 0x22, 0x5D]), b'["a\x01"]', b'def"]', b"7", b""]
 rng.shuffle(docs)
@@ -471,6 +514,7 @@ for sep in (b"\n", b" "):
                 bad += 1
                 assert to[k + 1] == to[k]  # (the per-document passes: tapes packed behind the walk, a failing document's range is empty)
             else:
+                assert_tape_equal(tape[int(to[k]):int(to[k + 1])], strings, want, k)
                 assert O.Parsed(tape[int(to[k]):int(to[k + 1])], strings, 0, 0, 0).to_python() == want.to_python(), k
         assert c["failed_documents"] == bad == 6, (c, bad)
 ctx.close()
@@ -528,6 +572,7 @@ def test_the_repair_stage_takes_what_it_can_and_only_that():
                 else:
                     got_idx = idx[int(io[k]):int(io[k + 1])].astype(np.int64) - int(offs[k])
                     assert np.array_equal(got_idx, O.stage1(d)[0].astype(np.int64)), (name, k)
+                    assert_tape_equal(tape[int(to[k]):int(to[k + 1])], strings, want, (name, k))
                     assert O.Parsed(tape[int(to[k]):int(to[k + 1])], strings, 0, 0, 0).to_python() == want.to_python(), (name, k)
             assert c["failed_documents"] == n_bad >= len(bad), (name, c, n_bad)
     finally:
@@ -571,6 +616,7 @@ def test_the_call_for_rejected_batches_on_its_own():
                     if want.error:
                         n_bad += 1
                     else:
+                        assert_tape_equal(tape[int(to[k]):int(to[k + 1])], strings, want, (entry, k))
                         assert O.Parsed(tape[int(to[k]):int(to[k + 1])], strings, 0, 0, 0).to_python() == want.to_python(), (entry, k)
                 assert c["failed_documents"] == n_bad == len(bad), (entry, c)
                 outs.append((err.copy(), c["structurals"], c["string_bytes"], strings))
@@ -603,6 +649,7 @@ def test_pipeline_in_safe_mode_with_a_faked_timeout_and_with_misaligned_buffers(
         for k, w in enumerate(want):
             assert int(err[k]) == w.error, (label, k)
             if not w.error:
+                assert_tape_equal(tape[int(to[k]):int(to[k + 1])], strings, w, (label, k))
                 assert O.Parsed(tape[int(to[k]):int(to[k + 1])], strings, 0, 0, 0).to_python() == w.to_python(), (label, k)
         assert c["failed_documents"] == 1, (label, c)
         return c

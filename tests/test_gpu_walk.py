@@ -10,10 +10,11 @@ import pytest
 from oracle import oracle as O
 from tests.conftest import load_fixture
 from tests.test_gpu_batch import _pack, _small_docs
-from tests.walk_common import NEEDS_HOST, number_documents
+from tests.walk_common import NEEDS_HOST, assert_tape_equal, number_documents
 
 pytestmark = pytest.mark.gpu
 
+CANARY, CANARY_WORDS = 0x7E5A7E5A7E5A7E5A, 512
 
 
 def gpu_walk(ctx, docs, max_depth=1024):
@@ -39,7 +40,8 @@ def gpu_walk(ctx, docs, max_depth=1024):
     ctx.unescape_batch_device(d_buf.data_ptr(), len(buf), d_idx.data_ptr(), count, d_offs.data_ptr(), d_io.data_ptr(), n,
                               d_sb.data_ptr(), d_sb.numel(), d_dso.data_ptr(), d_ures.data_ptr(), stream)
     cap = 2 * count + 2 * n + 8
-    d_tape = torch.zeros(cap, dtype=torch.int64, device="cuda")
+    d_tape = torch.zeros(cap + CANARY_WORDS, dtype=torch.int64, device="cuda")
+    d_tape[cap:] = CANARY  # (behind the capacity the walk is given: nothing may store there)
     d_to = torch.zeros(n + 1, dtype=torch.int64, device="cuda")
     d_err = torch.zeros(max(n, 1), dtype=torch.int32, device="cuda")
     d_wres = torch.zeros(4, dtype=torch.int64, device="cuda")
@@ -53,6 +55,8 @@ def gpu_walk(ctx, docs, max_depth=1024):
     assert int(wres[0]) == int(to[-1]) and (int(wres[3]) & 1) == 0
     assert int(wres[1]) == int((errors == NEEDS_HOST).sum()) and int(wres[2]) == int((errors > 0).sum())
     tape = d_tape.cpu().numpy().view(np.uint64)
+    assert (tape[cap:] == np.uint64(CANARY)).all(), "a store behind the tape's capacity"
+    tape = tape[:cap]
     total = int(d_ures[0].item())
     strings = bytes(d_sb[:total].cpu().numpy())
     tapes = [tape[to[k]:to[k + 1]] if errors[k] == 0 else None for k in range(n)]
@@ -72,6 +76,7 @@ def check_against_oracle(docs, tapes, strings, errors, host_ok=()):
         assert int(errors[k]) == want.error, (k, d[:60], int(errors[k]), want.error)
         if not want.error:
             assert tapes[k].size == want.tape.size, (k, d[:60])  # (STRING payloads differ: batch-wide string buffer)
+            assert_tape_equal(tapes[k], strings, want, k)
             assert O.Parsed(tapes[k], strings, 0, 0, 0).to_python() == want.to_python(), k
 
 
@@ -197,6 +202,7 @@ def test_reference_number_vectors_on_the_gpu(ctx):
         if "message" in v:
             assert want.error != 0 and O.error_message(want.error) == v["message"], v["input"][:40]
         else:
+            assert_tape_equal(tapes[k], strings, want, v["input"][:40])
             got = O.Parsed(tapes[k], strings, 0, 0, 0).to_python()
             assert got == (("l", v["long"]) if "long" in v else ("d", v["double_bits"])), (v["input"][:40], v["cite"], got)
         on_device += 1

@@ -71,3 +71,26 @@ def number_documents(rng, n):
         if any(v is False for v in verdicts):
             hard.add(k)
     return docs, hard, either
+
+
+def assert_tape_equal(got, got_strings, want, what=None):
+    """A batch's tape of one document against the oracle's (`want`: oracle.parse of the document alone), word for word: every word
+    bit-equal -- both root words, the back-pointers of opening and closing brackets, element counts saturated or not, numbers --
+    except the payload of a '"' word, which points into a different string buffer: there both must point to the same record (4-byte
+    big-endian length, then the bytes)."""
+    import numpy as np
+    got = np.ascontiguousarray(got).view(np.uint64)
+    exp = np.ascontiguousarray(want.tape).view(np.uint64)
+    assert got.size == exp.size, (what, "tape length", got.size, exp.size)
+    q = (exp >> np.uint64(56)) == np.uint64(0x22)
+    diff = np.nonzero((got != exp) & ~q)[0]
+    if diff.size:
+        i = int(diff[0])
+        raise AssertionError((what, "word %d of %d" % (i, exp.size), hex(int(got[i])), hex(int(exp[i]))))
+    low = np.uint64((1 << 56) - 1)
+    for i in np.nonzero(q)[0]:
+        g, w = int(got[i]), int(exp[i])
+        assert g >> 56 == 0x22, (what, "word %d" % i, hex(g), hex(w))
+        go, wo = g & int(low), w & int(low)
+        ln = int.from_bytes(want.strings[wo:wo + 4], "big")
+        assert got_strings[go:go + 4 + ln] == want.strings[wo:wo + 4 + ln], (what, "string word %d" % i, go, wo)

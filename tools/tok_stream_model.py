@@ -25,6 +25,8 @@ and broken documents):
     storing anything, and the next DOCSTART re-bases everything, whatever state the broken document left behind;
   * both root words of a document are written at its DOCSTART from its predicted length (exact for a well-formed document).
 -> per document: kept (bool), tape (list) -- tape payloads of strings are string_base + record_offsets[ordinal]."""
+import random
+
 from coop_walk_model import parse_number
 from tok_walk_model import (M64, TK_OPEN_A, TK_OPEN_O, TK_CLOSE_O, TK_STRING, TK_NONE, TK_ATOM, TOK_COMMA, TOK_COLON, TOK_SCAN_FIELDS,
                             LEVELS, atom, ballot, below, first)
@@ -32,9 +34,13 @@ from tok_walk_model import (M64, TK_OPEN_A, TK_OPEN_O, TK_CLOSE_O, TK_STRING, TK
 RING = 512
 
 
-def walk_run(tables, buf, structurals, docs, record_offsets, string_base=0, max_depth=1024):
+def walk_run(tables, buf, structurals, docs, record_offsets, string_base=0, max_depth=1024, conflict="highest", last_doc_only=True,
+             seed=0):
     """docs: list of dicts {from, to, dso, toff, room} -- structural index range, ordinal of its first string, tape word offset and
-    predicted length; consecutive (docs[j].to == docs[j + 1].from).  -> [(kept, tape words or None)] per document"""
+    predicted length; consecutive (docs[j].to == docs[j + 1].from).  conflict: which lane wins when lanes of one step store to one
+    stack level ("highest", "lowest", "random" -- seeded by `seed`); last_doc_only=False pushes from every document of the step, not
+    only from the last one (the rule whose result depends on that order).  -> [(kept, tape words or None)] per document"""
+    rng = random.Random(seed)
     tok_of_first_byte, grammar = tables
     R = len(docs)
     assert R <= 64
@@ -187,9 +193,21 @@ def walk_run(tables, buf, structurals, docs, record_offsets, string_base=0, max_
         pcnt = [cnt[par_lane[l]] if in_step[l] else stk[lvl[l]][1] for l in range(64)]
         own = list(cnt)
         opener = [(tpos[l] & 0x7FFFFFFF) | (0x80000000 if tk[l] == TK_OPEN_A else 0) for l in range(64)]
-        for l in range(64):
-            if (OPEN >> l) & 1 and not (EO >> l) & 1 and not own[l] & 0x80000000:
-                stk[h[l] & 63] = (opener[l], own[l])
+        # the stack push (the kernel's rule): an opening bracket of a document not failed before this step, neither empty nor closed
+        # in the step, of the step's LAST document -- only that one can continue into the next step, and an earlier document's
+        # bracket at the same level (one left open by a document that fails at the next one's start, NC) must not compete with
+        # it for the slot.  `conflict` orders the stores of one step to one level: which lane wins must not matter.
+        fl0 = [(failed >> docj[l]) & 1 for l in range(64)]
+        pushers = [l for l in range(64) if (OPEN >> l) & 1 and (V >> l) & 1 and not fl0[l] and not (EO >> l) & 1
+                   and not own[l] & 0x80000000 and (docj[l] == docj[nv - 1] or not last_doc_only)]
+        if conflict == "lowest":
+            pushers.reverse()
+        elif conflict == "random":
+            rng.shuffle(pushers)
+        else:
+            assert conflict == "highest", conflict
+        for l in pushers:
+            stk[h[l] & 63] = (opener[l], own[l])
         par = [opener[par_lane[l]] if in_step[l] else se_x[l] for l in range(64)]
         par_tpos = [x & 0x7FFFFFFF for x in par]
         par_cnt = [x & 0x3FFFFFFF for x in pcnt]
