@@ -37,7 +37,6 @@
 // 1024 open containers (when the caller raised max_depth), more than 65,536 listed literals in one launch, a document of
 // more than 2^31 - 256 structurals.
 #include <hip/hip_runtime.h>
-#include <atomic>
 #include <stdint.h>
 #include <stdlib.h>
 
@@ -402,7 +401,7 @@ k_coop_walk(const uint8_t* __restrict__ buf, const unsigned long long* __restric
             const uint32_t* __restrict__ doc_status, const uint32_t* __restrict__ soff, const uint8_t* __restrict__ sb,
             const unsigned long long* __restrict__ doc_str_offsets, unsigned long long string_base, int max_depth,
             unsigned long long* __restrict__ scratch_tape, uint32_t* __restrict__ tape_lens, int32_t* __restrict__ doc_errors, const Stage1Result* __restrict__ dev_count,
-            const UnescapeResult* __restrict__ dev_strings, WalkResult* res, uint32_t abl, ChunkWs cw, const uint32_t* run_only_if,
+            const UnescapeResult* __restrict__ dev_strings, WalkResult* res, ChunkWs cw, const uint32_t* run_only_if,
             unsigned long long* __restrict__ ovf, SlowList slow, ExactMode ex) {
     if (run_only_if && *run_only_if == 0) return;   // (the single-wave sweep behind a chunked launch: only on fall-back)
     if (CHUNKED && *cw.fallback != 0) return;
@@ -633,7 +632,6 @@ k_coop_walk(const uint8_t* __restrict__ buf, const unsigned long long* __restric
                 // (deeper than the device stack: the non-empty open at depth 63 is handed back below, at a lower position
                 //  than anything that would need a level beyond the stack)
                 if (hmax >= level_cap) hmax = level_cap - 1;
-                if (abl & 2u) hmax = hmin - 1;
                 for (int L = hmin; L <= hmax; ++L) {
                     const unsigned long long O = __ballot(is_open && h == L);                 // opens of level L
                     const unsigned long long C = __ballot(valid && cls == K_COMMA && plevel == L);  // commas directly inside level L
@@ -724,8 +722,7 @@ k_coop_walk(const uint8_t* __restrict__ buf, const unsigned long long* __restric
                                 else if (h + 1 >= level_cap) err = SJMI_WALK_NEEDS_HOST;     // deeper than the device stack
                             }
                         } else if (cls != K_QUOTE) {
-                            if (!(abl & 1u)) err = cw_primitive(buf, win, p, i == from, doc_end, &ptype, &praw);
-                            else ptype = 'n';
+                            err = cw_primitive(buf, win, p, i == from, doc_end, &ptype, &praw);
                             if (err == CW_SLOW_DOUBLE) {  // (rare) listed for k_slow_doubles, which overwrites the candidate
                                 err = 0;
                                 const unsigned long long slot = atomicAdd(slow.count, 1ull);
@@ -756,7 +753,7 @@ k_coop_walk(const uint8_t* __restrict__ buf, const unsigned long long* __restric
                 }
                 if (rc) root_closed = true;
                 // (7) the tape words of this step
-                const bool live = valid && lane <= rc_lane && !(abl & 4u);
+                const bool live = valid && lane <= rc_lane;
                 if (pq_live && pq_tpos < room) T[pq_tpos] = tape_word('"', string_base + pq_off);  // the previous step's strings
                 pq_live = live && cls == K_QUOTE;
                 pq_tpos = tpos;
@@ -968,9 +965,6 @@ struct __attribute__((aligned(16))) TsRun {
 #ifndef SJMI_TS_WAVES
 #define SJMI_TS_WAVES 6
 #endif
-#ifndef SJMI_TS_NT_IDX
-#define SJMI_TS_NT_IDX 1  // the positions as streaming loads (the index array is read once, two whole lines an instruction): 1227 / 1231 -> 1212 / 1219 us
-#endif
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SJMI_TS_WAVES, SJMI_TS_WAVES)))
 k_tok_stream(TokArgs a_by_value) {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -1089,14 +1083,11 @@ k_tok_stream(TokArgs a_by_value) {
         auto fail_lanes = [&](unsigned long long M, uint32_t dj_v) {  // (rare) the documents of the lanes in M
             for (; M; M &= M - 1) failed |= 1ull << ((uint32_t)__builtin_amdgcn_readlane((int)dj_v, __builtin_ctzll(M)) & 63u);
         };
-        // positions are requested two chunks ahead, first bytes one chunk ahead
+        // positions are requested two chunks ahead, first bytes one chunk ahead; as streaming loads (the index array is read
+        // once, two whole lines an instruction): 1227 / 1231 -> 1212 / 1219 us
         auto pos_of = [&](uint32_t cc) -> uint32_t {
             const uint32_t i = cc * 64u + (uint32_t)lane;
-#if SJMI_TS_NT_IDX
             return __builtin_nontemporal_load(&a.idx[I0 + (i < n ? i : n - 1u)]);
-#else
-            return a.idx[I0 + (i < n ? i : n - 1u)];
-#endif
         };
         uint32_t Pa = pos_of(0), Pb = pos_of(1);
         uint32_t Ba = a.buf[Pa];
@@ -1758,10 +1749,8 @@ hipError_t coop_walk_launch(const uint8_t* d_buf, const unsigned long long* d_do
         hipError_t e0 = hipMemsetAsync(slow.count, 0, 64, stream);
         if (e0 != hipSuccess) return e0;
     }
-    const uint32_t abl = (uint32_t)(getenv("SJMI_COOP_ABLATE") ? atoi(getenv("SJMI_COOP_ABLATE")) : 0);
     ChunkWs cw = {};
-    static const bool no_chunks = getenv("SJMI_COOP_CHUNKS") && atoi(getenv("SJMI_COOP_CHUNKS")) == 0;
-    const bool chunked = d_chunk_ws && n_docs == 1 && count_bound > COOP_CHUNK_MIN && !no_chunks && !tail.no_chunks;
+    const bool chunked = d_chunk_ws && n_docs == 1 && count_bound > COOP_CHUNK_MIN && !tail.no_chunks;
     SingleFinish fin = {slow, d_tape_lens, d_doc_errors, tape_capacity, d_single_tape_offsets, d_res, tail.s1, tail.u, tail.pack};
     const bool optimistic = chunked && d_single_tape_offsets && tail.optimistic && tail.pack && count_bound > COOP_OPTIMISTIC_MIN;
     const uint32_t* only_if = nullptr;
@@ -1780,7 +1769,7 @@ hipError_t coop_walk_launch(const uint8_t* d_buf, const unsigned long long* d_do
         hipLaunchKernelGGL(k_group_replay, dim3(ggrid), dim3(256), 0, stream, d_index_offsets, cw);
         hipLaunchKernelGGL((k_coop_walk<true>), dim3(grid), dim3(256), 0, stream, d_buf, d_doc_offsets, n_docs, d_idx, d_index_offsets,
                            d_doc_status, d_soff, d_sb, d_doc_str_offsets, (unsigned long long)string_base, max_depth,
-                           d_scratch_tape, d_tape_lens, d_doc_errors, dev_count, dev_strings, d_res, abl, cw, (const uint32_t*)nullptr,
+                           d_scratch_tape, d_tape_lens, d_doc_errors, dev_count, dev_strings, d_res, cw, (const uint32_t*)nullptr,
                            (unsigned long long*)nullptr, slow, in_place);
         hipLaunchKernelGGL(k_chunk_finish, dim3(1), dim3(64), 0, stream, d_buf, d_idx, d_index_offsets, d_doc_status, d_scratch_tape,
                            d_tape_lens, d_doc_errors, dev_count, dev_strings, cw, fin, optimistic ? 1u : 0u);
@@ -1791,7 +1780,7 @@ hipError_t coop_walk_launch(const uint8_t* d_buf, const unsigned long long* d_do
     const unsigned grid = (unsigned)(want < COOP_WALK_MAX_GRID ? want : COOP_WALK_MAX_GRID);
     hipLaunchKernelGGL((k_coop_walk<false>), dim3(grid), dim3(256), 0, stream, d_buf, d_doc_offsets, n_docs, d_idx, d_index_offsets,
                        d_doc_status, d_soff, d_sb, d_doc_str_offsets, (unsigned long long)string_base, max_depth,
-                       d_scratch_tape, d_tape_lens, d_doc_errors, dev_count, dev_strings, d_res, abl, cw, only_if,
+                       d_scratch_tape, d_tape_lens, d_doc_errors, dev_count, dev_strings, d_res, cw, only_if,
                        static_cast<unsigned long long*>(d_deep_ws), slow, in_place);
     if (d_single_tape_offsets)
         hipLaunchKernelGGL(k_single_finish, dim3(1), dim3(64), 0, stream, d_buf, fin);
@@ -1837,18 +1826,9 @@ hipError_t tok_walk_launch(const TokLaunch& t, hipStream_t stream) {
         // j = ceil(runs / W) ROUNDS of runs -- with 16 documents per run a batch of 125,000 (one rank's share of a strong-scaled
         // million) is 1.27 rounds' worth of work done in 2.  The run is sized so that the rounds come out whole:
         // j = ceil(n / (W * TS_RUN)), run = ceil(n / (W * j)).  (125,000 documents: 11 per run, 188 -> 167 us.)
-        static std::atomic<unsigned> resident_waves{0};
-        unsigned W = resident_waves.load(std::memory_order_relaxed);
-        if (!W) {
-            int per_cu = 0, cus = 0, dev = 0;
-            if (hipGetDevice(&dev) != hipSuccess || hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_tok_stream, 256, 0) != hipSuccess ||
-                hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || per_cu < 1 || cus < 1) {
-                per_cu = 6;
-                cus = 256;
-            }
-            W = (unsigned)per_cu * (unsigned)cus * 4u;
-            resident_waves.store(W, std::memory_order_relaxed);
-        }
+        unsigned wgs = 0;
+        if (resident_workgroups<k_tok_stream>(&wgs) != hipSuccess) wgs = 6 * 256;  // (only the run size depends on it: launch anyway)
+        const unsigned W = wgs * 4u;
         static const unsigned run_forced = getenv("SJMI_TS_RUN_DOCS") ? (unsigned)atoi(getenv("SJMI_TS_RUN_DOCS")) : 0u;  // (experiments)
         const uint64_t j = (t.n_docs + (uint64_t)W * TS_RUN - 1) / ((uint64_t)W * TS_RUN);
         uint64_t run = (t.n_docs + (uint64_t)W * j - 1) / ((uint64_t)W * j);
@@ -1857,8 +1837,7 @@ hipError_t tok_walk_launch(const TokLaunch& t, hipStream_t stream) {
         if (run > TS_RUN) run = TS_RUN;
         a.run_docs = (uint32_t)run;
         const uint64_t runs = (t.n_docs + run - 1) / run, want_s = (runs + 3) / 4;  // four runs (waves) per workgroup and trip
-        static const unsigned tok_grid_max = getenv("SJMI_TOK_GRID") ? (unsigned)atoi(getenv("SJMI_TOK_GRID")) : (unsigned)COOP_WALK_MAX_GRID;
-        hipLaunchKernelGGL(k_tok_stream, dim3((unsigned)(want_s < tok_grid_max ? want_s : tok_grid_max)), dim3(256), 0, stream, a);
+        hipLaunchKernelGGL(k_tok_stream, dim3((unsigned)(want_s < COOP_WALK_MAX_GRID ? want_s : COOP_WALK_MAX_GRID)), dim3(256), 0, stream, a);
     }
     ExactMode ex;
     ex.list = t.d_list;
@@ -1866,11 +1845,10 @@ hipError_t tok_walk_launch(const TokLaunch& t, hipStream_t stream) {
     ex.tape = t.d_tape;
     ex.tape_alt = t.d_scratch;
     ex.sel = t.d_sel;
-    const uint32_t abl = (uint32_t)(getenv("SJMI_COOP_ABLATE") ? atoi(getenv("SJMI_COOP_ABLATE")) : 0);
     const unsigned xgrid = (unsigned)(want < 1024 ? want : 1024);
     hipLaunchKernelGGL((k_coop_walk<false>), dim3(xgrid), dim3(256), 0, stream, t.d_buf, t.d_doc_offsets, t.n_docs, t.d_idx,
                        t.d_index_offsets, t.d_doc_status, t.d_soff, t.d_sb, t.d_doc_str_ordinals, (unsigned long long)t.string_base,
-                       t.max_depth, t.d_scratch, t.d_tape_lens, t.d_doc_errors, t.dev_count, t.dev_strings, t.d_res, abl, ChunkWs{},
+                       t.max_depth, t.d_scratch, t.d_tape_lens, t.d_doc_errors, t.dev_count, t.dev_strings, t.d_res, ChunkWs{},
                        (const uint32_t*)nullptr, deep, slow, ex);
     hipLaunchKernelGGL(k_slow_doubles, dim3(256), dim3(64), 0, stream, t.d_buf, slow);  // (nothing listed: 256 waves that leave at once)
     return hipGetLastError();

@@ -49,7 +49,7 @@ struct sjmi_ctx {
                                   // zeroes the half the next one will use), grown on demand
     size_t ws_dev_clean[2] = {0, 0};  // bytes of each half known to be zero
     int ws_dev_next = 0;              // half the next launch uses
-    void* ws_dev_last = nullptr;      // half the last launch used (debug read-back)
+    void* ws_dev_last = nullptr;      // half the last launch used (its prefixes and batch flags)
     HostBuf<sjmi_stage1_result> h_res;
     HostBuf<void> h_pack;                 // {error index, stage-1 record, string record} of sjmi_stage1_unescape
     uint8_t* staging = nullptr;           // sjmi_set_input_staging: the caller's page-locked copy of the input
@@ -328,14 +328,6 @@ void sjmi_destroy(sjmi_ctx* c) {
 }
 
 const char* sjmi_last_error(const sjmi_ctx* c) { return c ? c->err.c_str() : "null context"; }
-
-#ifdef SJMI_TRACE
-extern "C" int sjmi_debug_read_ws(sjmi_ctx* c, void* dst, uint64_t offset, uint64_t bytes) {
-    if (!c || !c->ws_dev_last || offset + bytes > c->d_ws_dev.bytes / 2) return SJMI_ERR_ARG;
-    (void)hipDeviceSynchronize();
-    return hipMemcpy(dst, (uint8_t*)c->ws_dev_last + offset, bytes, hipMemcpyDeviceToHost) == hipSuccess ? SJMI_OK : SJMI_ERR_HIP;
-}
-#endif
 
 int sjmi_set_tile_steps(sjmi_ctx* c, int steps) {
     if (!c || !(steps == 0 || steps == 1 || steps == 2 || steps == 4)) return SJMI_ERR_ARG;

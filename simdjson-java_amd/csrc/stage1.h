@@ -4,6 +4,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <atomic>
+
 #include "../../include/sjmi.h"
 
 namespace sjmi {
@@ -349,5 +351,23 @@ size_t masks_workspace_bytes(uint64_t len);
 hipError_t masks_launch(const uint8_t* d_buf, uint64_t len, unsigned long long* d_masks, void* d_ws, hipStream_t stream);
 hipError_t transpose_selftest_launch(const uint32_t* d_words, uint32_t nblocks, uint32_t* d_mismatches,
                                      hipStream_t stream);
+
+// workgroups of 256 threads of KERNEL that are resident at the same time on the current device (the grid of a persistent
+// launch), cached per device and per kernel (contexts on several host threads may get here together)
+template <auto KERNEL>
+inline hipError_t resident_workgroups(unsigned* out) {
+    static std::atomic<unsigned> cached[16];
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return e;
+    const bool cacheable = dev >= 0 && dev < 16;
+    if (cacheable && (*out = cached[dev].load(std::memory_order_relaxed)) != 0) return hipSuccess;
+    int per_cu = 0, cus = 0;
+    if ((e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, KERNEL, 256, 0)) != hipSuccess) return e;
+    if ((e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev)) != hipSuccess) return e;
+    *out = (unsigned)(per_cu > 0 ? per_cu : 1) * (unsigned)(cus > 0 ? cus : 1);
+    if (cacheable) cached[dev].store(*out, std::memory_order_relaxed);
+    return hipSuccess;
+}
 
 }  // namespace sjmi

@@ -34,7 +34,6 @@
 #include <hip/hip_ext.h>
 #include <stdint.h>
 
-#include <atomic>
 #include <type_traits>
 
 #include "sj_block.h"
@@ -471,7 +470,7 @@ __device__ __forceinline__ void scanner_wave(ScanHandoff* hand, int wave, const 
 // A worker wave owns one granule of S * 4 KiB at a time (S steps of 64 blocks); its indexes are one contiguous run
 // of the output.  Waves never synchronise with each other: no barrier, no workgroup-level table -- a workgroup is
 // just four waves sharing an LDS allocation.  A per-tile timeline of the earlier one-tile-per-workgroup kernel
-// (tools/trace.py) showed ~8 of every workgroup's ~20 us spent in two bubbles: the first load of a fresh
+// showed ~8 of every workgroup's ~20 us spent in two bubbles: the first load of a fresh
 // workgroup (~2.7 us) and the wait between "aggregate published" and "prefix known" (~2 us for the slowest
 // predecessor + ~3 us of cross-XCD visibility and load latency); that kernel's time followed
 // T = 0.15 ms + 7 ns * tiles -- the bubbles over the ~1000 resident workgroups.  Here both are overlapped:
@@ -525,17 +524,6 @@ __device__ __forceinline__ void load_step(StepData& d, const uint8_t* __restrict
     d.halo = *reinterpret_cast<const sj_u64*>(buf + ((b > 0 || left_halo) ? (long long)(b * 64) - 8 : 0ll));
 }
 
-#ifdef SJMI_TRACE  // experiments only (tools/trace.py): per-granule timestamps behind the granule states
-#define SJMI_TRACE_SLOTS 6
-#define SJMI_TSTAMP(g_, k_)                                                                                    \
-    do {                                                                                                       \
-        if (lane == 0) (gstate + 2 * (sj_u64)ngran + (sj_u64)(g_) * SJMI_TRACE_SLOTS)[k_] = wall_clock64();     \
-    } while (0)
-#else
-#define SJMI_TRACE_SLOTS 0
-#define SJMI_TSTAMP(g_, k_) do { } while (0)
-#endif
-
 constexpr uint32_t NO_TILE = 0xFFFFFFFFu;
 
 // Device-resident path: nothing but the kernel is queued per launch.  Every worker wave, on its way out, zeroes its
@@ -555,20 +543,9 @@ __device__ __forceinline__ void zero_next_workspace(uint4* zero_ptr, uint32_t ze
 constexpr uint32_t TICKET_CLASSES = 8;
 constexpr int LB_K = 1;  // SAFE mode's look-back window = 64 * LB_K granules
 
-#ifndef SJMI_S1_SORT
-#define SJMI_S1_SORT 1       // the expansion's half masks handed out by population (stage1_body, sorted_round)
-#endif
-#ifndef SJMI_S1_SORT_PLAIN
-#define SJMI_S1_SORT_PLAIN 1 // ... in k_stage1 as well as in k_stage1_batch
-#endif
-#ifndef SJMI_S1_TWO_ENDED
-#define SJMI_S1_TWO_ENDED 1  // the sorted round's per-bit loop takes the lowest AND the highest set bit a trip (k_stage1_batch 366 -> 356 us; the headline does not notice)
-#endif
-#ifndef SJMI_S1_NT_STORE
-#define SJMI_S1_NT_STORE 4  // 0: plain index stores; 1: streaming stores everywhere; 4: in the plain 16 KiB-granule kernels only
-#endif
 #ifndef SJMI_S1_SORT_MIN
-#define SJMI_S1_SORT_MIN 192 // ... for a round of more than this many indexes per 4 KiB step (below: the sort costs more than it saves)
+#define SJMI_S1_SORT_MIN 192 // the expansion's half masks are handed out by population (sorted_round) for a round of more than this
+                             // many indexes per 4 KiB step (below: the sort costs more than it saves)
 #endif
 // S = 4 KiB steps per granule, LDSW = bytes of LDS per wave
 template <int S>
@@ -652,7 +629,7 @@ stage1_body(const uint8_t* __restrict__ buf, sj_u64 len, uint32_t* __restrict__ 
     const uint32_t cls = worker % NC;
     uint32_t* const my_ticket = ticket + cls * 16u;                 // one counter per 64-byte line
     // The scanner's high-priority waves slow the workers that share its CU to ~2/3 speed, and a slow worker holds
-    // up the whole chain (per-CU timeline: tools/trace.py), so those workers retire after their first granule.
+    // up the whole chain (per-CU timeline), so those workers retire after their first granule.
     uint32_t retire = 0;
     if (!safe && gridDim.x >= 64)
         retire = __hip_atomic_load(scanner_cu, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) ^ my_cu;  // 0 = same CU (used a granule later)
@@ -687,7 +664,6 @@ stage1_body(const uint8_t* __restrict__ buf, sj_u64 len, uint32_t* __restrict__ 
             // up nobody: classification gets the SIMD first (equal priorities go oldest wave first, for ever the same
             // wave last in a persistent kernel: classifications of 25 us instead of 9 in the timeline)
             __builtin_amdgcn_s_setprio(2);
-            SJMI_TSTAMP(cur, 0);
             const uint32_t blk0 = cur * (64u * S);  // (block numbers are 32-bit: load_step)
             sj_u64 sm[S];
             uint32_t fl[S];     // bit0 quote parity, bit1 ue0, bit2 ue1, bit3 utf8 error
@@ -804,7 +780,6 @@ stage1_body(const uint8_t* __restrict__ buf, sj_u64 len, uint32_t* __restrict__ 
                 if (safe && cur == 0) publish_prefix(agg, 0, wpar ^ entry_par, (sj_u64)(entry_par ? WP - W0 : W0));  // nothing to look back at
                 else publish_aggregate(agg, cur, W0, WP - W0, wpar, gbits);
             }
-            SJMI_TSTAMP(cur, 1);
             __builtin_amdgcn_s_setprio(0);
         }
         uint32_t nxt = NO_TILE;
@@ -824,7 +799,6 @@ stage1_body(const uint8_t* __restrict__ buf, sj_u64 len, uint32_t* __restrict__ 
         if (prev != NO_TILE) {
             uint32_t pe = entry_par;  // parity entering the granule (granule 0: the document's / shard's own)
             sj_u64 cnt_in = 0;
-            SJMI_TSTAMP(prev, 2);
             if (dbg & DBG_NO_LOOKBACK) {  // ablation: no chain (indexes land at fake offsets)
                 cnt_in = (sj_u64)prev * 512ull * S;  // 1 index slot per 8 input bytes (ablation buffers are sized for it)
             } else if (prev != 0) {
@@ -844,7 +818,6 @@ stage1_body(const uint8_t* __restrict__ buf, sj_u64 len, uint32_t* __restrict__ 
                     cnt_in = pf & ((1ull << 40) - 1ull);
                 }
             }
-            SJMI_TSTAMP(prev, 3);
             const uint32_t WT_all = pe ? prev_c1 : prev_c0;  // indexes of the granule
             if (safe && lane == 0 && !(dbg & DBG_NO_LOOKBACK)) {
                 if (prev != 0) publish_prefix(agg, prev, pe ^ prev_par, cnt_in + WT_all);
@@ -912,7 +885,7 @@ stage1_body(const uint8_t* __restrict__ buf, sj_u64 len, uint32_t* __restrict__ 
                                 //  caches anyway -- streaming stores: +1.4 % on the headline, +1.5 % on twitter x1024; small documents keep
                                 //  theirs in L2 for the kernels behind this one, and the batch flavour is 3.5 % SLOWER with them:
                                 //  profiles/r6/README.md)
-                                if constexpr (SJMI_S1_NT_STORE == 1 || (SJMI_S1_NT_STORE == 4 && S == 4 && !BATCH)) {
+                                if constexpr (S == 4 && !BATCH) {
                                     typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
                                     u32x4_t nv = {v.x, v.y, v.z, v.w};
                                     __builtin_nontemporal_store(nv, reinterpret_cast<u32x4_t*>(gbp) + qi);
@@ -928,11 +901,10 @@ stage1_body(const uint8_t* __restrict__ buf, sj_u64 len, uint32_t* __restrict__ 
                         }
                         wave_lds_fence();
                     };
-                    auto fast_round = [&](int e0, int e1, uint32_t rbase, uint32_t rcount) {
+                    auto fast_round = [&](uint32_t rbase, uint32_t rcount) {
                         const uint32_t g0 = (uint32_t)((cnt_in + gbase + rbase) & 3ull);
 #pragma unroll
                         for (int e = 0; e < E; ++e) {
-                            if (e < e0 || e >= e1) continue;  // (wave-uniform; e itself stays a constant: mk / pos are registers)
                             const uint32_t bstart = (uint32_t)((pblk0 + (sj_u64)(g * E + e) * 64 + lane) * 64);
                             uint32_t* q = stage + g0 + (pos[e] - rbase);
                             for (uint32_t lo = (uint32_t)mk[e]; lo; lo &= lo - 1) *q++ = bstart | (uint32_t)__builtin_ctz(lo);
@@ -942,7 +914,7 @@ stage1_body(const uint8_t* __restrict__ buf, sj_u64 len, uint32_t* __restrict__ 
                         wave_lds_fence();
                         flush_round(rbase, rcount, g0);
                     };
-                    // The per-bit loops above run as long as the BUSIEST lane of each of their 2 (e1 - e0) trips has bits: 151 trips of
+                    // The per-bit loops above run as long as the BUSIEST lane of each of their 2 * E trips has bits: 151 trips of
                     // the loop body per 16 KiB of the configs[3] documents for a mean of 48 indexes per lane (56 for 22 on
                     // twitter.json) -- a third of the lanes at work.  The sorted form hands the round's 32-bit half masks out again by
                     // population: a counting sort in LDS (histogram by LDS atomics = the rank inside a bucket, one scan over the 33
@@ -993,7 +965,6 @@ stage1_body(const uint8_t* __restrict__ buf, sj_u64 len, uint32_t* __restrict__ 
                             if ((uint32_t)r >= trips) break;  // (wave-uniform)
                             uint32_t* q = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(stage) + (it[r].y & 0xFFFFu));
                             const uint32_t bv = b32 + (it[r].y >> 16);
-#if SJMI_S1_TWO_ENDED
                             // two indexes a trip: the lowest set bit to the front slot, the highest to the back one (a last single
                             // bit goes to the same slot twice)
                             uint32_t lo = it[r].x;
@@ -1004,9 +975,6 @@ stage1_body(const uint8_t* __restrict__ buf, sj_u64 len, uint32_t* __restrict__ 
                                 *qh-- = bv | (lz ^ 31u);
                                 lo = lo & (lo - 1) & ~(0x80000000u >> lz);
                             }
-#else
-                            for (uint32_t lo = it[r].x; lo; lo &= lo - 1) *q++ = bv | (uint32_t)__builtin_ctz(lo);
-#endif
                         }
                         wave_lds_fence();
                         flush_round(rbase, rcount, g0);
@@ -1015,22 +983,16 @@ stage1_body(const uint8_t* __restrict__ buf, sj_u64 len, uint32_t* __restrict__ 
                     //  the 2,304 slots, but each half of the granule fits)
                     const uint32_t split = E >= 2 ? (uint32_t)__builtin_amdgcn_readfirstlane((int)pos[E / 2]) : 0u;
                     using std::integral_constant;
-                    constexpr bool do_sort = SJMI_S1_SORT && (BATCH || SJMI_S1_SORT_PLAIN);
                     bool staged = false;
                     if (WT + 3 <= (uint32_t)CAP) {
-                        if (do_sort && WT > (uint32_t)(SJMI_S1_SORT_MIN * E)) sorted_round(integral_constant<int, 0>{}, integral_constant<int, E>{}, 0, WT);
-                        else fast_round(0, E, 0, WT);
+                        if (WT > (uint32_t)(SJMI_S1_SORT_MIN * E)) sorted_round(integral_constant<int, 0>{}, integral_constant<int, E>{}, 0, WT);
+                        else fast_round(0, WT);
                         staged = true;
                     }
                     if constexpr (E >= 2) {
                         if (!staged && split + 3 <= (uint32_t)CAP && WT - split + 3 <= (uint32_t)CAP) {
-                            if (do_sort) {
-                                sorted_round(integral_constant<int, 0>{}, integral_constant<int, E / 2>{}, 0, split);
-                                sorted_round(integral_constant<int, E / 2>{}, integral_constant<int, E>{}, split, WT - split);
-                            } else {
-                                fast_round(0, E / 2, 0, split);
-                                fast_round(E / 2, E, split, WT - split);
-                            }
+                            sorted_round(integral_constant<int, 0>{}, integral_constant<int, E / 2>{}, 0, split);
+                            sorted_round(integral_constant<int, E / 2>{}, integral_constant<int, E>{}, split, WT - split);
                             staged = true;
                         }
                     }
@@ -1064,12 +1026,6 @@ stage1_body(const uint8_t* __restrict__ buf, sj_u64 len, uint32_t* __restrict__ 
                     }
                 }
             }
-            SJMI_TSTAMP(prev, 4);
-#ifdef SJMI_TRACE
-            if (lane == 0)
-                (gstate + 2 * (sj_u64)ngran + (sj_u64)prev * SJMI_TRACE_SLOTS)[5] =
-                    (sj_u64)__builtin_amdgcn_s_getreg((31 << 11) | 4) | ((sj_u64)__builtin_amdgcn_s_getreg((31 << 11) | 20) << 32);
-#endif
         }
         if (!have) break;
         // park granule `cur` until its prefix is known (next iteration)
@@ -1152,7 +1108,7 @@ static uint64_t granules_for(uint64_t len, int steps, bool no_tail = false) {
 }
 
 size_t stage1_workspace_bytes(uint64_t len, int steps) {
-    return WS_TILE_STATE_OFFSET + (2 + SJMI_TRACE_SLOTS) * (size_t)granules_for(len, steps) * sizeof(sj_u64);
+    return WS_TILE_STATE_OFFSET + 2 * (size_t)granules_for(len, steps) * sizeof(sj_u64);
 }
 // The scanner's inclusive prefixes of a finished FAST launch over (len, steps), still in its workspace until the launch after
 // next: entry g = [63:62] == 2, [39:0] structurals in granules 0..g (a granule = steps * 4 KiB of input).  For consumers that
@@ -1172,34 +1128,12 @@ int stage1_pick_steps(uint64_t len) {
     return len <= (4u << 20) ? 1 : (len <= (16u << 20) ? 2 : 4);
 }
 
-// workgroups of k_stage1<...> that are resident at the same time on the current device (fast mode's grid)
-template <int S, int LDSW, bool SAFE, bool BATCH>
-static hipError_t resident_workgroups(unsigned* out) {
-    static std::atomic<unsigned> cached[16];  // (contexts on several host threads may get here together)
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    if (dev < 0 || dev >= 16 || !cached[dev]) {
-        int per_cu = 0, cus = 0;
-        if ((e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, Stage1Kernel<S, LDSW, SAFE, BATCH>::fn, 256, 0)) != hipSuccess) return e;
-        if ((e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev)) != hipSuccess) return e;
-        const unsigned n = (unsigned)(per_cu > 0 ? per_cu : 1) * (unsigned)(cus > 0 ? cus : 1);
-        if (dev < 0 || dev >= 16) {
-            *out = n;
-            return hipSuccess;
-        }
-        cached[dev].store(n, std::memory_order_relaxed);
-    }
-    *out = cached[dev];
-    return hipSuccess;
-}
-
 template <int S, int LDSW, bool SAFE, bool BATCH>
 static hipError_t launch_mode(const uint8_t* d_buf, uint64_t len, uint32_t* d_out, uint64_t out_cap, sj_u64* gs,
                                  uint32_t* ticket, Stage1Result* res, uint64_t ngran, hipStream_t stream,
                                  hipEvent_t ev_start, hipEvent_t ev_stop, uint32_t dbg, const Stage1Extras& ex) {
     unsigned resident = 0;
-    hipError_t e = resident_workgroups<S, LDSW, SAFE, BATCH>(&resident);
+    hipError_t e = resident_workgroups<Stage1Kernel<S, LDSW, SAFE, BATCH>::fn>(&resident);  // (fast mode's grid)
     if (e != hipSuccess) return e;
     const uint64_t want = (ngran + 3) / 4 + (SAFE ? 0 : 1);  // 4 worker waves each + the scanner workgroup
     if (dbg & DBG_SMALL_GRID) resident = SAFE ? 8 : 9;  // test hook: far fewer granules in flight than a scanner window
@@ -1243,7 +1177,7 @@ hipError_t stage1_launch(const uint8_t* d_buf, uint64_t len, uint32_t* d_out, ui
                          int steps, hipStream_t stream, hipEvent_t ev_start, hipEvent_t ev_stop, uint32_t dbg, const Stage1Extras& ex) {
     const uint64_t ngran = granules_for(len, steps, (dbg & FLAG_NO_TAIL) != 0);
     if (ngran == 0) return hipErrorInvalidValue;  // (an empty shard without a tail block: nothing to launch)
-    const size_t ws_bytes = WS_TILE_STATE_OFFSET + (2 + SJMI_TRACE_SLOTS) * (size_t)ngran * sizeof(sj_u64);
+    const size_t ws_bytes = WS_TILE_STATE_OFFSET + 2 * (size_t)ngran * sizeof(sj_u64);
     hipError_t e = hipSuccess;
     if (!ex.workspace_is_zero && (e = hipMemsetAsync(d_ws, 0, ws_bytes, stream)) != hipSuccess) return e;
     uint8_t* ws = static_cast<uint8_t*>(d_ws);

@@ -31,15 +31,9 @@
 #include <hip/hip_ext.h>
 #include <stdint.h>
 
-#include <atomic>
-
 #include "sj_strings.h"
 #include "sj_block32.h"
 #include "stage1.h"
-
-#ifndef SJMI_STR_ABL
-#define SJMI_STR_ABL 0  // ablation experiments only (results invalid): 1 no headers, 2 no copy, 4 no stores, 8 no \\u patches
-#endif
 
 namespace sjmi {
 
@@ -387,10 +381,6 @@ k_strings(const StrArgs a0) {
     uint32_t prev = STR_NONE, prev_n = 0, prev_pend = STR_NONE, prev_fclose = STR_NONE, prev_fclose_err = 0, prev_nopen = 0;
     uint32_t prev_oexcl = 0;  // per lane
     sj_u64 pf = 0, pf_or = 0, pf_pp = 0;  // requested a classification ahead: pfx[prev-1], orec[prev-1], pfx[prev-2]
-    uint32_t err_wave = 0;
-#ifdef SJMI_STR_SPINSTAT
-    unsigned long long stat_waits = 0, stat_spins = 0, stat_flushes = 0;
-#endif
 
     for (;;) {
         const bool have = cur < ngran;
@@ -453,12 +443,7 @@ k_strings(const StrArgs a0) {
             const uint32_t euc_hi_prev = (uint32_t)__shfl_up((int)(uint32_t)(euc >> 32), 1);
             const bool halo_bs = blk > 0 && active && (swar_has_backslash(hq.y) | swar_has_backslash(hq.z) | swar_has_backslash(hq.w));
             const bool trig = euc != 0 || (lane > 0 ? (euc_hi_prev >> 22) != 0 : halo_bs);
-#ifdef SJMI_STR_NO_U  /* experiment: how fast is the pass without the \u look-back in its register budget */
-            const bool do_u = false;
-            (void)trig;
-#else
             const bool do_u = __ballot(trig) != 0;
-#endif
             SjStrHalo halo;
             halo.e_in = 0;
             if (do_u) {
@@ -534,7 +519,6 @@ k_strings(const StrArgs a0) {
                     const sj_u64 bal = __ballot(cand != 0);
                     fclose_err = bal ? (uint32_t)__builtin_amdgcn_readlane((int)cand, __builtin_ctzll(bal)) : 0u;
                 }
-                err_wave = 1;
             }
             if (lane == 0) {
                 sg_store(&orec[cur], OR_VALID | ((exit_in && open_lanes) ? OR_HAS_OPEN : 0ull) | ((sj_u64)pend_err << 16) |
@@ -597,14 +581,7 @@ k_strings(const StrArgs a0) {
             sj_u64 outbase = 0;
             uint32_t ordbase = 0;
             if (prev != 0) {
-#ifdef SJMI_STR_SPINSTAT
-                if ((pf >> 62) != 2) ++stat_waits;
-                ++stat_flushes;
-#endif
                 for (uint32_t spins = 0; (pf >> 62) != 2; ++spins) {
-#ifdef SJMI_STR_SPINSTAT
-                    ++stat_spins;
-#endif
                     if (spins > STR_SPIN_LIMIT) {  // never expected: the scanner is not running
                         if (lane == 0) {
                             __hip_atomic_fetch_or(&a.wsflags[0], SJMI_ST_INTERNAL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -619,7 +596,7 @@ k_strings(const StrArgs a0) {
                 ordbase = (uint32_t)(pf >> 32) & 0x3FFFFFFFu;
             }
             const bool fits = (pf >> 62) == 2 || prev == 0 ? (outbase != 0xFFFFFFFFull && outbase + prev_n <= a.sb_cap) : false;
-            if (fits && !(SJMI_STR_ABL & 4)) {
+            if (fits) {
                 // 16-byte chunks of the tile, stored to byte-granular addresses (gfx950 global memory runs in unaligned access
                 // mode; measured against an LDS funnel shift to 16-byte aligned stores: 3.6 % faster).  The two chunks around a
                 // header that another granule will write, and the tail, go byte by byte, one byte per lane.
@@ -708,7 +685,7 @@ k_strings(const StrArgs a0) {
             const uint32_t Clo = (uint32_t)Kc, Chi = (uint32_t)(Kc >> 32);
             const uint32_t Bhi = B + (uint32_t)__popc(Klo) + 4u * (uint32_t)__popc(Olo);
 #pragma unroll
-            for (int i = 0; i < ((SJMI_STR_ABL & 2) ? 0 : 16); ++i) {
+            for (int i = 0; i < 16; ++i) {
                 const int sft = 4 * (i & 7);
                 const uint32_t ltm = (1u << sft) - 1u, grp = 0xFu << sft;
                 const uint32_t Kh = i < 8 ? Klo : Khi, Oh = i < 8 ? Olo : Ohi, Sh = i < 8 ? Slo : Shi, Ch = i < 8 ? Clo : Chi;
@@ -731,8 +708,7 @@ k_strings(const StrArgs a0) {
             str_lds_fence();
             // ---- headers, by the closing quotes: length = kept bytes between the quotes (32-bit halves: 64-bit shifts by
             //      a variable are slow) ----
-            if (SJMI_STR_ABL & 1) {
-            } else if (!any_err) {
+            if (!any_err) {
                 // The records of a block lie back to back -- [be32 length][bytes][be32 length][bytes] ...: nothing is kept between
                 // a closing quote and the next opening one -- so the header of the NEXT string begins where the output offset of a
                 // closing quote ends, and that offset is one v_bcnt (popcount + addend) once the header slots in front of it are
@@ -826,7 +802,7 @@ k_strings(const StrArgs a0) {
                     }
                 }
             }
-            if (any_items && u_dense && !(SJMI_STR_ABL & 8)) {  // \uXXXX: the UTF-8 bytes over the last hex digits (StringParser.java:126-153)
+            if (any_items && u_dense) {  // \uXXXX: the UTF-8 bytes over the last hex digits (StringParser.java:126-153)
                 const uint32_t* const uq = s_uq[wave];
                 for (uint32_t c0 = 0; c0 < u_n; c0 += 64) {
                     const uint32_t it = c0 + (uint32_t)lane;
@@ -850,7 +826,7 @@ k_strings(const StrArgs a0) {
                         tile_xor(tile, (ent & 0x3FFFu) - (L - 1u), old ^ nb);
                     }
                 }
-            } else if (any_items && !(SJMI_STR_ABL & 8)) {
+            } else if (any_items) {
                 int t = 0;
                 for (sj_u64 x = items; x; x &= x - 1, ++t) {
                     const uint32_t e = (uint32_t)__builtin_ctzll(x);
@@ -898,10 +874,6 @@ k_strings(const StrArgs a0) {
         prev_oexcl = oexcl;
         cur = nxt;
     }
-    (void)err_wave;
-#ifdef SJMI_STR_SPINSTAT  // experiments only: how often and how long the flush waited for its prefix (in the result record)
-    if (lane == 0) atomicAdd(reinterpret_cast<unsigned long long*>(&a.res->first_error_inv), stat_waits | (stat_spins << 20) | (stat_flushes << 44));
-#endif
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -917,27 +889,6 @@ size_t strings_workspace_bytes(uint64_t len) { return STR_WS_STATE_OFFSET + 3 * 
 size_t strings_parity_words(uint64_t len) { return (size_t)str_granules(len) + 4; }
 // a result record inside the workspace: strings_launch zeroes it with the rest (one memset less on the latency path)
 UnescapeResult* strings_workspace_result(void* d_ws) { return reinterpret_cast<UnescapeResult*>(static_cast<uint8_t*>(d_ws) + STR_WS_RESULT_OFFSET); }
-
-template <bool SOFF>
-static hipError_t str_resident(unsigned* out) {
-    static std::atomic<unsigned> cached[16];
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    if (dev < 0 || dev >= 16 || !cached[dev]) {
-        int per_cu = 0, cus = 0;
-        if ((e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_strings<SOFF>, 256, 0)) != hipSuccess) return e;
-        if ((e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev)) != hipSuccess) return e;
-        const unsigned n = (unsigned)(per_cu > 0 ? per_cu : 1) * (unsigned)(cus > 0 ? cus : 1);
-        if (dev < 0 || dev >= 16) {
-            *out = n;
-            return hipSuccess;
-        }
-        cached[dev].store(n, std::memory_order_relaxed);
-    }
-    *out = cached[dev];
-    return hipSuccess;
-}
 
 // d_res must have been zeroed by the caller's stream order (first_error_inv / flags accumulate); the records of every
 // string literal of buf[0, len) go to d_sb; optional: d_soff (offset of record k), d_blk_ord (see StrArgs)
@@ -970,7 +921,7 @@ hipError_t strings_launch(const uint8_t* d_buf, uint64_t len, const unsigned lon
     a.skip = d_skip;
     const bool soff = d_soff != nullptr || d_blk_ord != nullptr;
     unsigned resident = 0;
-    e = soff ? str_resident<true>(&resident) : str_resident<false>(&resident);
+    e = soff ? resident_workgroups<k_strings<true>>(&resident) : resident_workgroups<k_strings<false>>(&resident);
     if (e != hipSuccess) return e;
     const uint64_t want = (ngran + 3) / 4 + 1;
     const dim3 grid((unsigned)(want < resident ? want : resident)), block(256);

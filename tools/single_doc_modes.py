@@ -1,5 +1,5 @@
 """Single-document latency of the two walker placements (host walker over the stage-1 output vs all three stages on the
-device), twitter.json and a 64 MiB array of small objects; SJMI_COOP_CHUNKS=0 forces the single-wave sweep."""
+device), twitter.json and a 64 MiB array of small objects."""
 import gzip
 import os
 import sys
@@ -44,5 +44,5 @@ for name, doc, reps in cases:
         for _ in range(reps):
             p.parse(doc)
         t = (time.perf_counter() - t0) / reps
-        print("%s gpu_walk=%s chunks=%s: parse %.3f ms = %.2f GB/s" % (name, mode, os.environ.get("SJMI_COOP_CHUNKS", "1"), t * 1e3, len(doc) / t / 1e9))
+        print("%s gpu_walk=%s: parse %.3f ms = %.2f GB/s" % (name, mode, t * 1e3, len(doc) / t / 1e9))
         p.close()
