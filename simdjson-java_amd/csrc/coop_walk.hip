@@ -725,12 +725,16 @@ k_coop_walk(const uint8_t* __restrict__ buf, const unsigned long long* __restric
                             err = cw_primitive(buf, win, p, i == from, doc_end, &ptype, &praw);
                             if (err == CW_SLOW_DOUBLE) {  // (rare) listed for k_slow_doubles, which overwrites the candidate
                                 err = 0;
-                                const unsigned long long slot = atomicAdd(slow.count, 1ull);
-                                if (slot < slow.cap && tpos + 1 < room) {
-                                    slow.rec[2 * slot] = reinterpret_cast<unsigned long long>(T + tpos + 1);
-                                    slow.rec[2 * slot + 1] = (unsigned long long)p | ((unsigned long long)(i == from ? doc_end : 0xFFFFFFFFu) << 32);
-                                } else {
-                                    err = SJMI_WALK_NEEDS_HOST;  // (more than 65,536 such literals in one launch)
+                                // a word behind the tape's room is not stored, and the tape's length reports the shortfall: nothing to
+                                // list then.  Every slot taken below the cap gets its record (the finishers read each one of them).
+                                if (tpos + 1 < room) {
+                                    const unsigned long long slot = atomicAdd(slow.count, 1ull);
+                                    if (slot < slow.cap) {
+                                        slow.rec[2 * slot] = reinterpret_cast<unsigned long long>(T + tpos + 1);
+                                        slow.rec[2 * slot + 1] = (unsigned long long)p | ((unsigned long long)(i == from ? doc_end : 0xFFFFFFFFu) << 32);
+                                    } else {
+                                        err = SJMI_WALK_NEEDS_HOST;  // (more than 65,536 such literals in one launch)
+                                    }
                                 }
                             }
                         }

@@ -17,12 +17,13 @@ pytestmark = pytest.mark.gpu
 CANARY, CANARY_WORDS = 0x7E5A7E5A7E5A7E5A, 512
 
 
-def gpu_walk(ctx, docs, max_depth=1024):
-    """isolated stage 1 -> strings -> walk, all device-resident; -> (tapes list / None, strings bytes, errors int32)."""
+def gpu_walk(ctx, docs, max_depth=1024, packed=None, pad=0):
+    """isolated stage 1 -> strings -> walk, all device-resident; -> (tapes list / None, strings bytes, errors int32).
+    packed: (buffer, offsets) of the documents instead of _pack's; pad: the value of the 128 bytes behind the batch."""
     import torch
-    buf, offs = _pack(docs)
+    buf, offs = _pack(docs) if packed is None else packed
     n = len(docs)
-    d_buf = torch.zeros(len(buf) + 128, dtype=torch.uint8, device="cuda")
+    d_buf = torch.full((len(buf) + 128,), pad, dtype=torch.uint8, device="cuda")
     d_buf[:len(buf)] = torch.frombuffer(bytearray(buf), dtype=torch.uint8).cuda()
     d_offs = torch.from_numpy(offs.astype(np.int64)).cuda()
     d_idx = torch.zeros(len(buf) + 2, dtype=torch.int32, device="cuda")

@@ -94,3 +94,121 @@ def assert_tape_equal(got, got_strings, want, what=None):
         go, wo = g & int(low), w & int(low)
         ln = int.from_bytes(want.strings[wo:wo + 4], "big")
         assert got_strings[go:go + 4 + ln] == want.strings[wo:wo + 4 + ln], (what, "string word %d" % i, go, wo)
+
+
+_LITERAL = None
+
+
+def exact_number(lit):
+    """Plain reference for one JSON number literal, exact by construction: -> ('l', raw) for an integer inside the long range,
+    ('d', raw) for a floating literal (the decimal value as a Fraction, rounded to binary64 with ties to even: subnormals, and
+    +-infinity past the largest double, as the reference's DoubleParser gives them), None for anything else (bad grammar, an
+    integer outside [-2^63, 2^63 - 1]).  raw = the tape's second word (two's complement / IEEE bits as an unsigned 64-bit int)."""
+    import re
+    from fractions import Fraction
+    global _LITERAL
+    if _LITERAL is None:
+        _LITERAL = re.compile(r"(-?)(0|[1-9][0-9]*)(?:\.([0-9]+))?(?:[eE]([+-]?[0-9]+))?\Z")
+    m = _LITERAL.match(lit)
+    if not m:
+        return None
+    sign, ip, fp, ex = m.group(1), m.group(2), m.group(3), m.group(4)
+    if fp is None and ex is None:
+        v = int(sign + ip)
+        return ("l", v & (2 ** 64 - 1)) if -2 ** 63 <= v < 2 ** 63 else None
+    neg = 1 << 63 if sign else 0
+    digits = (ip + (fp or "")).lstrip("0")
+    if not digits:
+        return ("d", neg)
+    e10 = int(ex or "0") - len(fp or "")                # value = int(digits) * 10^e10
+    lead = e10 + len(digits) - 1                        # decimal exponent of the leading digit
+    if lead > 310:
+        return ("d", neg | 0x7FF0000000000000)
+    if lead < -330:                                     # below half the smallest subnormal (~2.47e-324)
+        return ("d", neg)
+    x = Fraction(int(digits)) * (Fraction(10) ** e10)
+    # x = q * 2^e with 2^52 <= q < 2^53 (q a real here), e >= -1074: the quantum of the subnormals
+    e = max(x.numerator.bit_length() - x.denominator.bit_length() - 53, -1074)
+    while e > -1074 and x < Fraction(2 ** 52) * Fraction(2) ** e:
+        e -= 1
+    while x >= Fraction(2 ** 53) * Fraction(2) ** e:
+        e += 1
+    s = x / Fraction(2) ** e
+    q, r = divmod(s.numerator, s.denominator)
+    if 2 * r > s.denominator or (2 * r == s.denominator and q & 1):
+        q += 1
+    if q == 2 ** 53:
+        q, e = q >> 1, e + 1
+    if q < 2 ** 52:                                     # subnormal (or zero): e == -1074, biased exponent 0
+        return ("d", neg | q)
+    biased = e + 1075
+    if biased >= 2047:
+        return ("d", neg | 0x7FF0000000000000)
+    return ("d", neg | (biased << 52) | (q - 2 ** 52))
+
+
+def tape_numbers(tape):
+    """The number words of a tape in order: [(type char, raw second word)] -- 'l' / 'd' words are followed by their payload."""
+    out, i = [], 0
+    words = [int(w) for w in tape]
+    while i < len(words):
+        t = words[i] >> 56
+        if t in (0x6C, 0x64):
+            out.append((chr(t), words[i + 1]))
+            i += 2
+        else:
+            i += 1
+    return out
+
+
+def _midpoint_text(rng):
+    """The exact decimal midpoint of two neighbouring doubles, as text (no sign), and whether it needs an exponent: short ones
+    (between 2^52 and 2^64: an integer, or an integer + .5), the subnormals, the overflow edge."""
+    from decimal import Decimal, getcontext
+    getcontext().prec = 1200
+    r = rng.random()
+    if r < 0.85:
+        e = rng.randint(0, 11)
+        m = rng.randrange(2 ** 52, 2 ** 53)
+        mid2 = (2 * m + 1) << e                          # twice the midpoint of m * 2^e and (m + 1) * 2^e
+        return ("%d.5" % (mid2 >> 1)) if e == 0 else str(mid2 >> 1)
+    if r < 0.95:                                         # subnormal: (2k + 1) * 2^-1075
+        k = rng.choice([0, 1, 2, rng.randrange(2 ** 20), rng.randrange(2 ** 52)])
+        return format(Decimal(2 * k + 1) / (Decimal(2) ** 1075), "f")
+    # between the largest double and 2^1024 (rounds to infinity from the midpoint up), and just below the largest double
+    m = (1 << 53) - rng.choice([1, 2])
+    return str((2 * m + 1) << 970)                      # (m * 2^971: the largest double for m = 2^53 - 1)
+
+
+def boundary_literal(rng, short=True):
+    """A floating literal of more than 19 significant digits that its two 19-digit neighbours w * 10^q and (w + 1) * 10^q do
+    not decide (exact_range is False: the device lists it for the exact midpoint comparison of sj_bigdec.h): an exact midpoint
+    of two doubles with a nonzero tail behind it, or just below it.  short: mostly 30 .. 45 bytes."""
+    while True:
+        text = _midpoint_text(rng)
+        if "." not in text:
+            text += ".0"
+        ip, fp = text.split(".")
+        above = rng.random() < 0.5
+        if above:                                        # just above: the midpoint, zeros, a last nonzero digit
+            fp = fp + "0" * rng.randint(0, 6) + rng.choice("123456789")
+        else:                                            # just below: minus one unit in the last place, then nines
+            digits = str(int(ip + fp) - 1).rjust(len(ip + fp), "0")
+            ip, fp = digits[:len(ip)], digits[len(ip):] + "9" * rng.randint(1, 6)
+        sig = (ip + fp).lstrip("0")
+        if len(sig) > 60 or rng.random() < 0.3:          # scientific form: d.ddd...e<exp>, cut after 24 .. 40 digits
+            lead = len(ip.lstrip("0")) - 1 if ip.lstrip("0") else -(len(fp) - len(fp.lstrip("0")) + 1)
+            cut = sig[:rng.randint(24, 40)]
+            if above and len(cut) < len(sig):            # (cut short: one unit up stays above the midpoint)
+                cut = str(int(cut) + 1)
+            cut = cut.rstrip("0")
+            if len(cut) < 21:
+                continue
+            lit = "%s.%se%s%d" % (cut[0], cut[1:], rng.choice(["", "+"]) if lead >= 0 else "", lead)
+            if rng.random() < 0.5:
+                lit = lit.replace("e", "E")
+        else:
+            lit = ip + "." + fp
+        lit = ("-" if rng.random() < 0.4 else "") + lit
+        if not exact_range(lit) and (not short or len(lit) <= 48):
+            return lit
