@@ -254,16 +254,17 @@ hipError_t parity_launch(sjmi_ctx* c, const uint8_t* d_buf, uint64_t len, hipStr
     return e;
 }
 // The block parities of (d_buf, len) for the string pass: those of the context's last stage-1 launch if it was over the same
-// bytes, else a parity-only launch queued on `st`.
+// bytes, else a parity-only launch queued on `st`.  Parities derived here serve this call only: the caller may put other bytes
+// under the same pointer before the next call (a caching allocator hands the same block out again), and only a stage-1 launch
+// over them describes them (include/sjmi.h, sjmi_unescape_device).
 const unsigned long long* parity_for(sjmi_ctx* c, const void* d_buf, uint64_t len, hipStream_t st) {
     if (c->par_valid && c->par_buf == d_buf && c->par_len == len) return c->d_blkpar;
     if (!grow(c, c->d_ws_par, sjmi::stage1_workspace_bytes(len, stage1_steps(c, len)), "hipMalloc(ws_par)")) return nullptr;
     sjmi::Stage1Extras ex;
     ex.blkpar = parity_out(c, d_buf, len);
     if (!ex.blkpar) return nullptr;
-    c->par_valid = false;  // (until the launch is queued)
+    c->par_valid = false;
     if (fail(c, "parity launch", parity_launch(c, (const uint8_t*)d_buf, len, st, ex))) return nullptr;
-    c->par_valid = true;
     return c->d_blkpar;
 }
 

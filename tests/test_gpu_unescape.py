@@ -94,10 +94,10 @@ def test_first_error_is_the_lowest_position(ctx):
 
 
 def test_window_boundaries_of_the_cooperative_path(ctx):
-    """The wave-cooperative parser walks a string in windows of 64 bytes (256 per memory round trip): every kind of
-    escape, backslash runs, surrogate pairs and every error placed so that it straddles those boundaries; also the
-    paths around it (closing quote followed by more than 15 bytes of whitespace, rows spanning more than 2 KiB,
-    documents shorter than the 16-byte windows)."""
+    """The string pass gives each lane a 64-byte block and each wave a granule of 64 blocks (4 KiB): every kind of escape,
+    backslash runs, surrogate pairs and every error placed so that they straddle the block edges at 64 to 512 bytes; also
+    closing quotes followed by long whitespace runs, long strings between structurals, and documents shorter than the
+    16-byte halo in front of a block.  Granule edges are the business of tests/test_gpu_string_granules.py."""
     pieces = ["\\n", "\\\\", "\\\"", "\\u00e9", "\\u20AC", "\\uD83D\\uDE00", "\\\\\\\\\\\\", "\\/"]
     docs = []
     for boundary in (64, 128, 256, 512):

@@ -73,8 +73,9 @@ def check_against_oracle(doc, run):
         assert sb[:len(want)] == want
 
 
-@pytest.fixture(scope="module")
-def sim():
+def sim_runners():
+    """-> (run with the kernel's shortcuts, run with the full algebra): run(doc) -> (string buffer bytes, record offsets,
+    first error as (byte position, code) or None, unclosed).  Builds tests/host_sim/libstrsim.so with g++ when it is stale."""
     so = os.path.join(SIM_DIR, "libstrsim.so")
     src = os.path.join(SIM_DIR, "str_sim.cpp")
     hdrs = [os.path.join(ROOT, "simdjson-java_amd", "csrc", h) for h in ("sj_block.h", "sj_strings.h")]
@@ -99,6 +100,11 @@ def sim():
             return sb[:total.value].tobytes(), soff[:ns.value].copy(), err, rc == 1
         return run
     return make(0), make(1)
+
+
+@pytest.fixture(scope="module")
+def sim():
+    return sim_runners()
 
 
 ESC = ['\\"', "\\\\", "\\/", "\\b", "\\f", "\\n", "\\r", "\\t", "\\u00e9", "\\uD83D\\uDE00", "\\u0000", "\\u0041", "\\u07FF",
