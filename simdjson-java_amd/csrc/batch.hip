@@ -16,6 +16,7 @@
 #include <stdint.h>
 
 #include "sj_block.h"
+#include "sj_chain.h"
 #include "sj_strings.h"
 #include "stage1.h"
 
@@ -421,10 +422,6 @@ __device__ __forceinline__ void doc_store_block(uint8_t* __restrict__ dst, const
     }
 }
 
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ uint32_t bdpp_add(uint32_t v) {
-    return v + (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, ROW_MASK, 0xF, true);
-}
 // WRITE = false: doc_status[k] and counts[k] (0 for a failing document); WRITE = true: the indexes of the passing
 // documents at index_offsets[k].  Same per-block algebra as the single-document kernel (sj_block.h); blocks are counted
 // from the document's first byte, so the loads are byte-granular.
@@ -502,8 +499,7 @@ k_doc_pass(const uint8_t* __restrict__ buf, const unsigned long long* __restrict
                 uint4* const mine = &s_rows[wvi][lane][0];
 #pragma unroll
                 for (int q = 0; q < 4; ++q) mine[q] = make_uint4(w[4 * q], w[4 * q + 1], w[4 * q + 2], w[4 * q + 3]);
-                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-                __builtin_amdgcn_wave_barrier();
+                wave_lds_fence();
                 const sj_u64 row_off = b0 * 64;  // (bytes of the document in front of the row's blocks of this trip)
                 const uint32_t row_valid = (live && len > row_off) ? (len - row_off < 1024 ? (uint32_t)(len - row_off) : 1024u) : 0u;
                 uint8_t* const row_dst = copy + s + row_off;
@@ -519,8 +515,7 @@ k_doc_pass(const uint8_t* __restrict__ buf, const unsigned long long* __restrict
                         doc_store_block(row_dst + 16u * c2, wq, row_valid - 16u * c2);
                     }
                 }
-                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-                __builtin_amdgcn_wave_barrier();
+                wave_lds_fence();
             }
             sj_transpose_butterfly(w, p);
             sj_mask_tail(p, rem < 64 ? (uint32_t)rem : 64u);
@@ -537,11 +532,7 @@ k_doc_pass(const uint8_t* __restrict__ buf, const unsigned long long* __restrict
             if (lp ? bm.ue1 : bm.ue0) err |= SJMI_ST_UNESCAPED;            // :252
             if (bm.utf8) err |= SJMI_ST_UTF8;
             const uint32_t c = (uint32_t)__popcll(m);
-            uint32_t incl = c;  // inclusive scan inside the row of 16 lanes
-            incl = bdpp_add<0x111, 0xF>(incl);
-            incl = bdpp_add<0x112, 0xF>(incl);
-            incl = bdpp_add<0x114, 0xF>(incl);
-            incl = bdpp_add<0x118, 0xF>(incl);
+            const uint32_t incl = row_incl_add(c);
             if (WRITE) {
                 sj_u64 pos = base + cnt + (incl - c);
                 const uint32_t bstart = (uint32_t)start;
@@ -584,27 +575,6 @@ k_doc_pass(const uint8_t* __restrict__ buf, const unsigned long long* __restrict
 // ---- index_offsets = exclusive scan of counts: chunk sums, scan of the chunk sums (one workgroup), chunk scans ----
 constexpr int SCAN_CHUNK = 16384;  // documents per workgroup of 1024 lanes
 
-__device__ __forceinline__ unsigned long long block_excl_scan_1024(unsigned long long v, unsigned long long* s_wave,
-                                                                    unsigned long long* total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    unsigned long long x = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const unsigned long long t = __shfl_up(x, d);
-        if (lane >= d) x += t;
-    }
-    if (lane == 63) s_wave[wave] = x;
-    __syncthreads();
-    unsigned long long off = 0, all = 0;
-    for (int w = 0; w < 16; ++w) {
-        if (w < wave) off += s_wave[w];
-        all += s_wave[w];
-    }
-    __syncthreads();
-    *total = all;
-    return off + x - v;
-}
-
 __global__ void __launch_bounds__(1024)
 k_doc_chunk_sums(const uint32_t* __restrict__ counts, const uint32_t* __restrict__ doc_status, uint64_t n_docs,
                  unsigned long long* __restrict__ chunk_sums, uint32_t* __restrict__ status_or, const uint32_t* __restrict__ skip) {
@@ -644,15 +614,7 @@ k_doc_scan(unsigned long long* __restrict__ chunk_sums, uint64_t nchunks, const 
            Stage1Result* res, const uint32_t* __restrict__ skip) {
     if (skip && *skip) return;
     __shared__ unsigned long long s_wave[16];
-    unsigned long long carry = 0;
-    for (uint64_t b = 0; b < nchunks; b += 1024) {
-        const uint64_t i = b + threadIdx.x;
-        const unsigned long long v = i < nchunks ? chunk_sums[i] : 0ull;
-        unsigned long long total;
-        const unsigned long long ex = block_excl_scan_1024(v, s_wave, &total);
-        if (i < nchunks) chunk_sums[i] = carry + ex;
-        carry += total;
-    }
+    const unsigned long long carry = block_scan_in_place<16>(chunk_sums, nchunks, s_wave);
     if (threadIdx.x == 0) {
         index_offsets[n_docs] = carry;
         res->count = carry;
@@ -674,7 +636,7 @@ k_doc_offsets(const uint32_t* __restrict__ counts, uint64_t n_docs, const unsign
         const uint64_t i = base + (uint64_t)j * 1024 + threadIdx.x;
         const unsigned long long v = i < n_docs ? counts[i] : 0ull;
         unsigned long long total;
-        const unsigned long long ex = block_excl_scan_1024(v, s_wave, &total);
+        const unsigned long long ex = block_excl_scan<16>(v, s_wave, &total);
         if (i < n_docs) index_offsets[i] = carry + ex;
         carry += total;
     }

@@ -102,7 +102,7 @@ struct Stage1Single {
     uint32_t* walk_result = nullptr;   // sizeof(WalkResult) bytes
     uint32_t* slow_header = nullptr;   // 64 bytes
 };
-// optional work folded into the kernel (device-resident path): see zero_next_workspace / scanner_wave in stage1.hip
+// optional work folded into the kernel (device-resident path): see zero_next_workspace / Stage1Chain::finish in stage1.hip
 struct Stage1Extras {
     bool workspace_is_zero = false;  // skip the workspace memset (a previous launch zeroed this workspace)
     void* zero_next = nullptr;       // workspace the NEXT launch will use: zeroed by this one (16-byte aligned)

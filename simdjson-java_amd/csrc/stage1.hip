@@ -38,6 +38,7 @@
 
 #include "sj_block.h"
 #include "sj_block32.h"
+#include "sj_chain.h"
 #include "stage1.h"
 
 namespace sjmi {
@@ -105,26 +106,6 @@ __global__ void k_transpose_selftest(const uint32_t* __restrict__ words, uint32_
     if (bad) atomicAdd(mismatches, bad);
 }
 
-// ---------------------------------------------------------------------------------------------
-// wave helpers (wave = 64 lanes)
-// ---------------------------------------------------------------------------------------------
-// Inclusive + scan over the 64 lanes with DPP (no LDS traffic): Kogge-Stone inside each row of 16 lanes
-// (row_shr 1/2/4/8, out-of-row reads give 0), then the row totals are carried across with row_bcast:15 / :31.
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ uint32_t dpp_add(uint32_t v) {
-    return v + (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, ROW_MASK, 0xF, true);
-}
-__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v, int lane) {
-    (void)lane;
-    v = dpp_add<0x111, 0xF>(v);  // row_shr:1
-    v = dpp_add<0x112, 0xF>(v);  // row_shr:2
-    v = dpp_add<0x114, 0xF>(v);  // row_shr:4
-    v = dpp_add<0x118, 0xF>(v);  // row_shr:8
-    v = dpp_add<0x142, 0xA>(v);  // row_bcast:15 -> rows 1 and 3
-    v = dpp_add<0x143, 0xC>(v);  // row_bcast:31 -> rows 2 and 3
-    return v;
-}
-
 __device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
@@ -132,35 +113,21 @@ __device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// chain granules (u64; one AGGREGATE and one PREFIX array entry per granule of input, zeroed by hipMemsetAsync
+// chain granules (sj_chain.h; one AGGREGATE and one PREFIX array entry per granule of input, zeroed by hipMemsetAsync
 // before every launch)
-//   bits 63..62 : 0 = nothing yet, 1 = AGGREGATE, 2 = INCLUSIVE PREFIX
 //   AGGREGATE   : [19:0] structurals if the granule is entered with parity 0, [39:20] with parity 1,
 //                 [40] quote parity of the granule, [41] UTF-8 error in the granule, [42] / [43] unescaped control
 //                 character inside a string if the granule is entered with parity 0 / 1, [44] a shard's left halo was too
 //                 short to resolve a backslash run
 //   PREFIX      : [39:0] structurals in granules 0..t, [40] in-string parity after granule t
-// A granule is one naturally aligned 8-byte relaxed agent-scope store/load: the data is the flag
-// (cdna_hip_programming.md Guideline 16, form R2), so no fences are needed.
+// A tripped spin bound reports SJMI_ST_INTERNAL, and the host re-runs the launch in SAFE mode.
 // ---------------------------------------------------------------------------------------------
-constexpr sj_u64 TS_AGG = 1ull << 62, TS_PFX = 2ull << 62;
-// bounded spins: ~2^19 polls of >= 100 cycles (s_sleep 1 + an uncached load) = tens of milliseconds; a healthy chain needs
-// a handful of polls, a launch whose grid is not resident trips this, reports SJMI_ST_INTERNAL and is re-run in SAFE mode
-constexpr uint32_t SPIN_LIMIT = 1u << 19;
-
-__device__ __forceinline__ void ts_store(sj_u64* p, sj_u64 v) {
-    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ sj_u64 ts_load(const sj_u64* p) {
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
 __device__ __forceinline__ void publish_aggregate(sj_u64* tile_state, uint32_t tile, uint32_t T0, uint32_t T1,
                                                   uint32_t tpar, uint32_t errbits = 0) {
-    ts_store(&tile_state[tile], TS_AGG | ((sj_u64)errbits << 41) | ((sj_u64)tpar << 40) | ((sj_u64)T1 << 20) | (sj_u64)T0);
+    granule_store(&tile_state[tile], CHAIN_AGG | ((sj_u64)errbits << 41) | ((sj_u64)tpar << 40) | ((sj_u64)T1 << 20) | (sj_u64)T0);
 }
 __device__ __forceinline__ void publish_prefix(sj_u64* tile_state, uint32_t tile, uint32_t par_after, sj_u64 cnt_after) {
-    ts_store(&tile_state[tile], TS_PFX | ((sj_u64)par_after << 40) | cnt_after);
+    granule_store(&tile_state[tile], CHAIN_PFX | ((sj_u64)par_after << 40) | cnt_after);
 }
 
 
@@ -183,7 +150,7 @@ __device__ __forceinline__ void tile_lookback(const sj_u64* tile_state, uint32_t
         int J = 64;  // first lane that holds a PREFIX
         for (uint32_t spins = 0;; ++spins) {
 #pragma unroll
-            for (int j = 0; j < K; ++j) v[j] = (hi - j >= 0) ? ts_load(&tile_state[hi - j]) : TS_PFX;  // "before tile 0": prefix (0, 0)
+            for (int j = 0; j < K; ++j) v[j] = (hi - j >= 0) ? granule_load(&tile_state[hi - j]) : CHAIN_PFX;  // "before tile 0": prefix (0, 0)
             jp = K;
 #pragma unroll
             for (int j = K - 1; j >= 0; --j)
@@ -196,7 +163,7 @@ __device__ __forceinline__ void tile_lookback(const sj_u64* tile_state, uint32_t
             J = pm ? __builtin_ctzll(pm) : 64;
             const sj_u64 need = J >= 63 ? ~0ull : ((2ull << J) - 1ull);  // lanes 0..J
             if ((__ballot(ready) & need) == need) break;
-            if (spins > SPIN_LIMIT) {  // never expected: a predecessor tile did not publish
+            if (spins > CHAIN_SPIN_LIMIT) {  // never expected: a predecessor tile did not publish
                 if (lane == 0)
                     __hip_atomic_fetch_or(&res->status, SJMI_ST_INTERNAL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 break;
@@ -246,81 +213,6 @@ __device__ __forceinline__ void tile_lookback(const sj_u64* tile_state, uint32_t
     *cnt_in = C;
 }
 
-// The SCANNER: workgroup 0 does nothing but turn the workers' per-granule AGGREGATEs, in order, into per-granule
-// inclusive PREFIXes in a second array.  Every granule crosses the chip exactly twice (aggregate: worker ->
-// scanner, prefix: scanner -> worker).  Measured alternative: every worker polling a 64..256-granule window of
-// uncached granules itself, whose traffic and round trips (one per window of distance to the nearest prefix)
-// were the bottleneck.  The workers need a granule's prefix one whole classification after they published its
-// aggregate, so the scanner's latency (load + store visibility, ~3 us) is off the critical path; its THROUGHPUT
-// is not (200+ granules per us): a single wave managed ~250/us, so the four waves take the windows of 256 granules
-// round-robin, do everything that does not depend on the running state (polling, folding 4 granules per lane,
-// cross-lane scans for both entry parities) in parallel, and pass the running (parity, count) from window to
-// window through LDS, which is the only serial step.
-constexpr int SCAN_K = 4;  // granules per lane
-struct ScanHandoff {
-    uint32_t seq;  // window whose entry state is in P / C; 0xFFFFFFFF = a scanner wave gave up
-    uint32_t P;    // in-string parity after the windows scanned so far
-    uint32_t err;  // SJMI_ST_UTF8 / SJMI_ST_UNESCAPED found in the granules scanned so far
-    sj_u64 C;      // structurals in them
-};
-
-__device__ __forceinline__ void scanner_load(sj_u64 v[SCAN_K], const sj_u64* agg, sj_u64 first, uint32_t n) {
-#pragma unroll
-    for (int j = 0; j < SCAN_K; ++j) v[j] = first + j < n ? ts_load(&agg[first + j]) : TS_AGG;  // past the end: empty aggregates
-}
-__device__ __forceinline__ bool scanner_ready(const sj_u64 v[SCAN_K]) {
-    bool ready = true;
-#pragma unroll
-    for (int j = 0; j < SCAN_K; ++j) ready &= v[j] != 0;
-    return ready;
-}
-// the lane's granules as one function {entered outside, inside a string} -> (count, parity)
-__device__ __forceinline__ void scanner_fold(const sj_u64 v[SCAN_K], uint32_t* c0, uint32_t* c1, uint32_t* par) {
-    uint32_t a = 0, b = 0, lp = 0;
-#pragma unroll
-    for (int j = 0; j < SCAN_K; ++j) {
-        const uint32_t a0 = (uint32_t)v[j] & 0xFFFFFu, a1 = (uint32_t)(v[j] >> 20) & 0xFFFFFu;
-        const uint32_t n0 = a + (lp ? a1 : a0), n1 = b + (lp ? a0 : a1);
-        a = n0;
-        b = n1;
-        lp ^= (uint32_t)(v[j] >> 40) & 1u;
-    }
-    *c0 = a;
-    *c1 = b;
-    *par = lp;
-}
-// SJMI_ST_* bits of the lane's granules, given the parity entering the first one (the aggregates carry "UTF-8 error" and
-// "unescaped control character if entered outside / inside a string": the status of a launch is complete as soon as
-// the scanner has seen every aggregate, no worker has to be waited for)
-__device__ __forceinline__ uint32_t scanner_errors(const sj_u64 v[SCAN_K], uint32_t q) {
-    uint32_t e = 0;
-#pragma unroll
-    for (int j = 0; j < SCAN_K; ++j) {
-        if ((v[j] >> 41) & 1u) e |= SJMI_ST_UTF8;
-        if ((v[j] >> 44) & 1u) e |= SJMI_ST_HALO;
-        if ((v[j] >> (42 + q)) & 1u) e |= SJMI_ST_UNESCAPED;
-        q ^= (uint32_t)(v[j] >> 40) & 1u;
-    }
-    return e;
-}
-__device__ __forceinline__ void scanner_report(ScanHandoff* hand, uint32_t e) {
-    if (__ballot(e != 0)) {  // rare
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) e |= __shfl_xor(e, d);
-        if ((threadIdx.x & 63) == 0) __hip_atomic_fetch_or(&hand->err, e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    }
-}
-// prefixes of the lane's granules, given the parity entering the first one and the structurals before it
-__device__ __forceinline__ void scanner_publish(const sj_u64 v[SCAN_K], sj_u64* pfx, sj_u64 first, uint32_t n, uint32_t q,
-                                                sj_u64 run) {
-#pragma unroll
-    for (int j = 0; j < SCAN_K; ++j) {
-        run += q ? (uint32_t)(v[j] >> 20) & 0xFFFFFu : (uint32_t)v[j] & 0xFFFFFu;
-        q ^= (uint32_t)(v[j] >> 40) & 1u;
-        if (first + j < n) publish_prefix(pfx, (uint32_t)(first + j), q, run);
-    }
-}
-
 // (one lane, behind the result record: see Stage1Single)
 __device__ __forceinline__ void single_doc_setup(const Stage1Single& ss, sj_u64 len, sj_u64 count, uint32_t status) {
     if (!ss.index_offsets) return;
@@ -335,134 +227,135 @@ __device__ __forceinline__ void single_doc_setup(const Stage1Single& ss, sj_u64 
     for (int i = 0; i < 16; ++i) ss.slow_header[i] = 0;
 }
 
-__device__ __forceinline__ void scanner_wave(ScanHandoff* hand, int wave, const sj_u64* agg, sj_u64* pfx, uint32_t n,
-                                             int lane, uint32_t* out, sj_u64 out_cap, Stage1Result* res,
-                                             Stage1Result* result_out, const Stage1Single& ss, sj_u64 len) {
-    __builtin_amdgcn_s_setprio(3);  // everybody waits for these four waves
-    constexpr uint32_t WIN = 64 * SCAN_K;
-    const sj_u64 lt_mask = (1ull << lane) - 1ull;
-    for (sj_u64 win = (sj_u64)wave; win * WIN < n; win += 4) {
-        const sj_u64 first = win * WIN + (sj_u64)lane * SCAN_K;  // this lane's granules
-        sj_u64 v[SCAN_K];
-        uint32_t P2;
-        sj_u64 C2;
-        // poll the window until it is complete (then most of the work can be done before the running state arrives) or
-        // until the running state has arrived (then the ready part cannot wait for the rest)
-        bool full;
-        for (;;) {
-            scanner_load(v, agg, first, n);
-            full = __ballot(scanner_ready(v)) == ~0ull;
-            if (full) break;
-            const uint32_t seq = __hip_atomic_load(&hand->seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            if (seq == (uint32_t)win || seq == 0xFFFFFFFFu) break;
-            __builtin_amdgcn_s_sleep(1);
-        }
-        if (full) {
-            // ---- the scanner is behind the workers: the window is complete at the first look.  Everything that does
-            //      not depend on the running state is done before waiting for it ----
-            uint32_t c0, c1, lp;
-            scanner_fold(v, &c0, &c1, &lp);
-            const sj_u64 pb = __ballot(lp);
-            const uint32_t qrel = (uint32_t)__popcll(pb & lt_mask) & 1u;      // parity of the lanes in front
-            const uint32_t mine0 = qrel ? c1 : c0, mine1 = qrel ? c0 : c1;  // window entered outside / inside
-            const uint32_t incl0 = wave_incl_scan(mine0, lane), incl1 = wave_incl_scan(mine1, lane);
-            const uint32_t tot0 = (uint32_t)__builtin_amdgcn_readlane((int)incl0, 63);
-            const uint32_t tot1 = (uint32_t)__builtin_amdgcn_readlane((int)incl1, 63);
-            // the serial step: take the running state from the previous window's wave, pass it on
-            uint32_t seq;
-            do {
-                seq = __hip_atomic_load(&hand->seq, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP);
-            } while (seq != (uint32_t)win && seq != 0xFFFFFFFFu);
-            if (seq == 0xFFFFFFFFu) return;
-            const uint32_t P = hand->P;
-            const sj_u64 C = hand->C;
-            P2 = P ^ ((uint32_t)__popcll(pb) & 1u);
-            C2 = C + (P ? tot1 : tot0);
-            scanner_report(hand, scanner_errors(v, P ^ qrel));
-            if (lane == 0) {
-                hand->P = P2;
-                hand->C = C2;
-                __hip_atomic_store(&hand->seq, (uint32_t)win + 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-            }
-            scanner_publish(v, pfx, first, n, P ^ qrel, C + (P ? incl1 - mine1 : incl0 - mine0));
-        } else {
-            // ---- the scanner is at the workers' frontier: take the running state first, then publish whatever
-            //      becomes ready, lane by lane in order (a worker may be waiting for a prefix in the front part of this
-            //      window while the back part has not even been handed out) ----
-            uint32_t seq;
-            do {
-                seq = __hip_atomic_load(&hand->seq, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP);
-            } while (seq != (uint32_t)win && seq != 0xFFFFFFFFu);
-            if (seq == 0xFFFFFFFFu) return;
-            uint32_t P = hand->P;
-            sj_u64 C = hand->C;
-            int done = 0;  // lanes already turned into prefixes
-            for (uint32_t spins = 0;; ++spins) {
-                const sj_u64 rb = __ballot(scanner_ready(v));
-                const int nr = ~rb ? __builtin_ctzll(~rb) : 64;  // lanes ready in a row from lane 0
-                if (nr > done) {
-                    const bool act = lane >= done && lane < nr;
-                    uint32_t c0, c1, lp;
-                    scanner_fold(v, &c0, &c1, &lp);
-                    const sj_u64 pb = __ballot(act && lp);
-                    const uint32_t q = P ^ ((uint32_t)__popcll(pb & lt_mask) & 1u);
-                    const uint32_t mine = act ? (q ? c1 : c0) : 0u;
-                    const uint32_t incl = wave_incl_scan(mine, lane);
-                    if (act) scanner_publish(v, pfx, first, n, q, C + (incl - mine));
-                    scanner_report(hand, act ? scanner_errors(v, q) : 0u);
-                    C += (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
-                    P ^= (uint32_t)__popcll(pb) & 1u;
-                    done = nr;
-                    spins = 0;
-                }
-                if (done == 64) break;
-                if (spins > SPIN_LIMIT) {  // never expected: a worker did not publish
-                    if (lane == 0) {
-                        __hip_atomic_fetch_or(&res->status, SJMI_ST_INTERNAL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        __hip_atomic_store(&hand->seq, 0xFFFFFFFFu, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                        if (result_out) {
-                            result_out->count = 0;
-                            result_out->status = SJMI_ST_INTERNAL;
-                            result_out->reserved = 0;
-                            single_doc_setup(ss, len, 0, SJMI_ST_INTERNAL);
-                        }
-                    }
-                    return;
-                }
-                __builtin_amdgcn_s_sleep(1);
-                sj_u64 nv[SCAN_K];
-                scanner_load(nv, agg, first, n);
+// The SCANNER (chain_scanner_wave, sj_chain.h) is workgroup 0; its four waves take windows of 64 * SCAN_K = 256 granules.  The
+// running state is (in-string parity, structurals) behind the windows scanned so far.  A granule's aggregate counts its
+// structurals for both entry parities, so a complete window is folded and scanned for both before the state arrives.
+// (ChainState: w = the in-string parity, c = the structurals.)  The aggregates' error bits go into one LDS word, and the last
+// window's wave turns them into the launch's status.
+constexpr int SCAN_K = 4;  // granules per lane
+struct Stage1Chain {
+    static constexpr int K = SCAN_K;
+    uint32_t* err;  // (LDS) SJMI_ST_UTF8 / SJMI_ST_UNESCAPED / SJMI_ST_HALO found in the granules scanned so far
+    Stage1Result* res;
+    uint32_t* out;
+    sj_u64 out_cap;
+    Stage1Result* result_out;
+    const Stage1Single& ss;
+    sj_u64 len;
+
+    // the lane's granules as one function {entered outside, inside a string} -> (count, parity)
+    __device__ static void fold(const sj_u64 (&v)[K], uint32_t* c0, uint32_t* c1, uint32_t* par) {
+        uint32_t a = 0, b = 0, lp = 0;
 #pragma unroll
-                for (int j = 0; j < SCAN_K; ++j)
-                    if (lane >= done) v[j] = nv[j];  // (finished lanes keep what their prefixes were computed from)
-            }
-            P2 = P;
-            C2 = C;
-            if (lane == 0) {
-                hand->P = P2;
-                hand->C = C2;
-                __hip_atomic_store(&hand->seq, (uint32_t)win + 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-            }
+        for (int j = 0; j < K; ++j) {
+            const uint32_t a0 = (uint32_t)v[j] & 0xFFFFFu, a1 = (uint32_t)(v[j] >> 20) & 0xFFFFFu;
+            const uint32_t n0 = a + (lp ? a1 : a0), n1 = b + (lp ? a0 : a1);
+            a = n0;
+            b = n1;
+            lp ^= (uint32_t)(v[j] >> 40) & 1u;
         }
-        if ((win + 1) * WIN >= n && lane == 0) {
-            // that was the last window: count, sentinel, unclosed string -- and the complete status of the launch
-            // (every window's errors were reported before its wave passed the running state on)
-            res->count = C2;
-            uint32_t e = __hip_atomic_load(&hand->err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            if (P2) e |= SJMI_ST_UNCLOSED;   // StructuralIndexer.java:297-299
-            if (C2 < out_cap) out[C2] = 0;   // BitIndexes.finish :82-96
-            else e |= SJMI_ST_CAPACITY;      // (== some granule did not fit: they are written in order)
-            if (e) __hip_atomic_fetch_or(&res->status, e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (result_out) {  // device-resident path: the caller's record, without a copy queued behind the kernel
-                const uint32_t st_all = e | __hip_atomic_load(&res->status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                result_out->count = C2;
-                result_out->status = st_all;
-                result_out->reserved = 0;
-                single_doc_setup(ss, len, C2, st_all);
-            }
+        *c0 = a;
+        *c1 = b;
+        *par = lp;
+    }
+    // SJMI_ST_* bits of the lane's granules, given the parity entering the first one (the aggregates carry "UTF-8 error" and
+    // "unescaped control character if entered outside / inside a string": the status of a launch is complete as soon as
+    // the scanner has seen every aggregate, no worker has to be waited for)
+    __device__ static uint32_t errors(const sj_u64 (&v)[K], uint32_t q) {
+        uint32_t e = 0;
+#pragma unroll
+        for (int j = 0; j < K; ++j) {
+            if ((v[j] >> 41) & 1u) e |= SJMI_ST_UTF8;
+            if ((v[j] >> 44) & 1u) e |= SJMI_ST_HALO;
+            if ((v[j] >> (42 + q)) & 1u) e |= SJMI_ST_UNESCAPED;
+            q ^= (uint32_t)(v[j] >> 40) & 1u;
+        }
+        return e;
+    }
+    __device__ void report(uint32_t e) const {
+        if (__ballot(e != 0)) {  // rare
+#pragma unroll
+            for (int d = 32; d >= 1; d >>= 1) e |= __shfl_xor(e, d);
+            if ((threadIdx.x & 63) == 0) __hip_atomic_fetch_or(err, e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         }
     }
-}
+    // prefixes of the lane's granules, given the parity entering the first one and the structurals before it
+    __device__ static void publish(const sj_u64 (&v)[K], sj_u64* pfx, sj_u64 first, uint32_t n, uint32_t q, sj_u64 run) {
+#pragma unroll
+        for (int j = 0; j < K; ++j) {
+            run += q ? (uint32_t)(v[j] >> 20) & 0xFFFFFu : (uint32_t)v[j] & 0xFFFFFu;
+            q ^= (uint32_t)(v[j] >> 40) & 1u;
+            if (first + j < n) publish_prefix(pfx, (uint32_t)(first + j), q, run);
+        }
+    }
+
+    struct Window {
+        sj_u64 pb;                   // the lanes' parities
+        uint32_t qrel;               // parity of the lanes in front
+        uint32_t mine0, mine1;       // the lane's structurals if the window is entered outside / inside a string
+        uint32_t incl0, incl1;       // ... their inclusive scans
+        uint32_t tot0, tot1;         // ... and totals
+    };
+    __device__ Window window(const sj_u64 (&v)[K], int lane) const {
+        Window w;
+        uint32_t c0, c1, lp;
+        fold(v, &c0, &c1, &lp);
+        w.pb = __ballot(lp);
+        w.qrel = (uint32_t)__popcll(w.pb & ((1ull << lane) - 1ull)) & 1u;
+        w.mine0 = w.qrel ? c1 : c0;
+        w.mine1 = w.qrel ? c0 : c1;
+        w.incl0 = wave_incl_add(w.mine0);
+        w.incl1 = wave_incl_add(w.mine1);
+        w.tot0 = (uint32_t)__builtin_amdgcn_readlane((int)w.incl0, 63);
+        w.tot1 = (uint32_t)__builtin_amdgcn_readlane((int)w.incl1, 63);
+        return w;
+    }
+    __device__ ChainState advance(ChainState in, const sj_u64 (&v)[K], const Window& w) const {
+        report(errors(v, in.w ^ w.qrel));
+        return {in.w ^ ((uint32_t)__popcll(w.pb) & 1u), in.c + (in.w ? w.tot1 : w.tot0)};
+    }
+    __device__ void publish_window(const sj_u64 (&v)[K], sj_u64* pfx, sj_u64 first, uint32_t n, ChainState in, const Window& w) const {
+        publish(v, pfx, first, n, in.w ^ w.qrel, in.c + (in.w ? w.incl1 - w.mine1 : w.incl0 - w.mine0));
+    }
+    __device__ ChainState publish_ready(const sj_u64 (&v)[K], sj_u64* pfx, sj_u64 first, uint32_t n, int lane, bool act,
+                                        ChainState s) const {
+        uint32_t c0, c1, lp;
+        fold(v, &c0, &c1, &lp);
+        const sj_u64 pb = __ballot(act && lp);
+        const uint32_t q = s.w ^ ((uint32_t)__popcll(pb & ((1ull << lane) - 1ull)) & 1u);
+        const uint32_t mine = act ? (q ? c1 : c0) : 0u;
+        const uint32_t incl = wave_incl_add(mine);
+        if (act) publish(v, pfx, first, n, q, s.c + (incl - mine));
+        report(act ? errors(v, q) : 0u);
+        return {s.w ^ ((uint32_t)__popcll(pb) & 1u), s.c + (uint32_t)__builtin_amdgcn_readlane((int)incl, 63)};
+    }
+    __device__ void give_up() const {
+        __hip_atomic_fetch_or(&res->status, SJMI_ST_INTERNAL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (result_out) {
+            result_out->count = 0;
+            result_out->status = SJMI_ST_INTERNAL;
+            result_out->reserved = 0;
+            single_doc_setup(ss, len, 0, SJMI_ST_INTERNAL);
+        }
+    }
+    // count, sentinel, unclosed string -- and the complete status of the launch (every window's errors were reported before
+    // its wave passed the running state on)
+    __device__ void finish(ChainState s) const {
+        res->count = s.c;
+        uint32_t e = __hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        if (s.w) e |= SJMI_ST_UNCLOSED;   // StructuralIndexer.java:297-299
+        if (s.c < out_cap) out[s.c] = 0;  // BitIndexes.finish :82-96
+        else e |= SJMI_ST_CAPACITY;       // (== some granule did not fit: they are written in order)
+        if (e) __hip_atomic_fetch_or(&res->status, e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (result_out) {  // device-resident path: the caller's record, without a copy queued behind the kernel
+            const uint32_t st_all = e | __hip_atomic_load(&res->status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            result_out->count = s.c;
+            result_out->status = st_all;
+            result_out->reserved = 0;
+            single_doc_setup(ss, len, s.c, st_all);
+        }
+    }
+};
 
 // ---------------------------------------------------------------------------------------------
 // the stage-1 kernel: PERSISTENT, WAVE-AUTONOMOUS workers, software-pipelined across granules.
@@ -496,11 +389,6 @@ __device__ __forceinline__ void scanner_wave(ScanHandoff* hand, int wave, const 
 // per tile and look-back windows of 64..256 granules (uncached polling traffic), 16 KiB workgroup tiles
 // (ticket-bound), wave-autonomous tiles with per-wave look-back (chain rate ~100 tiles/us).
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ void wave_lds_fence() {
-    // LDS accesses of one wave execute in order; this only stops the compiler from reordering them
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
 
 // The 64 bytes of one lane's block plus the 8 bytes before it (carries), as loaded from HBM.
 struct StepData {
@@ -579,15 +467,14 @@ stage1_body(const uint8_t* __restrict__ buf, sj_u64 len, uint32_t* __restrict__ 
     if (skip && *skip) return;  // (fused batch pipeline: this pass is not needed; uniform for the whole launch)
     static_assert(S <= 4, "meta packs 14-bit offsets: at most 4 steps per granule");
     __shared__ WaveShared<S, LDSW> sh[4];
-    __shared__ ScanHandoff hand;
+    __shared__ ChainHandoff hand;
+    __shared__ uint32_t scan_err;
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     constexpr bool safe = SAFE;  // a separate instantiation: the look-back code costs the fast kernel 8+ VGPRs
     sj_u64* const agg = gstate;         // AGGREGATE per granule (SAFE mode: overwritten by its PREFIX)
     sj_u64* const pfx = gstate + ngran;  // the scanner's prefixes (FAST mode)
-    // (xcc, se, sh, cu) of the CU this workgroup runs on, never 0
-    const uint32_t my_cu = (((uint32_t)__builtin_amdgcn_s_getreg((31 << 11) | 4) >> 8) & 0xFFu) |
-                           (((uint32_t)__builtin_amdgcn_s_getreg((31 << 11) | 20) & 0xFu) << 8) | 0x80000000u;
+    const uint32_t my_cu = cu_id();
     uint32_t* const scanner_cu = reinterpret_cast<uint32_t*>(res) + WS_SCANNER_CU_WORD;
     if (!safe && blockIdx.x == 0) {
         if (threadIdx.x == 0) __hip_atomic_store(scanner_cu, my_cu, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -595,12 +482,15 @@ stage1_body(const uint8_t* __restrict__ buf, sj_u64 len, uint32_t* __restrict__ 
             __hip_atomic_fetch_or(&res->status, SJMI_ST_INTERNAL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (threadIdx.x == 0) {
             hand.seq = 0;
-            hand.P = (dbg & FLAG_ENTRY_PARITY) ? 1u : 0u;  // (a shard of a longer document may start inside a string)
-            hand.err = 0;
-            hand.C = 0;
+            hand.w = (dbg & FLAG_ENTRY_PARITY) ? 1u : 0u;  // (a shard of a longer document may start inside a string)
+            hand.c = 0;
+            scan_err = 0;
         }
         __syncthreads();
-        if (!(dbg & DBG_NO_LOOKBACK)) scanner_wave(&hand, wave, agg, pfx, ngran, lane, out, out_cap, res, result_out, ss, len);
+        if (!(dbg & DBG_NO_LOOKBACK)) {
+            const Stage1Chain pol = {&scan_err, res, out, out_cap, result_out, ss, len};
+            chain_scanner_wave(&hand, wave, lane, agg, pfx, ngran, pol);
+        }
         return;
     }
     const uint32_t nworkers = (gridDim.x - (safe ? 0u : 1u)) * 4u;
@@ -640,11 +530,8 @@ stage1_body(const uint8_t* __restrict__ buf, sj_u64 len, uint32_t* __restrict__ 
     const bool first_by_ticket = safe || (dbg & FLAG_ALL_TICKETS) != 0;
     uint32_t cur;
     const uint32_t ticket_base = first_by_ticket ? 0u : (nworkers - cls + NC - 1u) / NC;
-    if (first_by_ticket) {
-        uint32_t t = 0;
-        if (lane == 0) t = __hip_atomic_fetch_add(my_ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        cur = (uint32_t)__builtin_amdgcn_readfirstlane((int)t) * NC + cls;
-    } else cur = worker;
+    if (first_by_ticket) cur = take_ticket(my_ticket) * NC + cls;
+    else cur = worker;
     uint32_t prev = NO_TILE, prev_par = 0, prev_c0 = 0, prev_c1 = 0;  // the parked granule and its aggregate
     uint32_t err = 0;
     StepData d;  // the step being loaded / classified (single buffer: re-used as soon as it has been transposed)
@@ -687,7 +574,7 @@ stage1_body(const uint8_t* __restrict__ buf, sj_u64 len, uint32_t* __restrict__ 
                     // (a ticket held through a whole slow iteration delays every granule behind it), early enough to
                     // hide the round trips
                     if (lane == 0 && retire != 0) tk = __hip_atomic_fetch_add(my_ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    if (prev != NO_TILE && prev != 0) pf = ts_load(&pfx[prev - 1]);
+                    if (prev != NO_TILE && prev != 0) pf = granule_load(&pfx[prev - 1]);
                 }
                 asm volatile("" ::: "memory");
                 pot[s] = 0;
@@ -757,7 +644,7 @@ stage1_body(const uint8_t* __restrict__ buf, sj_u64 len, uint32_t* __restrict__ 
                 wpar ^= (uint32_t)__popcll(bal) & 1u;
                 m[s] = lp ? (pot[s] & sm[s]) : (pot[s] & ~sm[s]);  // StructuralIndexer.java:251
                 const uint32_t c0 = (uint32_t)__popcll(m[s]), cp = (uint32_t)__popcll(pot[s]);
-                const uint32_t packed = wave_incl_scan(c0 | (cp << 16), lane);  // both <= 4096 per step: no carry
+                const uint32_t packed = wave_incl_add(c0 | (cp << 16));  // both <= 4096 per step: no carry
                 const uint32_t tot = (uint32_t)__builtin_amdgcn_readlane((int)packed, 63);
                 const uint32_t ex0 = W0 + (packed & 0xFFFFu) - c0;  // granule-relative exclusive offsets
                 const uint32_t exp_ = WP + (packed >> 16) - cp;
@@ -785,9 +672,7 @@ stage1_body(const uint8_t* __restrict__ buf, sj_u64 len, uint32_t* __restrict__ 
         uint32_t nxt = NO_TILE;
         if (have) {
             if (safe) {
-                uint32_t t = 0;
-                if (lane == 0) t = __hip_atomic_fetch_add(my_ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                nxt = (uint32_t)__builtin_amdgcn_readfirstlane((int)t);
+                nxt = take_ticket(my_ticket);
             } else {
                 nxt = retire != 0 ? ((uint32_t)__builtin_amdgcn_readfirstlane((int)tk) + ticket_base) * NC + cls : NO_TILE;
             }
@@ -805,15 +690,9 @@ stage1_body(const uint8_t* __restrict__ buf, sj_u64 len, uint32_t* __restrict__ 
                 if constexpr (safe) {
                     tile_lookback<LB_K>(agg, prev, lane, &pe, &cnt_in, res);
                 } else {
-                    for (uint32_t spins = 0; (pf >> 62) != 2; ++spins) {
-                        if (spins > SPIN_LIMIT) {  // never expected: the scanner is not running
-                            if (lane == 0)
-                                __hip_atomic_fetch_or(&res->status, SJMI_ST_INTERNAL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                            break;
-                        }
-                        if (spins) __builtin_amdgcn_s_sleep(1);
-                        pf = ts_load(&pfx[prev - 1]);
-                    }
+                    wait_prefix(&pfx[prev - 1], pf, [&] {
+                        if (lane == 0) __hip_atomic_fetch_or(&res->status, SJMI_ST_INTERNAL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    });
                     pe = (uint32_t)(pf >> 40) & 1u;
                     cnt_in = pf & ((1ull << 40) - 1ull);
                 }
@@ -947,7 +826,7 @@ stage1_body(const uint8_t* __restrict__ buf, sj_u64 len, uint32_t* __restrict__ 
                         }
                         wave_lds_fence();
                         const uint32_t hv = lane <= 32 ? hist[32 - lane] : 0u;
-                        const uint32_t incl = wave_incl_scan(hv, lane);
+                        const uint32_t incl = wave_incl_add(hv);
                         if (lane <= 32) bbase[32 - lane] = incl - hv;
                         const uint32_t nz = (uint32_t)__builtin_amdgcn_readlane((int)incl, 31);  // half masks with a bit
                         wave_lds_fence();

@@ -33,6 +33,7 @@
 
 #include "sj_strings.h"
 #include "sj_block32.h"
+#include "sj_chain.h"
 #include "stage1.h"
 
 namespace sjmi {
@@ -42,50 +43,14 @@ constexpr uint32_t STR_NONE = 0xFFFFFFFFu;
 // header costs at least one quote byte of the granule and a second one for all but one of them: <= 4100 + 2 * 2048
 constexpr int STR_TILE_BYTES = 8192 + 64;
 constexpr int STR_TILE_DW = STR_TILE_BYTES / 4;
-constexpr uint32_t STR_SPIN_LIMIT = 1u << 19;
 
-// granule states (u64, relaxed agent-scope, the data is the flag: cdna_hip_programming.md Guideline 16 form R2)
+// granule states (sj_chain.h; the open records are stored and loaded the same way)
 //   AGGREGATE  [63:62] = 1, [36] a string error in the granule, [35:20] strings opened, [19:0] bytes produced
 //   PREFIX     [63:62] = 2, [61:32] strings opened in granules 0..t, [31:0] bytes (saturating: the buffer is < 4 GiB)
 //   OPEN REC   [63] valid, [62] the granule holds the opening quote of the string that is open at its end,
 //              [23:16] first error of that string inside this granule, [15:0] granule-relative offset of its header
-constexpr sj_u64 SG_AGG = 1ull << 62, SG_PFX = 2ull << 62;
+// A tripped spin bound reports SJMI_ST_INTERNAL in wsflags[0] and flags 4.
 constexpr sj_u64 OR_VALID = 1ull << 63, OR_HAS_OPEN = 1ull << 62;
-
-__device__ __forceinline__ void sg_store(sj_u64* p, sj_u64 v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ sj_u64 sg_load(const sj_u64* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ uint32_t sdpp_add(uint32_t v) {
-    return v + (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, ROW_MASK, 0xF, true);
-}
-__device__ __forceinline__ uint32_t str_incl_scan(uint32_t v) {
-    v = sdpp_add<0x111, 0xF>(v);  // row_shr:1
-    v = sdpp_add<0x112, 0xF>(v);
-    v = sdpp_add<0x114, 0xF>(v);
-    v = sdpp_add<0x118, 0xF>(v);
-    v = sdpp_add<0x142, 0xA>(v);  // row_bcast:15
-    v = sdpp_add<0x143, 0xC>(v);  // row_bcast:31
-    return v;
-}
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ uint32_t sdpp_max(uint32_t v) {
-    const uint32_t o = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, ROW_MASK, 0xF, true);
-    return v > o ? v : o;
-}
-__device__ __forceinline__ uint32_t str_incl_max(uint32_t v) {
-    v = sdpp_max<0x111, 0xF>(v);
-    v = sdpp_max<0x112, 0xF>(v);
-    v = sdpp_max<0x114, 0xF>(v);
-    v = sdpp_max<0x118, 0xF>(v);
-    v = sdpp_max<0x142, 0xA>(v);
-    v = sdpp_max<0x143, 0xC>(v);
-    return v;
-}
-__device__ __forceinline__ void str_lds_fence() {
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
 
 struct StrArgs {
     const uint8_t* buf;
@@ -111,153 +76,89 @@ struct StrArgs {
 };
 
 // ---------------------------------------------------------------------------------------------------------------------
-// the scanner: workgroup 0 turns the workers' aggregates, in order, into inclusive prefixes (see stage1.hip's scanner for
-// why it is built like this: four waves take windows of 64 * SSCAN_K granules round-robin, everything that does not depend on
-// the running state is done before it arrives through LDS, and at the workers' frontier a wave publishes whatever
-// is ready lane by lane so that a launch with few resident workgroups cannot deadlock on a half-handed-out window)
+// the scanner (chain_scanner_wave, sj_chain.h): the first workgroup to arrive turns the workers' aggregates, in order, into
+// inclusive prefixes.  Its state is (strings opened, bytes produced) in front of a window: a plain sum.
 // ---------------------------------------------------------------------------------------------------------------------
 // (windows of 128 granules: twitter x1024 0.400 ms against 0.406 with 256, 0.75 with 512 -- the frontier window is never
 //  complete and goes lane by lane; 64: 0.60)
 #ifndef SJMI_SSCAN_K
 #define SJMI_SSCAN_K 2
 #endif
-constexpr int SSCAN_K = SJMI_SSCAN_K;
-struct StrHand {
-    uint32_t seq;  // window whose entry state is in ord / out; 0xFFFFFFFF = a scanner wave gave up
-    uint32_t ord;
-    sj_u64 out;
-};
-__device__ __forceinline__ void sscan_load(sj_u64 v[SSCAN_K], const sj_u64* agg, sj_u64 first, uint32_t n) {
-#pragma unroll
-    for (int j = 0; j < SSCAN_K; ++j) v[j] = first + j < n ? sg_load(&agg[first + j]) : SG_AGG;
-}
-__device__ __forceinline__ bool sscan_ready(const sj_u64 v[SSCAN_K]) {
-    bool r = true;
-#pragma unroll
-    for (int j = 0; j < SSCAN_K; ++j) r &= v[j] != 0;
-    return r;
-}
-__device__ __forceinline__ void sscan_fold(const sj_u64 v[SSCAN_K], uint32_t* s0, uint32_t* s1) {
-    uint32_t a = 0, b = 0;
-#pragma unroll
-    for (int j = 0; j < SSCAN_K; ++j) {
-        a += (uint32_t)v[j] & 0xFFFFFu;
-        b += (uint32_t)(v[j] >> 20) & 0xFFFFu;
-    }
-    *s0 = a;
-    *s1 = b;
-}
-__device__ __forceinline__ void sscan_publish(const sj_u64 v[SSCAN_K], sj_u64* pfx, sj_u64 first, uint32_t n, sj_u64 out, uint32_t ord) {
-#pragma unroll
-    for (int j = 0; j < SSCAN_K; ++j) {
-        out += (uint32_t)v[j] & 0xFFFFFu;
-        ord += (uint32_t)(v[j] >> 20) & 0xFFFFu;
-        if (first + j < n) {
-            const sj_u64 o32 = out > 0xFFFFFFFFull ? 0xFFFFFFFFull : out;
-            const sj_u64 r30 = ord > 0x3FFFFFFFu ? 0x3FFFFFFFu : ord;
-            sg_store(&pfx[first + j], SG_PFX | (r30 << 32) | o32);
-        }
-    }
-}
+struct StrChain {
+    static constexpr int K = SJMI_SSCAN_K;
+    const StrArgs& a;
 
-__device__ __forceinline__ void str_scanner_wave(StrHand* hand, int wave, const StrArgs& a, int lane) {
-    __builtin_amdgcn_s_setprio(3);
-    constexpr uint32_t WIN = 64 * SSCAN_K;
-    const sj_u64* agg = a.gstate;
-    sj_u64* pfx = a.gstate + a.ngran;
-    const uint32_t n = a.ngran;
-    for (sj_u64 win = (sj_u64)wave; win * WIN < n; win += 4) {
-        const sj_u64 first = win * WIN + (sj_u64)lane * SSCAN_K;
-        sj_u64 v[SSCAN_K];
-        sj_u64 out2;
-        uint32_t ord2;
-        bool full;
-        for (;;) {
-            sscan_load(v, agg, first, n);
-            full = __ballot(sscan_ready(v)) == ~0ull;
-            if (full) break;
-            const uint32_t seq = __hip_atomic_load(&hand->seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            if (seq == (uint32_t)win || seq == 0xFFFFFFFFu) break;
-            __builtin_amdgcn_s_sleep(1);
-        }
-        if (full) {
-            uint32_t s0, s1;
-            sscan_fold(v, &s0, &s1);
-            const uint32_t i0 = str_incl_scan(s0), i1 = str_incl_scan(s1);
-            const uint32_t t0 = (uint32_t)__builtin_amdgcn_readlane((int)i0, 63), t1 = (uint32_t)__builtin_amdgcn_readlane((int)i1, 63);
-            uint32_t seq;
-            do {
-                seq = __hip_atomic_load(&hand->seq, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP);
-            } while (seq != (uint32_t)win && seq != 0xFFFFFFFFu);
-            if (seq == 0xFFFFFFFFu) return;
-            const sj_u64 out = hand->out;
-            const uint32_t ord = hand->ord;
-            out2 = out + t0;
-            ord2 = ord + t1;
-            if (lane == 0) {
-                hand->out = out2;
-                hand->ord = ord2;
-                __hip_atomic_store(&hand->seq, (uint32_t)win + 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-            }
-            sscan_publish(v, pfx, first, n, out + (i0 - s0), ord + (i1 - s1));
-        } else {
-            uint32_t seq;
-            do {
-                seq = __hip_atomic_load(&hand->seq, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP);
-            } while (seq != (uint32_t)win && seq != 0xFFFFFFFFu);
-            if (seq == 0xFFFFFFFFu) return;
-            sj_u64 out = hand->out;
-            uint32_t ord = hand->ord;
-            int done = 0;
-            for (uint32_t spins = 0;; ++spins) {
-                const sj_u64 rb = __ballot(sscan_ready(v));
-                const int nr = ~rb ? __builtin_ctzll(~rb) : 64;
-                if (nr > done) {
-                    const bool act = lane >= done && lane < nr;
-                    uint32_t s0, s1;
-                    sscan_fold(v, &s0, &s1);
-                    if (!act) s0 = s1 = 0;
-                    const uint32_t i0 = str_incl_scan(s0), i1 = str_incl_scan(s1);
-                    if (act) sscan_publish(v, pfx, first, n, out + (i0 - s0), ord + (i1 - s1));
-                    out += (uint32_t)__builtin_amdgcn_readlane((int)i0, 63);
-                    ord += (uint32_t)__builtin_amdgcn_readlane((int)i1, 63);
-                    done = nr;
-                    spins = 0;
-                }
-                if (done == 64) break;
-                if (spins > STR_SPIN_LIMIT) {  // never expected: a worker did not publish
-                    if (lane == 0) {
-                        __hip_atomic_fetch_or(&a.wsflags[0], SJMI_ST_INTERNAL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        __hip_atomic_store(&hand->seq, 0xFFFFFFFFu, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                        __hip_atomic_fetch_or(&a.res->flags, 4u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    }
-                    return;
-                }
-                __builtin_amdgcn_s_sleep(1);
-                sj_u64 nv[SSCAN_K];
-                sscan_load(nv, agg, first, n);
+    // the lane's granules: bytes, strings
+    __device__ static void fold(const sj_u64 (&v)[K], uint32_t* s0, uint32_t* s1) {
+        uint32_t b = 0, o = 0;
 #pragma unroll
-                for (int j = 0; j < SSCAN_K; ++j)
-                    if (lane >= done) v[j] = nv[j];
-            }
-            out2 = out;
-            ord2 = ord;
-            if (lane == 0) {
-                hand->out = out2;
-                hand->ord = ord2;
-                __hip_atomic_store(&hand->seq, (uint32_t)win + 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-            }
+        for (int j = 0; j < K; ++j) {
+            b += (uint32_t)v[j] & 0xFFFFFu;
+            o += (uint32_t)(v[j] >> 20) & 0xFFFFu;
         }
-        if ((win + 1) * WIN >= n && lane == 0) {  // the last window: the launch's totals
-            a.res->total_bytes = out2;
-            a.res->reserved = ord2;
-            uint32_t f = 0;
-            if (out2 > a.sb_cap || out2 > 0xFFFFFFFFull) f |= 1u;   // string buffer too small (nothing was written past its end)
-            if (a.soff && (sj_u64)ord2 > a.soff_cap) f |= 2u;       // record table too small
-            if (f) __hip_atomic_fetch_or(&a.res->flags, f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        *s0 = b;
+        *s1 = o;
+    }
+    // prefixes of the lane's granules, given the bytes and strings in front of them
+    __device__ static void publish(const sj_u64 (&v)[K], sj_u64* pfx, sj_u64 first, uint32_t n, sj_u64 out, uint32_t ord) {
+#pragma unroll
+        for (int j = 0; j < K; ++j) {
+            out += (uint32_t)v[j] & 0xFFFFFu;
+            ord += (uint32_t)(v[j] >> 20) & 0xFFFFu;
+            if (first + j < n) {
+                const sj_u64 o32 = out > 0xFFFFFFFFull ? 0xFFFFFFFFull : out;
+                const sj_u64 r30 = ord > 0x3FFFFFFFu ? 0x3FFFFFFFu : ord;
+                granule_store(&pfx[first + j], CHAIN_PFX | (r30 << 32) | o32);
+            }
         }
     }
-}
+
+    struct Window {
+        uint32_t s0, s1;  // the lane's bytes, strings
+        uint32_t i0, i1;  // ... their inclusive scans
+        uint32_t t0, t1;  // ... and totals
+    };
+    __device__ Window window(const sj_u64 (&v)[K], int) const {
+        Window w;
+        fold(v, &w.s0, &w.s1);
+        w.i0 = wave_incl_add(w.s0);
+        w.i1 = wave_incl_add(w.s1);
+        w.t0 = (uint32_t)__builtin_amdgcn_readlane((int)w.i0, 63);
+        w.t1 = (uint32_t)__builtin_amdgcn_readlane((int)w.i1, 63);
+        return w;
+    }
+    // (ChainState: w = strings, c = bytes -- the reverse of the order of the aggregate's fields and of Window)
+    __device__ ChainState advance(ChainState in, const sj_u64 (&)[K], const Window& w) const {
+        return {in.w + w.t1, in.c + w.t0};
+    }
+    __device__ void publish_window(const sj_u64 (&v)[K], sj_u64* pfx, sj_u64 first, uint32_t n, ChainState in, const Window& w) const {
+        publish(v, pfx, first, n, in.c + (w.i0 - w.s0), in.w + (w.i1 - w.s1));
+    }
+    __device__ ChainState publish_ready(const sj_u64 (&v)[K], sj_u64* pfx, sj_u64 first, uint32_t n, int, bool act,
+                                        ChainState s) const {
+        uint32_t s0, s1;
+        fold(v, &s0, &s1);
+        if (!act) s0 = s1 = 0;
+        const uint32_t i0 = wave_incl_add(s0), i1 = wave_incl_add(s1);
+        if (act) publish(v, pfx, first, n, s.c + (i0 - s0), s.w + (i1 - s1));
+        return {s.w + (uint32_t)__builtin_amdgcn_readlane((int)i1, 63), s.c + (uint32_t)__builtin_amdgcn_readlane((int)i0, 63)};
+    }
+    __device__ void give_up() const {
+        __hip_atomic_fetch_or(&a.wsflags[0], SJMI_ST_INTERNAL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_fetch_or(&a.res->flags, 4u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    // the launch's totals
+    __device__ void finish(ChainState s) const {
+        const sj_u64 bytes = s.c;
+        const uint32_t strings = s.w;
+        a.res->total_bytes = bytes;
+        a.res->reserved = strings;
+        uint32_t f = 0;
+        if (bytes > a.sb_cap || bytes > 0xFFFFFFFFull) f |= 1u;  // string buffer too small (nothing was written past its end)
+        if (a.soff && (sj_u64)strings > a.soff_cap) f |= 2u;     // record table too small
+        if (f) __hip_atomic_fetch_or(&a.res->flags, f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+};
 
 // ---------------------------------------------------------------------------------------------------------------------
 // workers
@@ -326,15 +227,14 @@ k_strings(const StrArgs a0) {
     __shared__ StrWaveLds<SOFF> sh[4];
     __shared__ uint32_t s_uq[4][STR_UQ_ITEMS];  // the \uXXXX sequences of a wave's granule: tile offset | position << 14 | pair << 26
     __shared__ uint32_t s_lut[16];
-    __shared__ StrHand hand;
+    __shared__ ChainHandoff hand;
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const uint32_t ngran = a.ngran;
     sj_u64* const agg = a.gstate;
     sj_u64* const pfx = a.gstate + ngran;
     sj_u64* const orec = a.gstate + 2 * (sj_u64)ngran;
-    const uint32_t my_cu = (((uint32_t)__builtin_amdgcn_s_getreg((31 << 11) | 4) >> 8) & 0xFFu) |
-                           (((uint32_t)__builtin_amdgcn_s_getreg((31 << 11) | 20) & 0xFu) << 8) | 0x80000000u;
+    const uint32_t my_cu = cu_id();
     // Roles by ARRIVAL, not by workgroup number: the first workgroup that gets a CU is the scanner, so the scanner is resident
     // whenever a worker is.  (Workgroups are not placed in order when another process's persistent kernel holds part of the GPU:
     // with the scanner = workgroup 0, two processes alternating stage 1 and this pass left workers polling for a scanner that was
@@ -347,11 +247,12 @@ k_strings(const StrArgs a0) {
         if (threadIdx.x == 0) {
             __hip_atomic_store(&a.wsflags[1], my_cu, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             hand.seq = 0;
-            hand.ord = 0;
-            hand.out = 0;
+            hand.w = 0;
+            hand.c = 0;
         }
         __syncthreads();
-        str_scanner_wave(&hand, wave, a, lane);
+        const StrChain pol = {a};
+        chain_scanner_wave(&hand, wave, lane, agg, pfx, ngran, pol);
         return;
     }
     if (threadIdx.x < 16) s_lut[threadIdx.x] = sj_str_pack_selector(threadIdx.x);
@@ -368,12 +269,7 @@ k_strings(const StrArgs a0) {
     // workers that share the scanner's CU run at ~2/3 speed and would pace the chain: they retire after one granule
     uint32_t retire = 1;
     if (gridDim.x >= 64) retire = __hip_atomic_load(&a.wsflags[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) ^ my_cu;
-    uint32_t cur;
-    {
-        uint32_t t = 0;
-        if (lane == 0) t = __hip_atomic_fetch_add(my_ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        cur = (uint32_t)__builtin_amdgcn_readfirstlane((int)t) * NC + cls;
-    }
+    uint32_t cur = take_ticket(my_ticket) * NC + cls;
     StrStep d;
     str_load_step(d, a.buf, (sj_u64)cur * 64 + lane, nblocks);
 
@@ -458,7 +354,7 @@ k_strings(const StrArgs a0) {
             m = sj_str_block(p, s, pin, any_esc || do_u, do_u, &halo);
             entered_in = pin;
             const uint32_t nout = sj_str_out_bytes(m), nopen = (uint32_t)__popcll(m.O);
-            const uint32_t packed = str_incl_scan(nout | (nopen << 16));
+            const uint32_t packed = wave_incl_add(nout | (nopen << 16));
             const uint32_t tot = (uint32_t)__builtin_amdgcn_readlane((int)packed, 63);
             tot_out = tot & 0xFFFFu;
             tot_open = tot >> 16;
@@ -466,7 +362,7 @@ k_strings(const StrArgs a0) {
             oexcl = (packed >> 16) - nopen;
             // the header of the string that is open where a lane's block begins: the last opening quote in front of it
             const uint32_t lastD = m.O ? base + sj_str_offset(m, 63u - (uint32_t)__builtin_clzll(m.O)) + 1u : 0u;
-            const uint32_t lm = str_incl_max(lastD ? ((lastD << 6) | (uint32_t)lane) : 0u);
+            const uint32_t lm = wave_incl_max(lastD ? ((lastD << 6) | (uint32_t)lane) : 0u);
             uint32_t prevv = (uint32_t)__shfl_up((int)lm, 1);
             if (lane == 0) prevv = 0;
             prevD = prevv >> 6;
@@ -521,9 +417,9 @@ k_strings(const StrArgs a0) {
                 }
             }
             if (lane == 0) {
-                sg_store(&orec[cur], OR_VALID | ((exit_in && open_lanes) ? OR_HAS_OPEN : 0ull) | ((sj_u64)pend_err << 16) |
+                granule_store(&orec[cur], OR_VALID | ((exit_in && open_lanes) ? OR_HAS_OPEN : 0ull) | ((sj_u64)pend_err << 16) |
                                          (sj_u64)(pend_rel == STR_NONE ? 0u : pend_rel));
-                sg_store(&agg[cur], SG_AGG | ((sj_u64)(any_err ? 1u : 0u) << 36) | ((sj_u64)tot_open << 20) | (sj_u64)tot_out);
+                granule_store(&agg[cur], CHAIN_AGG | ((sj_u64)(any_err ? 1u : 0u) << 36) | ((sj_u64)tot_open << 20) | (sj_u64)tot_out);
                 if (retire != 0) tk = __hip_atomic_fetch_add(my_ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
             __builtin_amdgcn_s_setprio(0);
@@ -543,7 +439,7 @@ k_strings(const StrArgs a0) {
         bool u_dense = false;
         if (any_items) {
             const uint32_t n_it = (uint32_t)__popcll(items);
-            const uint32_t sc = str_incl_scan(n_it);
+            const uint32_t sc = wave_incl_add(n_it);
             const uint32_t tot_it = (uint32_t)__builtin_amdgcn_readlane((int)sc, 63);
             u_dense = tot_it <= STR_UQ_ITEMS;
             if (u_dense) {
@@ -554,7 +450,7 @@ k_strings(const StrArgs a0) {
                     const uint32_t dest = base + sj_str_offset(m, e);  // (< STR_TILE_BYTES: 14 bits)
                     uq[i] = dest | ((((uint32_t)lane << 6) | e) << 14) | ((uint32_t)((m.pair >> e) & 1ull) << 26);
                 }
-                str_lds_fence();
+                wave_lds_fence();
                 u_n = tot_it;
                 if ((uint32_t)lane < u_n) {
                     u_ent = uq[lane];
@@ -581,17 +477,12 @@ k_strings(const StrArgs a0) {
             sj_u64 outbase = 0;
             uint32_t ordbase = 0;
             if (prev != 0) {
-                for (uint32_t spins = 0; (pf >> 62) != 2; ++spins) {
-                    if (spins > STR_SPIN_LIMIT) {  // never expected: the scanner is not running
-                        if (lane == 0) {
-                            __hip_atomic_fetch_or(&a.wsflags[0], SJMI_ST_INTERNAL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                            __hip_atomic_fetch_or(&a.res->flags, 4u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        }
-                        break;
+                wait_prefix(&pfx[prev - 1], pf, [&] {
+                    if (lane == 0) {
+                        __hip_atomic_fetch_or(&a.wsflags[0], SJMI_ST_INTERNAL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        __hip_atomic_fetch_or(&a.res->flags, 4u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                     }
-                    if (spins) __builtin_amdgcn_s_sleep(1);  // (no sleep: 0.407 ms instead of 0.389 -- the polls compete with the stores; 2 .. 8: no change)
-                    pf = sg_load(&pfx[prev - 1]);
-                }
+                });
                 outbase = pf & 0xFFFFFFFFull;
                 ordbase = (uint32_t)(pf >> 32) & 0x3FFFFFFFu;
             }
@@ -627,14 +518,14 @@ k_strings(const StrArgs a0) {
                 sj_u64 rec = pf_or, pp = pf_pp;
                 for (uint32_t hops = 0; prev != 0; ++hops) {
                     if (hops) {
-                        rec = sg_load(&orec[g]);
-                        pp = g ? sg_load(&pfx[g - 1]) : SG_PFX;
+                        rec = granule_load(&orec[g]);
+                        pp = g ? granule_load(&pfx[g - 1]) : CHAIN_PFX;
                     }
                     for (uint32_t spins = 0; !(rec & OR_VALID) || (g && (pp >> 62) != 2); ++spins) {
-                        if (spins > STR_SPIN_LIMIT) break;
+                        if (spins > CHAIN_SPIN_LIMIT) break;
                         __builtin_amdgcn_s_sleep(1);
-                        rec = sg_load(&orec[g]);
-                        pp = g ? sg_load(&pfx[g - 1]) : SG_PFX;
+                        rec = granule_load(&orec[g]);
+                        pp = g ? granule_load(&pfx[g - 1]) : CHAIN_PFX;
                     }
                     if (!(rec & OR_VALID)) break;
                     const uint32_t e2 = (uint32_t)(rec >> 16) & 0xFFu;
@@ -668,7 +559,7 @@ k_strings(const StrArgs a0) {
                     }
                 }
             }
-            str_lds_fence();
+            wave_lds_fence();
         }
         if (!have) break;
 
@@ -676,7 +567,7 @@ k_strings(const StrArgs a0) {
         {
             const uint4 z = make_uint4(0, 0, 0, 0);
             for (uint32_t q = (uint32_t)lane; q * 16u < tot_out + 32u; q += 64) reinterpret_cast<uint4*>(tile)[q] = z;
-            str_lds_fence();
+            wave_lds_fence();
             const SjStrGroups g = sj_str_groups(m.K, m.O);
             const sj_u64 Kc = m.K & ~(g.bad << 1);
             const uint32_t B = base + m.head;
@@ -705,7 +596,7 @@ k_strings(const StrArgs a0) {
             asm volatile("" ::: "memory");
             str_load_step(d, a.buf, (sj_u64)nxt * 64 + lane, nblocks);
             asm volatile("" ::: "memory");
-            str_lds_fence();
+            wave_lds_fence();
             // ---- headers, by the closing quotes: length = kept bytes between the quotes (32-bit halves: 64-bit shifts by
             //      a variable are slow) ----
             if (!any_err) {
@@ -853,17 +744,17 @@ k_strings(const StrArgs a0) {
                     tile_xor(tile, base + sj_str_offset(m, e) - (L - 1u), old ^ nb);
                 }
             }
-            str_lds_fence();
+            wave_lds_fence();
         }
         // one classification ahead of their use: the prefix in front of this granule (and what a closing quote needs)
         if (cur != 0) {
-            pf = sg_load(&pfx[cur - 1]);
-            pf_or = sg_load(&orec[cur - 1]);
-            pf_pp = cur >= 2 ? sg_load(&pfx[cur - 2]) : SG_PFX;
+            pf = granule_load(&pfx[cur - 1]);
+            pf_or = granule_load(&orec[cur - 1]);
+            pf_pp = cur >= 2 ? granule_load(&pfx[cur - 2]) : CHAIN_PFX;
         } else {
-            pf = SG_PFX;
+            pf = CHAIN_PFX;
             pf_or = 0;
-            pf_pp = SG_PFX;
+            pf_pp = CHAIN_PFX;
         }
         prev = cur;
         prev_n = tot_out;

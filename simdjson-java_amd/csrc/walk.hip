@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "sj_chain.h"
 #include "stage1.h"
 
 namespace sjmi {
@@ -21,27 +22,6 @@ __device__ __forceinline__ unsigned long long scratch_slot(unsigned long long fr
 
 // ---- packing the tapes ---------------------------------------------------------------------------
 constexpr int PACK_DOCS = 1024;  // documents per workgroup
-
-__device__ __forceinline__ unsigned long long block_excl_scan(unsigned long long v, unsigned long long* s_wave,
-                                                              unsigned long long* total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    unsigned long long incl = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const unsigned long long o = __shfl_up(incl, d);
-        if (lane >= d) incl += o;
-    }
-    __syncthreads();
-    if (lane == 63) s_wave[wave] = incl;
-    __syncthreads();
-    unsigned long long base = 0, t = 0;
-    for (int i = 0; i < nw; ++i) {
-        if (i < wave) base += s_wave[i];
-        t += s_wave[i];
-    }
-    *total = t;
-    return base + incl - v;
-}
 
 __global__ void __launch_bounds__(1024)
 k_tape_chunk_sums(const uint32_t* __restrict__ tape_lens, const int32_t* __restrict__ doc_errors, uint64_t n_docs,
@@ -65,16 +45,7 @@ k_tape_chunk_scan(unsigned long long* __restrict__ chunk_sums, uint64_t nchunks,
                   unsigned long long* __restrict__ tape_offsets, WalkResult* res, const uint32_t* __restrict__ gate, uint32_t gate_want) {
     if (gate && (*gate != 0) != (gate_want != 0)) return;
     __shared__ unsigned long long s_wave[16];
-    unsigned long long carry = 0;
-    for (uint64_t b = 0; b < nchunks; b += 1024) {
-        const uint64_t i = b + threadIdx.x;
-        const unsigned long long v = i < nchunks ? chunk_sums[i] : 0ull;
-        unsigned long long total;
-        const unsigned long long ex = block_excl_scan(v, s_wave, &total);
-        if (i < nchunks) chunk_sums[i] = carry + ex;
-        carry += total;
-        __syncthreads();
-    }
+    const unsigned long long carry = block_scan_in_place(chunk_sums, nchunks, s_wave);
     if (threadIdx.x == 0) {
         tape_offsets[0] = 0;  // (the others: k_tape_compact; a single document written in place has no other)
         tape_offsets[n_docs] = carry;
@@ -140,16 +111,7 @@ k_batch_layout(BatchLayout a, uint64_t nchunks) {
     if (threadIdx.x < 16) static_cast<uint32_t*>(a.slow_header)[threadIdx.x] = 0;
     __syncthreads();
     if (!s_acc) return;
-    unsigned long long carry = 0;
-    for (uint64_t b = 0; b < nchunks; b += 1024) {
-        const uint64_t i = b + threadIdx.x;
-        const unsigned long long v = i < nchunks ? a.chunk_sums[i] : 0ull;
-        unsigned long long total;
-        const unsigned long long ex = block_excl_scan(v, s_wave, &total);
-        if (i < nchunks) a.chunk_sums[i] = carry + ex;
-        carry += total;
-        __syncthreads();
-    }
+    const unsigned long long carry = block_scan_in_place(a.chunk_sums, nchunks, s_wave);
     if (threadIdx.x == 0) {
         a.tape_offsets[0] = 0;
         a.tape_offsets[a.n_docs] = carry;
