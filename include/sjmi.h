@@ -465,6 +465,46 @@ int sjmi_value_size(const sjmi_parser* p, const sjmi_value* v);                 
 int sjmi_value_first(const sjmi_parser* p, const sjmi_value* container, sjmi_value* out);
 int sjmi_value_next(const sjmi_parser* p, const sjmi_value* container, const sjmi_value* child, sjmi_value* out);
 
+/* ---- selecting fields of a parsed batch on the device ----------------------------------------------------------------
+ * JsonValue.get (JsonValue.java:91-107) and arrayIterator (:143-168) applied step by step along a path, for every path of
+ * a PLAN and every document of a batch whose tapes are still in device memory (csrc/select.hip).
+ *
+ * A path is an RFC 6901 JSON Pointer: "" = the document's root value, "/a/b" = get("a").get("b"), "~0" = '~', "~1" = '/'.
+ * The container at hand decides how a token is read.  Object: the token is a key, compared byte for byte with the unescaped
+ * key records (Arrays.compare(...) == 0, :102); the FIRST matching member wins (:95-105), so duplicate keys resolve as in the
+ * reference.  Array: the token must be "0" or a decimal without a leading zero, and names the k-th element of the iterator
+ * chain (Tape.computeNextIndex, Tape.java:86-98), whose end is the matching index (:151), not the 24-bit scope count.
+ * Anything else -- a scalar at hand, a token that is no index on an array ("-" included), an index past the end, a key that
+ * is not there -- makes the path MISSING for that document.
+ *
+ * sjmi_select_plan_compile: n_paths pointers, pointer p = pointers[pointer_offsets[p], pointer_offsets[p + 1]) (n_paths + 1
+ * offsets).  Host only: no device, no context.  The paths are compiled to a trie, so the members of a container are visited
+ * once for all paths that pass through it; results never depend on that sharing.  SJMI_ERR_ARG: a pointer is not empty and
+ * does not begin with '/'; a '~' is followed by anything but '0' or '1'; or a limit is exceeded: */
+#define SJMI_SELECT_MAX_PATHS 64u       /* paths of one plan */
+#define SJMI_SELECT_MAX_STEPS 16u       /* reference tokens of one path */
+#define SJMI_SELECT_MAX_NAME_BYTES 4096u /* the distinct (prefix, token) pairs of the plan, each token's unescaped bytes rounded up to a
+                                          * multiple of 8, together (the plan has to fit in LDS) */
+typedef struct sjmi_select_plan sjmi_select_plan;
+int sjmi_select_plan_compile(const uint8_t* pointers, const uint64_t* pointer_offsets, uint64_t n_paths, sjmi_select_plan** out);
+void sjmi_select_plan_destroy(sjmi_select_plan* plan);
+/* Every path of `plan` on every document: d_tape, d_tape_offsets, d_doc_errors, d_string_buffer are the outputs of
+ * sjmi_parse_batch_device / _optimistic / _rejected or of sjmi_walk_batch_device with string_base 0 (read only here).
+ * Outputs, path-major so that a column is contiguous: d_types[p * n_docs + k] (uint8) and d_values[p * n_docs + k] (uint64):
+ *   type 0                  MISSING; value 0
+ *   'l' 'd'                 the payload word: the int64, or the IEEE bits (Tape.getInt64Value, Tape.java:69-71; JsonValue.asDouble :73-75)
+ *   't' 'f'                 1 / 0 (JsonValue.asBoolean :77-79)
+ *   'n'                     0
+ *   '"'                     (length << 32) | (record offset + 4): the unescaped bytes in d_string_buffer (JsonValue.getString :85-89)
+ *   '[' '{'                 (Tape.getScopeCount << 32, Tape.java:82-84) | tape index of the value inside its document
+ * A document with doc_errors[k] != 0 (a JSON error or SJMI_WALK_NEEDS_HOST) is MISSING on every path and its tape slot is never
+ * read.  Asynchronous on `stream` (NULL = the context's), no host synchronisation, nothing queued but the kernel; the first
+ * call with a plan copies it to the context's device memory (one blocking upload), later calls with the same plan reuse it.
+ * A context holds one plan at a time: a call with another plan first waits for the device, then uploads that one. */
+int sjmi_select_batch_device(sjmi_ctx* ctx, const sjmi_select_plan* plan, const void* d_tape, const void* d_tape_offsets,
+                             const void* d_doc_errors, const void* d_string_buffer, uint64_t n_docs, void* d_types, void* d_values,
+                             void* stream);
+
 /* Optional: page-lock caller-owned host memory that is passed to the host-buffer entry points again and again
  * (SimdJsonParser's padded input, index array and string buffer): H2D / D2H copies of pinned memory skip the
  * driver's staging copy (3-4x faster for the ~1 MB transfers of a single-document parse).  Purely a performance

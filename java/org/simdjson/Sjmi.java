@@ -63,6 +63,13 @@ final class Sjmi {
     static final MethodHandle CREATE = h("sjmi_create", FunctionDescriptor.of(JAVA_INT, ADDRESS, JAVA_INT, JAVA_LONG));
     // void sjmi_destroy(sjmi_ctx* ctx)
     static final MethodHandle DESTROY = h("sjmi_destroy", FunctionDescriptor.ofVoid(ADDRESS));
+    // int sjmi_select_plan_compile(const uint8_t* pointers, const uint64_t* pointer_offsets, uint64_t n_paths, sjmi_select_plan** out)
+    static final MethodHandle SELECT_PLAN_COMPILE = h("sjmi_select_plan_compile", FunctionDescriptor.of(JAVA_INT, ADDRESS, ADDRESS, JAVA_LONG, ADDRESS));
+    // void sjmi_select_plan_destroy(sjmi_select_plan* plan)
+    static final MethodHandle SELECT_PLAN_DESTROY = h("sjmi_select_plan_destroy", FunctionDescriptor.ofVoid(ADDRESS));
+    // int sjmi_select_batch_device(ctx, plan, d_tape, d_tape_offsets, d_doc_errors, d_string_buffer, uint64_t n_docs, d_types, d_values, stream)
+    static final MethodHandle SELECT_BATCH_DEVICE = h("sjmi_select_batch_device",
+            FunctionDescriptor.of(JAVA_INT, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS, JAVA_LONG, ADDRESS, ADDRESS, ADDRESS));
     // const char* sjmi_last_error(const sjmi_ctx* ctx)
     static final MethodHandle LAST_ERROR = critical("sjmi_last_error", FunctionDescriptor.of(ADDRESS, ADDRESS));
 

@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_HERE)
 _CSRC = os.path.join(_HERE, "csrc")
 _LIB = os.path.join(_HERE, "libsjmi.so")
-SOURCES = ["stage1.hip", "strings.hip", "batch.hip", "walk.hip", "coop_walk.hip", "masks.hip", "sjmi_api.hip", "host/simdjson_parser.cpp"]
+SOURCES = ["stage1.hip", "strings.hip", "batch.hip", "walk.hip", "coop_walk.hip", "masks.hip", "select.hip", "sjmi_api.hip", "host/simdjson_parser.cpp"]
 
 ST_UTF8, ST_UNCLOSED, ST_UNESCAPED, ST_CAPACITY, ST_INTERNAL = 1, 2, 4, 0x100, 0x200
 PADDING = 64
@@ -105,7 +105,8 @@ EXPORTS = ["sjmi_create", "sjmi_destroy", "sjmi_last_error", "sjmi_version", "sj
            "sjmi_parser_ondemand_init", "sjmi_od_skip_child", "sjmi_od_get_boolean", "sjmi_od_get_long", "sjmi_od_get_integral", "sjmi_od_get_double", "sjmi_od_get_float", "sjmi_od_get_char",
            "sjmi_od_get_string", "sjmi_od_get_field_name", "sjmi_od_start_array", "sjmi_od_next_array_element",
            "sjmi_od_start_object", "sjmi_od_next_object_field", "sjmi_od_move_to_field_value", "sjmi_od_assert_no_more_values",
-           "sjmi_od_depth", "sjmi_od_peek"]
+           "sjmi_od_depth", "sjmi_od_peek",
+           "sjmi_select_plan_compile", "sjmi_select_plan_destroy", "sjmi_select_batch_device"]
 
 
 # Handles that are still open when the interpreter exits are closed HERE, in an atexit hook -- i.e. while the HIP runtime
@@ -252,6 +253,13 @@ def lib():
         L.sjmi_parse_batch_device_rejected.argtypes = L.sjmi_parse_batch_device.argtypes
         L.sjmi_kernel_time.restype = C.c_int
         L.sjmi_kernel_time.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.sjmi_select_plan_compile.restype = C.c_int
+        L.sjmi_select_plan_compile.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p)]
+        L.sjmi_select_plan_destroy.restype = None
+        L.sjmi_select_plan_destroy.argtypes = [C.c_void_p]
+        L.sjmi_select_batch_device.restype = C.c_int
+        L.sjmi_select_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
+                                               C.c_void_p, C.c_void_p, C.c_void_p]
         _lib = L
     return _lib
 
@@ -467,6 +475,12 @@ class Context:
                                                            max_depth, d_tape, tape_capacity, d_tape_offsets, d_doc_errors, d_result,
                                                            stream), "sjmi_parse_batch_device_rejected")
 
+    def select_batch_device(self, plan, d_tape, d_tape_offsets, d_doc_errors, d_sb, n_docs, d_types, d_values, stream=0):
+        """sjmi_select_batch_device: every path of `plan` (a SelectPlan) on every document of a parsed batch; d_types
+        (uint8) / d_values (uint64) are path-major columns of n_docs entries each.  Asynchronous on `stream`."""
+        self._check(lib().sjmi_select_batch_device(self._h, plan._h, d_tape, d_tape_offsets, d_doc_errors, d_sb, n_docs, d_types,
+                                                   d_values, stream), "sjmi_select_batch_device")
+
     def stage1_batch_device(self, d_buf, total_len, d_doc_offsets, n_docs, d_indexes, index_capacity, d_index_offsets,
                             d_result, stream=0):
         self._check(lib().sjmi_stage1_batch_device(self._h, d_buf, total_len, d_doc_offsets, n_docs, d_indexes,
@@ -517,6 +531,37 @@ class Context:
         n = C.c_uint32(0)
         self._check(lib().sjmi_kernel_time(self._h, C.addressof(ms), C.addressof(n)), "sjmi_kernel_time")
         return ms.value, n.value
+
+
+class SelectPlan:
+    """sjmi_select_plan: a set of RFC 6901 JSON Pointers (str or bytes) compiled once, on the host (no device needed), for
+    Context.select_batch_device / BatchShard.select.  Raises ValueError for a malformed pointer or an exceeded limit
+    (include/sjmi.h: SJMI_SELECT_MAX_*)."""
+
+    MISSING = 0
+
+    def __init__(self, pointers):
+        self.pointers = [p.encode("utf-8") if isinstance(p, str) else bytes(p) for p in pointers]
+        self.n_paths = len(self.pointers)
+        blob = np.frombuffer(b"".join(self.pointers) + b"\0", dtype=np.uint8)
+        offs = np.zeros(self.n_paths + 1, dtype=np.uint64)
+        offs[1:] = np.cumsum([len(p) for p in self.pointers], dtype=np.uint64)
+        self._h = C.c_void_p()
+        rc = lib().sjmi_select_plan_compile(blob.ctypes.data, offs.ctypes.data, self.n_paths, C.byref(self._h))
+        if rc != 0:
+            self._h = C.c_void_p()
+            raise ValueError("sjmi_select_plan_compile failed (rc=%d): a malformed JSON Pointer or a plan limit exceeded" % rc)
+
+    def close(self):
+        if self._h:
+            lib().sjmi_select_plan_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class JsonParsingException(Exception):

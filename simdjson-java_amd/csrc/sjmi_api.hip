@@ -114,6 +114,8 @@ struct sjmi_ctx {
     bool profiling = false;  // bracket every stage-1 kernel with HIP events (bench.py roofline)
     std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
     size_t events_used = 0;
+    DevBuf<void> d_plan;                     // sjmi_select_batch_device: the plan the last call used, as k_select reads it
+    uint64_t plan_serial = 0;                // ... and which one it is (0: none)
     std::string err;
 };
 
@@ -897,6 +899,32 @@ int sjmi_walk_batch_device(sjmi_ctx* c, const void* d_buf, const void* d_doc_off
     w.dev_strings = (const sjmi::UnescapeResult*)c->d_ures_walk.p;
     w.d_soff = c->d_soff;
     return fail(c, "walk launch", sjmi::walk_launch(w, st)) ? SJMI_ERR_HIP : SJMI_OK;
+}
+
+int sjmi_select_batch_device(sjmi_ctx* c, const sjmi_select_plan* plan, const void* d_tape, const void* d_tape_offsets,
+                             const void* d_doc_errors, const void* d_string_buffer, uint64_t n_docs, void* d_types, void* d_values,
+                             void* stream) {
+    if (!c || !plan) return SJMI_ERR_ARG;
+    size_t bytes;
+    uint64_t serial;
+    uint32_t n_paths;
+    const void* image = sjmi::select_plan_image(plan, &bytes, &serial, &n_paths);
+    if (n_docs && n_paths && (!d_tape || !d_tape_offsets || !d_doc_errors || !d_string_buffer || !d_types || !d_values)) return SJMI_ERR_ARG;
+    if (fail(c, "hipSetDevice", hipSetDevice(c->device))) return SJMI_ERR_HIP;
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    if (c->plan_serial != serial) {
+        // another plan than the one on the device: a launch of the old one may still be reading it
+        c->plan_serial = 0;
+        if (c->d_plan.p && fail(c, "sync", hipDeviceSynchronize())) return SJMI_ERR_HIP;
+        if (!grow(c, c->d_plan, bytes, "hipMalloc(plan)") || fail(c, "H2D(plan)", hipMemcpy(c->d_plan, image, bytes, hipMemcpyHostToDevice)))
+            return SJMI_ERR_HIP;
+        c->plan_serial = serial;
+    }
+    if (!n_paths) return SJMI_OK;
+    return fail(c, "select launch", sjmi::select_launch(c->d_plan, bytes, d_tape, d_tape_offsets, d_doc_errors, d_string_buffer, n_docs,
+                                                        d_types, d_values, st))
+               ? SJMI_ERR_HIP
+               : SJMI_OK;
 }
 
 int sjmi_stage1_device(sjmi_ctx* c, const void* d_buf, uint64_t len, void* d_indexes, uint64_t index_capacity,

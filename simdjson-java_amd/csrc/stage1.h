@@ -370,4 +370,11 @@ inline hipError_t resident_workgroups(unsigned* out) {
     return hipSuccess;
 }
 
+// ---- the selector (select.hip) ----
+// a compiled plan as the kernel reads it (host memory owned by the plan), its size, the plan's serial number and its paths
+const void* select_plan_image(const sjmi_select_plan* plan, size_t* bytes, uint64_t* serial, uint32_t* n_paths);
+// k_select over a parsed batch with the plan image at d_plan; columns types[p * n_docs + k] / values[p * n_docs + k]
+hipError_t select_launch(const void* d_plan, size_t plan_bytes, const void* d_tape, const void* d_tape_offsets, const void* d_doc_errors,
+                         const void* d_string_buffer, uint64_t n_docs, void* d_types, void* d_values, hipStream_t stream);
+
 }  // namespace sjmi

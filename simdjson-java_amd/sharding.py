@@ -103,11 +103,31 @@ class BatchShard:
             fn = self.engine.parse_batch_device if exact or rejected or not hasattr(self.engine, "parse_batch_device_optimistic") \
                 else self.engine.parse_batch_device_optimistic
         self._last_stream = stream
+        self._sel_pending = None  # (a select queued behind an earlier step does not belong to this one)
         fn(self.buf.data_ptr(), self.n, self.offs.data_ptr(), self.n_docs, self.idx.data_ptr(),
                                        self.index_capacity, self.index_offsets.data_ptr(), self.doc_status.data_ptr(),
                                        self.sb.data_ptr(), self.sb_capacity, self.doc_string_offsets.data_ptr(), self.max_depth,
                                        self.tape.data_ptr(), self.tape_capacity, self.tape_offsets.data_ptr(),
                                        self.doc_errors.data_ptr(), self.result.data_ptr(), stream)
+
+    def select(self, plan, stream=0):
+        """Every path of `plan` (a binding.SelectPlan) on every document of the shard: sjmi_select_batch_device, queued on
+        `stream` behind the step() that was queued there -- no host synchronisation, the tapes never leave the device.
+        -> (sel_types [n_paths, n_docs] uint8, sel_values [n_paths, n_docs] int64), allocated once per plan and overwritten
+        by every call: types 0 = MISSING, else the tape type byte; values as include/sjmi.h lays them out (string values
+        point into self.sb).  A step that came back SJMI_ST_REJECTED has no valid outputs, so the columns are valid only for
+        a step check() has accepted: when check() runs the step again through the call for rejected batches (or the exact
+        call), it queues this select again behind it, and the columns then belong to that run.  A document that failed
+        (doc_errors[k] != 0) is MISSING on every path."""
+        import torch
+        if getattr(self, "_sel_plan", None) is not plan:
+            self.sel_types = torch.zeros((plan.n_paths, self.n_docs), dtype=torch.uint8, device=self.device)
+            self.sel_values = torch.zeros((plan.n_paths, self.n_docs), dtype=torch.int64, device=self.device)
+            self._sel_plan = plan
+        self._sel_pending = (plan, stream)
+        self.engine.select_batch_device(plan, self.tape.data_ptr(), self.tape_offsets.data_ptr(), self.doc_errors.data_ptr(),
+                                        self.sb.data_ptr(), self.n_docs, self.sel_types.data_ptr(), self.sel_values.data_ptr(), stream)
+        return self.sel_types, self.sel_values
 
     def counts_tensor(self):
         """The per-shard row of the count gather, on the device, without a host copy:
@@ -122,6 +142,7 @@ class BatchShard:
         st1, sflags, wflags = int(r[1]) & 0xFFFFFFFF, int(r[4]) & 0xFFFFFFFF, int(r[8]) & 0xFFFFFFFF
         if st1 & 0x800:  # SJMI_ST_REJECTED: not a batch for the optimistic pipeline -- the exact call, here, off the hot path
             import torch
+            pending = getattr(self, "_sel_pending", None)
             self.rejected_steps = getattr(self, "rejected_steps", 0) + 1
             if not (st1 & 0xFF):
                 self.format_rejected = True  # (a clean stage-1 verdict and still rejected: the separators)
@@ -129,6 +150,8 @@ class BatchShard:
                 # the call for rejected batches (repair on the device); a batch it cannot take either -- documents that are not
                 # separated AND let a scalar run on across a boundary -- says REJECTED once more and is the exact call's
                 self.step(getattr(self, "_last_stream", 0), **entry)
+                if pending is not None:  # the select that was queued behind the rejected step read outputs that were not valid
+                    self.select(*pending)
                 if str(self.device) != "cpu":  # (the CPU tests' stub engines are synchronous)
                     torch.cuda.synchronize(self.device)
                 r = self.result.cpu().numpy()
