@@ -17,50 +17,79 @@ from tests.golden.vectors import TWITTER_DEFAULT_PROFILE_USERS
 SIM_DIR = os.path.join(ROOT, "tests", "host_sim")
 
 
-@pytest.fixture(scope="module")
-def sim():
+def load_sim():
+    """tests/host_sim/sel_sim.cpp as a shared library, built when it is older than its sources"""
     so = os.path.join(SIM_DIR, "libselsim.so")
     src = os.path.join(SIM_DIR, "sel_sim.cpp")
     hdrs = [os.path.join(ROOT, "simdjson-java_amd", "csrc", h) for h in ("sj_block.h", "sj_select.h")]
     if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(f) for f in [src] + hdrs):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", so, src])
+        tmp = "%s.%d.tmp" % (so, os.getpid())
+        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", tmp, src])
+        os.replace(tmp, so)
     lib = C.CDLL(so)
     lib.sim_select.restype = C.c_int
     lib.sim_select.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
                                C.c_void_p, C.c_void_p]
+    lib.sim_select_guarded.restype = C.c_int
+    lib.sim_select_guarded.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_uint64, C.c_void_p, C.c_void_p]
     lib.sim_select_slice_words.restype = C.c_uint32
+    return lib
 
-    def run(parsed, pointers):
-        """parsed: oracle.Parsed per document -> (types [n_paths, n_docs], values, the batch's string buffer)"""
-        ptrs = [p.encode("utf-8") if isinstance(p, str) else p for p in pointers]
-        blob = np.frombuffer(b"".join(ptrs) + b"\0", dtype=np.uint8)
-        poffs = np.zeros(len(ptrs) + 1, dtype=np.uint64)
-        poffs[1:] = np.cumsum([len(p) for p in ptrs], dtype=np.uint64)
-        tapes, sbs, toffs, errs, base = [], [], [0], [], 0
-        for p in parsed:
-            errs.append(p.error)
-            t = p.tape.copy() if p.error == 0 else np.full(3, 0x7B00000000000099, dtype=np.uint64)  # (a failed document's slot: garbage)
-            if p.error == 0:
-                # STRING payloads are offsets into the batch's shared buffer: only words at chain positions may be moved
-                i, n = 1, len(t) - 1
-                while i < n:
-                    ty = int(t[i]) >> 56
-                    if ty == ord('"'):
-                        t[i] = np.uint64(int(t[i]) + base)
-                    i += 2 if ty in (ord("l"), ord("d")) else 1
-                sbs.append(p.strings)
-                base += len(p.strings)
-            tapes.append(t)
-            toffs.append(toffs[-1] + len(t))
-        tape = np.concatenate(tapes) if tapes else np.zeros(1, dtype=np.uint64)
-        sb = np.frombuffer(b"".join(sbs) + b"\0" * 8, dtype=np.uint8)
-        n = len(parsed)
-        types = np.full((len(ptrs), n), 0xEE, dtype=np.uint8)
-        values = np.full((len(ptrs), n), 0xEEEEEEEEEEEEEEEE, dtype=np.uint64)
-        rc = lib.sim_select(blob.ctypes.data, poffs.ctypes.data, len(ptrs), tape.ctypes.data, np.array(toffs, dtype=np.uint64).ctypes.data,
-                            np.array(errs + [0], dtype=np.int32).ctypes.data, sb.ctypes.data, n, types.ctypes.data, values.ctypes.data)
-        assert rc == 0, rc
-        return types, values, sb.tobytes()
+
+def run_sim(lib, parsed, pointers, guarded=False):
+    """parsed: oracle.Parsed per document -> (types [n_paths, n_docs], values, the batch's string buffer).  guarded: through
+    sim_select_guarded -- every tape and every document's last string record end at a page that cannot be read."""
+    ptrs = [p.encode("utf-8") if isinstance(p, str) else p for p in pointers]
+    blob = np.frombuffer(b"".join(ptrs) + b"\0", dtype=np.uint8)
+    poffs = np.zeros(len(ptrs) + 1, dtype=np.uint64)
+    poffs[1:] = np.cumsum([len(p) for p in ptrs], dtype=np.uint64)
+    tapes, sbs, toffs, errs, base, sb_lo, sb_hi = [], [], [0], [], 0, [], []
+    for p in parsed:
+        errs.append(p.error)
+        t = p.tape.copy() if p.error == 0 else np.full(3, 0x7B00000000000099, dtype=np.uint64)  # (a failed document's slot: garbage)
+        end = base
+        if p.error == 0:
+            # STRING payloads are offsets into the batch's shared buffer: only words at chain positions may be moved
+            i, n = 1, len(t) - 1
+            while i < n:
+                ty = int(t[i]) >> 56
+                if ty == ord('"'):
+                    off = int(t[i]) & 0x00FFFFFFFFFFFFFF
+                    end = max(end, base + off + 4 + int.from_bytes(p.strings[off:off + 4], "big"))  # where the document's last record ends
+                    t[i] = np.uint64(int(t[i]) + base)
+                i += 2 if ty in (ord("l"), ord("d")) else 1
+            sbs.append(p.strings)
+            sb_lo.append(base)
+            base += len(p.strings)
+        else:
+            sb_lo.append(base)
+        sb_hi.append(end)
+        tapes.append(t)
+        toffs.append(toffs[-1] + len(t))
+    tape = np.concatenate(tapes) if tapes else np.zeros(1, dtype=np.uint64)
+    sb = np.frombuffer(b"".join(sbs) + b"\0" * 8, dtype=np.uint8)
+    n = len(parsed)
+    types = np.full((len(ptrs), n), 0xEE, dtype=np.uint8)
+    values = np.full((len(ptrs), n), 0xEEEEEEEEEEEEEEEE, dtype=np.uint64)
+    toffs, errs = np.array(toffs, dtype=np.uint64), np.array(errs + [0], dtype=np.int32)
+    if guarded:
+        lo, hi = np.array(sb_lo + [0], dtype=np.uint64), np.array(sb_hi + [0], dtype=np.uint64)
+        rc = lib.sim_select_guarded(blob.ctypes.data, poffs.ctypes.data, len(ptrs), tape.ctypes.data, toffs.ctypes.data, errs.ctypes.data,
+                                    sb.ctypes.data, lo.ctypes.data, hi.ctypes.data, n, types.ctypes.data, values.ctypes.data)
+    else:
+        rc = lib.sim_select(blob.ctypes.data, poffs.ctypes.data, len(ptrs), tape.ctypes.data, toffs.ctypes.data, errs.ctypes.data,
+                            sb.ctypes.data, n, types.ctypes.data, values.ctypes.data)
+    assert rc == 0, rc
+    return types, values, sb.tobytes()
+
+
+@pytest.fixture(scope="module")
+def sim():
+    lib = load_sim()
+
+    def run(parsed, pointers, guarded=False):
+        return run_sim(lib, parsed, pointers, guarded)
     run.slice_words = lib.sim_select_slice_words()
     return run
 
