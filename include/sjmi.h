@@ -505,6 +505,42 @@ int sjmi_select_batch_device(sjmi_ctx* ctx, const sjmi_select_plan* plan, const 
                              const void* d_doc_errors, const void* d_string_buffer, uint64_t n_docs, void* d_types, void* d_values,
                              void* stream);
 
+/* ---- exploding one array of every parsed document into rows on the device ----------------------------------------------
+ * JsonValue.arrayIterator (JsonValue.java:143-168) over ONE array per document, with JsonValue.get (:91-107) paths evaluated on
+ * every element: Arrow's list<struct> shape (csrc/explode.hip).  An explode plan is a BASE pointer plus up to
+ * SJMI_SELECT_MAX_PATHS ELEMENT pointers, all RFC 6901 with the token rules, limits (SJMI_SELECT_MAX_STEPS for the base and for
+ * each element pointer; SJMI_SELECT_MAX_NAME_BYTES for the base and for the element pointers together) and SJMI_ERR_ARG cases
+ * of sjmi_select_plan_compile.  Host only: no device, no context.
+ *
+ * For document k the base value is what sjmi_select_batch_device yields for the base pointer.  If it is an array ('['), its
+ * elements are those of the iterator chain: from idx + 1 (:149), by Tape.computeNextIndex (Tape.java:86-98), to
+ * getMatchingBraceIndex - 1 (:151) -- never the 24-bit scope count (Tape.getScopeCount, Tape.java:82-84), which saturates.
+ * The document contributes 0 rows when the base is MISSING, a scalar, a string or an object, or when doc_errors[k] != 0 (its
+ * tape slot is never read).  Row r = row_offsets[k] + j belongs to element j; cell (r, p) is element pointer p evaluated with
+ * the element as the root ("" = the element itself, "/a/0" = get("a") then element 0), i.e. what sjmi_select_batch_device gives
+ * document k for the pointer base + "/" + j + p, in the same (type, value) encoding, container values' tape indexes included. */
+typedef struct sjmi_explode_plan sjmi_explode_plan;
+int sjmi_explode_plan_compile(const uint8_t* base_pointer, uint64_t base_len, const uint8_t* pointers, const uint64_t* pointer_offsets,
+                              uint64_t n_paths, sjmi_explode_plan** out);
+void sjmi_explode_plan_destroy(sjmi_explode_plan* plan);
+/* Inputs as sjmi_select_batch_device.  d_row_offsets (uint64[n_docs + 1]) is the exclusive prefix sum of the documents' row
+ * counts and is ALWAYS complete: d_row_offsets[n_docs] is the total number of rows, whatever row_capacity is.  Columns are
+ * strided by row_capacity: d_types[p * row_capacity + r] (uint8), d_values[p * row_capacity + r] (uint64).  Rows r >=
+ * row_capacity are not written and nothing past the n_paths * row_capacity elements is touched: a caller sees the overflow
+ * from d_row_offsets[n_docs].  row_capacity == 0 with NULL d_types / d_values is legal and writes the offsets only, so that a
+ * caller can size its columns.  Asynchronous on `stream` (NULL = the context's), no host synchronisation, nothing queued but
+ * the kernels -- except that the first call with a plan copies it to the context's device memory (one blocking upload; the
+ * context keeps the explode plan in a slot of its own, so alternating select and explode calls do not evict each other's
+ * plan), and that a call with more documents than any explode call before it on this context grows the context's
+ * per-document scratch (row counts, base tape indexes, chunk sums), which waits for the device and may block.
+ * That scratch is one per context: explode calls on ONE context must be ordered with respect to each other (the same stream, or
+ * streams the caller orders with events); two of them running at the same time would share it.  Use a context per stream otherwise.
+ * A document whose rows begin below row_capacity and run past it is walked only as far as its rows are stored.
+ * One group of sixteen lanes walks all elements of its document: one very wide array among small ones serialises (4.9). */
+int sjmi_explode_batch_device(sjmi_ctx* ctx, const sjmi_explode_plan* plan, const void* d_tape, const void* d_tape_offsets,
+                              const void* d_doc_errors, const void* d_string_buffer, uint64_t n_docs, void* d_row_offsets,
+                              uint64_t row_capacity, void* d_types, void* d_values, void* stream);
+
 /* Optional: page-lock caller-owned host memory that is passed to the host-buffer entry points again and again
  * (SimdJsonParser's padded input, index array and string buffer): H2D / D2H copies of pinned memory skip the
  * driver's staging copy (3-4x faster for the ~1 MB transfers of a single-document parse).  Purely a performance

@@ -70,6 +70,16 @@ final class Sjmi {
     // int sjmi_select_batch_device(ctx, plan, d_tape, d_tape_offsets, d_doc_errors, d_string_buffer, uint64_t n_docs, d_types, d_values, stream)
     static final MethodHandle SELECT_BATCH_DEVICE = h("sjmi_select_batch_device",
             FunctionDescriptor.of(JAVA_INT, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS, JAVA_LONG, ADDRESS, ADDRESS, ADDRESS));
+    // int sjmi_explode_plan_compile(const uint8_t* base_pointer, uint64_t base_len, const uint8_t* pointers, const uint64_t* pointer_offsets,
+    //                               uint64_t n_paths, sjmi_explode_plan** out)
+    static final MethodHandle EXPLODE_PLAN_COMPILE = h("sjmi_explode_plan_compile",
+            FunctionDescriptor.of(JAVA_INT, ADDRESS, JAVA_LONG, ADDRESS, ADDRESS, JAVA_LONG, ADDRESS));
+    // void sjmi_explode_plan_destroy(sjmi_explode_plan* plan)
+    static final MethodHandle EXPLODE_PLAN_DESTROY = h("sjmi_explode_plan_destroy", FunctionDescriptor.ofVoid(ADDRESS));
+    // int sjmi_explode_batch_device(ctx, plan, d_tape, d_tape_offsets, d_doc_errors, d_string_buffer, uint64_t n_docs, d_row_offsets,
+    //                               uint64_t row_capacity, d_types, d_values, stream)
+    static final MethodHandle EXPLODE_BATCH_DEVICE = h("sjmi_explode_batch_device",
+            FunctionDescriptor.of(JAVA_INT, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS, JAVA_LONG, ADDRESS, JAVA_LONG, ADDRESS, ADDRESS, ADDRESS));
     // const char* sjmi_last_error(const sjmi_ctx* ctx)
     static final MethodHandle LAST_ERROR = critical("sjmi_last_error", FunctionDescriptor.of(ADDRESS, ADDRESS));
 

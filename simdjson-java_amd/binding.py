@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_HERE)
 _CSRC = os.path.join(_HERE, "csrc")
 _LIB = os.path.join(_HERE, "libsjmi.so")
-SOURCES = ["stage1.hip", "strings.hip", "batch.hip", "walk.hip", "coop_walk.hip", "masks.hip", "select.hip", "sjmi_api.hip", "host/simdjson_parser.cpp"]
+SOURCES = ["stage1.hip", "strings.hip", "batch.hip", "walk.hip", "coop_walk.hip", "masks.hip", "select.hip", "explode.hip", "sjmi_api.hip", "host/simdjson_parser.cpp"]
 
 ST_UTF8, ST_UNCLOSED, ST_UNESCAPED, ST_CAPACITY, ST_INTERNAL = 1, 2, 4, 0x100, 0x200
 PADDING = 64
@@ -106,7 +106,8 @@ EXPORTS = ["sjmi_create", "sjmi_destroy", "sjmi_last_error", "sjmi_version", "sj
            "sjmi_od_get_string", "sjmi_od_get_field_name", "sjmi_od_start_array", "sjmi_od_next_array_element",
            "sjmi_od_start_object", "sjmi_od_next_object_field", "sjmi_od_move_to_field_value", "sjmi_od_assert_no_more_values",
            "sjmi_od_depth", "sjmi_od_peek",
-           "sjmi_select_plan_compile", "sjmi_select_plan_destroy", "sjmi_select_batch_device"]
+           "sjmi_select_plan_compile", "sjmi_select_plan_destroy", "sjmi_select_batch_device",
+           "sjmi_explode_plan_compile", "sjmi_explode_plan_destroy", "sjmi_explode_batch_device"]
 
 
 # Handles that are still open when the interpreter exits are closed HERE, in an atexit hook -- i.e. while the HIP runtime
@@ -257,6 +258,13 @@ def lib():
         L.sjmi_select_plan_compile.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p)]
         L.sjmi_select_plan_destroy.restype = None
         L.sjmi_select_plan_destroy.argtypes = [C.c_void_p]
+        L.sjmi_explode_plan_compile.restype = C.c_int
+        L.sjmi_explode_plan_compile.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p)]
+        L.sjmi_explode_plan_destroy.restype = None
+        L.sjmi_explode_plan_destroy.argtypes = [C.c_void_p]
+        L.sjmi_explode_batch_device.restype = C.c_int
+        L.sjmi_explode_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
+                                                C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
         L.sjmi_select_batch_device.restype = C.c_int
         L.sjmi_select_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
                                                C.c_void_p, C.c_void_p, C.c_void_p]
@@ -481,6 +489,14 @@ class Context:
         self._check(lib().sjmi_select_batch_device(self._h, plan._h, d_tape, d_tape_offsets, d_doc_errors, d_sb, n_docs, d_types,
                                                    d_values, stream), "sjmi_select_batch_device")
 
+    def explode_batch_device(self, plan, d_tape, d_tape_offsets, d_doc_errors, d_sb, n_docs, d_row_offsets, row_capacity, d_types,
+                             d_values, stream=0):
+        """sjmi_explode_batch_device: the base array of `plan` (an ExplodePlan) of every document of a parsed batch as rows;
+        d_row_offsets (uint64, n_docs + 1 entries) is always complete, d_types (uint8) / d_values (uint64) are path-major
+        columns strided by row_capacity (both None / 0 with row_capacity 0: the offsets only).  Asynchronous on `stream`."""
+        self._check(lib().sjmi_explode_batch_device(self._h, plan._h, d_tape, d_tape_offsets, d_doc_errors, d_sb, n_docs, d_row_offsets,
+                                                    row_capacity, d_types or None, d_values or None, stream), "sjmi_explode_batch_device")
+
     def stage1_batch_device(self, d_buf, total_len, d_doc_offsets, n_docs, d_indexes, index_capacity, d_index_offsets,
                             d_result, stream=0):
         self._check(lib().sjmi_stage1_batch_device(self._h, d_buf, total_len, d_doc_offsets, n_docs, d_indexes,
@@ -555,6 +571,40 @@ class SelectPlan:
     def close(self):
         if self._h:
             lib().sjmi_select_plan_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class ExplodePlan:
+    """sjmi_explode_plan: a base pointer and a set of element pointers (RFC 6901, str or bytes) compiled once, on the host (no
+    device needed), for Context.explode_batch_device / BatchShard.explode.  Raises ValueError for a malformed pointer or an
+    exceeded limit (include/sjmi.h: SJMI_SELECT_MAX_*)."""
+
+    MISSING = 0
+
+    def __init__(self, base, pointers):
+        self.base = base.encode("utf-8") if isinstance(base, str) else bytes(base)
+        self.pointers = [p.encode("utf-8") if isinstance(p, str) else bytes(p) for p in pointers]
+        self.n_paths = len(self.pointers)
+        base_blob = np.frombuffer(self.base + b"\0", dtype=np.uint8)
+        blob = np.frombuffer(b"".join(self.pointers) + b"\0", dtype=np.uint8)
+        offs = np.zeros(self.n_paths + 1, dtype=np.uint64)
+        offs[1:] = np.cumsum([len(p) for p in self.pointers], dtype=np.uint64)
+        self._h = C.c_void_p()
+        rc = lib().sjmi_explode_plan_compile(base_blob.ctypes.data, len(self.base), blob.ctypes.data, offs.ctypes.data, self.n_paths,
+                                             C.byref(self._h))
+        if rc != 0:
+            self._h = C.c_void_p()
+            raise ValueError("sjmi_explode_plan_compile failed (rc=%d): a malformed JSON Pointer or a plan limit exceeded" % rc)
+
+    def close(self):
+        if self._h:
+            lib().sjmi_explode_plan_destroy(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):

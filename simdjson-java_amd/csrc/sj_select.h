@@ -9,8 +9,8 @@
 //   g.stride_first() / g.stride()  -- the lane's first element and the step of a cooperative copy
 //   g.fence()                      -- orders the group's slice / scratch accesses
 //   g.ballot(f)                    -- f(lane) for every lane of the group -> bit j = what lane j returned
-// csrc/select.hip gives the 16-lane form (four groups to a wave), tests/host_sim/sel_sim.cpp the sequential one: this file is
-// compiled verbatim by both, so the CPU suite checks the walk the kernel runs.
+// csrc/select.hip and csrc/explode.hip give the 16-lane form (four groups to a wave), tests/host_sim/sel_sim.cpp and
+// explode_sim.cpp the sequential one: this file is compiled verbatim by all of them, so the CPU suite checks the walk the kernels run.
 //
 // The chain is walked serially, so whether a tape word is a header or the raw second word of an 'l' / 'd' entry is never a
 // question: only words AT chain positions are read as headers (an int64 of 0x5B00000000000005 is a payload, not '[').
@@ -194,9 +194,9 @@ SJ_HD uint32_t sel_match_round(G& g, const SelHeader* plan, const SelDoc& d, Sel
     return hits;
 }
 
-// Every path of the plan on one document.  s.types / s.values of the group must be zero (MISSING) on entry.
+// The document's tape, staged in the group's slice when it fits (a larger one is walked in global memory by the same code).
 template <class G>
-SJ_HD void sel_document(G& g, const SelHeader* plan, const sj_u64* tape, uint32_t n_words, const uint8_t* sb, SelScratch& s) {
+SJ_HD SelDoc sel_stage(G& g, const sj_u64* tape, uint32_t n_words, const uint8_t* sb, SelScratch& s) {
     SelDoc d;
     d.tape = tape;
     d.n = n_words;
@@ -221,7 +221,20 @@ SJ_HD void sel_document(G& g, const SelHeader* plan, const sj_u64* tape, uint32_
         }
         g.fence();
     }
-    if (n_words < 2) return;
+    return d;
+}
+
+// what enumerating the container at tape index v covers: [v + 1, the closing word) -- Tape.getMatchingBraceIndex :78-80, kept
+// inside the document whatever the word holds
+SJ_HD uint32_t sel_container_end(const SelDoc& d, sj_u64 w, uint32_t v) {
+    const uint32_t match = (uint32_t)w;
+    return match > v + 1 && match - 1 <= d.n ? match - 1 : v + 1;
+}
+
+// Every path of the plan with the value at tape index v as the root (v = 1: the document's root value).  s.types / s.values of
+// the group must be zero (MISSING) on entry.
+template <class G>
+SJ_HD void sel_walk(G& g, const SelHeader* plan, const SelDoc& d, SelScratch& s, uint32_t v0) {
     const SelNode* nodes = sel_nodes(plan);
     int level = -1;
     // the value at tape index v belongs to `node`: its result, and a frame if paths go on through it
@@ -234,8 +247,7 @@ SJ_HD void sel_document(G& g, const SelHeader* plan, const sj_u64* tape, uint32_
         SelFrame& f = s.frames[++level];
         f.node = ni;
         f.pos = v + 1;
-        const uint32_t match = (uint32_t)w;  // Tape.getMatchingBraceIndex :78-80
-        f.end = match > v + 1 && match - 1 <= d.n ? match - 1 : v + 1;
+        f.end = sel_container_end(d, w, v);
         f.k = sel_type(w) == '[' ? 0 : SEL_NO_INDEX;
         f.found = 0;
         if (sel_type(w) == '[')
@@ -243,7 +255,7 @@ SJ_HD void sel_document(G& g, const SelHeader* plan, const sj_u64* tape, uint32_
                 if (nodes[node.first_child + c].index == SEL_NO_INDEX) f.found |= 1ull << c;
         return true;
     };
-    enter(0, 1);
+    enter(0, v0);
     while (level >= 0) {
         SelFrame& f = s.frames[level];
         const SelNode& node = nodes[f.node];
@@ -280,6 +292,54 @@ SJ_HD void sel_document(G& g, const SelHeader* plan, const sj_u64* tape, uint32_
                     break;  // (sibling tokens differ: one child per index)
                 }
         }
+    }
+}
+
+// Every path of the plan on one document.  s.types / s.values of the group must be zero (MISSING) on entry.
+template <class G>
+SJ_HD void sel_document(G& g, const SelHeader* plan, const sj_u64* tape, uint32_t n_words, const uint8_t* sb, SelScratch& s) {
+    const SelDoc d = sel_stage(g, tape, n_words, sb, s);
+    if (n_words < 2) return;
+    sel_walk(g, plan, d, s, 1);
+}
+
+// ---- explode (csrc/explode.hip): one array per document becomes rows, an element plan is walked on every
+// element.  The array is the value of a BASE pointer, compiled as a plan of one path.
+// The staged document's base array: its elements by the iterator chain (JsonValue.arrayIterator :143-168 -- from idx + 1, by
+// Tape.computeNextIndex, to getMatchingBraceIndex - 1), never by the 24-bit scope count, which saturates.
+// -> the number of elements; *base = the array's tape index, 0 when the base is MISSING or no array (then no elements).
+// s.types[0] / s.values[0] must be zero on entry.
+template <class G>
+SJ_HD uint32_t sel_explode_count(G& g, const SelHeader* base_plan, const SelDoc& d, SelScratch& s, uint32_t* base) {
+    *base = 0;
+    if (d.n < 2) return 0;
+    sel_walk(g, base_plan, d, s, 1);
+    if (s.types[0] != '[') return 0;
+    const uint32_t v = (uint32_t)s.values[0];
+    *base = v;
+    const uint32_t end = sel_container_end(d, sel_word(d, s, v), v);
+    uint32_t n = 0;
+    for (uint32_t pos = v + 1; pos < end; pos = sel_next(d, s, pos, end)) ++n;
+    return n;
+}
+
+// Every path of the element plan on the first `limit` elements of the array at tape index `base` of the staged document (the
+// elements whose rows fit the caller's columns: the others are not walked): for element j, row(j) is called with the element's
+// results in s.types / s.values (sel_emit's form: sel_finish is the caller's, when it stores the row).  row() runs in every
+// lane of the group and may use the group's primitives.
+template <class G, class Row>
+SJ_HD void sel_explode_rows(G& g, const SelHeader* plan, const SelDoc& d, SelScratch& s, uint32_t base, uint32_t limit, Row row) {
+    const uint32_t end = sel_container_end(d, sel_word(d, s, base), base);
+    uint32_t j = 0;
+    for (uint32_t pos = base + 1; pos < end && j < limit; pos = sel_next(d, s, pos, end), ++j) {
+        for (uint32_t p = g.stride_first(); p < plan->n_paths; p += g.stride()) {  // MISSING until the walk says otherwise
+            s.types[p] = 0;
+            s.values[p] = 0;
+        }
+        g.fence();
+        sel_walk(g, plan, d, s, pos);
+        g.fence();
+        row(j);
     }
 }
 

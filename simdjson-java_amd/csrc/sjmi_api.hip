@@ -116,6 +116,9 @@ struct sjmi_ctx {
     size_t events_used = 0;
     DevBuf<void> d_plan;                     // sjmi_select_batch_device: the plan the last call used, as k_select reads it
     uint64_t plan_serial = 0;                // ... and which one it is (0: none)
+    DevBuf<void> d_explode_plan;             // sjmi_explode_batch_device: a plan slot of its own (select and explode calls alternate)
+    uint64_t explode_serial = 0;
+    DevBuf<void> d_ws_explode;               // ... and its per-document scratch: row counts, base tape indexes, chunk sums
     std::string err;
 };
 
@@ -923,6 +926,41 @@ int sjmi_select_batch_device(sjmi_ctx* c, const sjmi_select_plan* plan, const vo
     if (!n_paths) return SJMI_OK;
     return fail(c, "select launch", sjmi::select_launch(c->d_plan, bytes, d_tape, d_tape_offsets, d_doc_errors, d_string_buffer, n_docs,
                                                         d_types, d_values, st))
+               ? SJMI_ERR_HIP
+               : SJMI_OK;
+}
+
+int sjmi_explode_batch_device(sjmi_ctx* c, const sjmi_explode_plan* plan, const void* d_tape, const void* d_tape_offsets,
+                              const void* d_doc_errors, const void* d_string_buffer, uint64_t n_docs, void* d_row_offsets,
+                              uint64_t row_capacity, void* d_types, void* d_values, void* stream) {
+    if (!c || !plan || !d_row_offsets) return SJMI_ERR_ARG;
+    size_t bytes, base_bytes;
+    uint64_t serial;
+    uint32_t n_paths;
+    const void* image = sjmi::explode_plan_image(plan, &bytes, &base_bytes, &serial, &n_paths);
+    if (n_docs && (!d_tape || !d_tape_offsets || !d_doc_errors || !d_string_buffer)) return SJMI_ERR_ARG;
+    if (row_capacity && n_paths && (!d_types || !d_values)) return SJMI_ERR_ARG;
+    if (n_paths && row_capacity > ~0ull / 8 / n_paths) return SJMI_ERR_ARG;
+    if (fail(c, "hipSetDevice", hipSetDevice(c->device))) return SJMI_ERR_HIP;
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    if (c->explode_serial != serial) {
+        // another plan than the one on the device: a launch of the old one may still be reading it
+        c->explode_serial = 0;
+        if (c->d_explode_plan.p && fail(c, "sync", hipDeviceSynchronize())) return SJMI_ERR_HIP;
+        if (!grow(c, c->d_explode_plan, bytes, "hipMalloc(explode plan)") ||
+            fail(c, "H2D(explode plan)", hipMemcpy(c->d_explode_plan, image, bytes, hipMemcpyHostToDevice)))
+            return SJMI_ERR_HIP;
+        c->explode_serial = serial;
+    }
+    const size_t ws = sjmi::explode_workspace_bytes(n_docs);
+    if (ws > c->d_ws_explode.bytes) {
+        // the scratch grows: a launch of an earlier call may still be using the old one
+        if (c->d_ws_explode.p && fail(c, "sync", hipDeviceSynchronize())) return SJMI_ERR_HIP;
+        if (!grow(c, c->d_ws_explode, ws, "hipMalloc(ws_explode)")) return SJMI_ERR_HIP;
+    }
+    return fail(c, "explode launch", sjmi::explode_launch(c->d_explode_plan, bytes, base_bytes, n_paths, d_tape, d_tape_offsets, d_doc_errors,
+                                                          d_string_buffer, n_docs, c->d_ws_explode, d_row_offsets, row_capacity, d_types,
+                                                          d_values, st))
                ? SJMI_ERR_HIP
                : SJMI_OK;
 }

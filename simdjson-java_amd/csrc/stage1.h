@@ -377,4 +377,16 @@ const void* select_plan_image(const sjmi_select_plan* plan, size_t* bytes, uint6
 hipError_t select_launch(const void* d_plan, size_t plan_bytes, const void* d_tape, const void* d_tape_offsets, const void* d_doc_errors,
                          const void* d_string_buffer, uint64_t n_docs, void* d_types, void* d_values, hipStream_t stream);
 
+// ---- explode (explode.hip) ----
+// a compiled plan as the kernels read it: [the base pointer as a plan of one path: base_bytes][the element plan], the plan's
+// serial number and the paths of the element plan
+const void* explode_plan_image(const sjmi_explode_plan* plan, size_t* bytes, size_t* base_bytes, uint64_t* serial, uint32_t* n_paths);
+// per-document scratch of one call: row counts, base tape indexes, the scan's chunk sums
+size_t explode_workspace_bytes(uint64_t n_docs);
+// k_explode_count, the scan into d_row_offsets[n_docs + 1], and (row_capacity != 0, n_paths != 0) k_explode_rows into the columns
+// types[p * row_capacity + r] / values[p * row_capacity + r]
+hipError_t explode_launch(const void* d_plan, size_t plan_bytes, size_t base_bytes, uint32_t n_paths, const void* d_tape,
+                          const void* d_tape_offsets, const void* d_doc_errors, const void* d_string_buffer, uint64_t n_docs, void* d_ws,
+                          void* d_row_offsets, uint64_t row_capacity, void* d_types, void* d_values, hipStream_t stream);
+
 }  // namespace sjmi

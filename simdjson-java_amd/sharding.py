@@ -104,6 +104,7 @@ class BatchShard:
                 else self.engine.parse_batch_device_optimistic
         self._last_stream = stream
         self._sel_pending = None  # (a select queued behind an earlier step does not belong to this one)
+        self._exp_pending = None
         fn(self.buf.data_ptr(), self.n, self.offs.data_ptr(), self.n_docs, self.idx.data_ptr(),
                                        self.index_capacity, self.index_offsets.data_ptr(), self.doc_status.data_ptr(),
                                        self.sb.data_ptr(), self.sb_capacity, self.doc_string_offsets.data_ptr(), self.max_depth,
@@ -129,6 +130,28 @@ class BatchShard:
                                         self.sb.data_ptr(), self.n_docs, self.sel_types.data_ptr(), self.sel_values.data_ptr(), stream)
         return self.sel_types, self.sel_values
 
+    def explode(self, plan, row_capacity, stream=0):
+        """The base array of `plan` (a binding.ExplodePlan) of every document of the shard as rows, every element pointer on
+        every element: sjmi_explode_batch_device, queued on `stream` behind the step() that was queued there -- no host
+        synchronisation.  -> (exp_row_offsets [n_docs + 1] int64, exp_types [n_paths, row_capacity] uint8, exp_values
+        [n_paths, row_capacity] int64), allocated once per (plan, row_capacity) and overwritten by every call.  The offsets
+        are always complete (exp_row_offsets[n_docs] = the total number of rows); rows at or behind row_capacity are not
+        written.  row_capacity 0: the offsets only (the columns are empty).  As for select(), the outputs are valid only for
+        a step check() has accepted, and check() queues the explode again behind a step it had to run again."""
+        import torch
+        row_capacity = int(row_capacity)
+        if getattr(self, "_exp_plan", None) is not plan or getattr(self, "_exp_capacity", None) != row_capacity:
+            self.exp_row_offsets = torch.zeros(self.n_docs + 1, dtype=torch.int64, device=self.device)
+            self.exp_types = torch.zeros((plan.n_paths, row_capacity), dtype=torch.uint8, device=self.device)
+            self.exp_values = torch.zeros((plan.n_paths, row_capacity), dtype=torch.int64, device=self.device)
+            self._exp_plan, self._exp_capacity = plan, row_capacity
+        self._exp_pending = (plan, row_capacity, stream)
+        cells = plan.n_paths * row_capacity
+        self.engine.explode_batch_device(plan, self.tape.data_ptr(), self.tape_offsets.data_ptr(), self.doc_errors.data_ptr(),
+                                         self.sb.data_ptr(), self.n_docs, self.exp_row_offsets.data_ptr(), row_capacity,
+                                         self.exp_types.data_ptr() if cells else 0, self.exp_values.data_ptr() if cells else 0, stream)
+        return self.exp_row_offsets, self.exp_types, self.exp_values
+
     def counts_tensor(self):
         """The per-shard row of the count gather, on the device, without a host copy:
         {documents, structurals, string bytes, failed + handed-back documents}."""
@@ -143,6 +166,7 @@ class BatchShard:
         if st1 & 0x800:  # SJMI_ST_REJECTED: not a batch for the optimistic pipeline -- the exact call, here, off the hot path
             import torch
             pending = getattr(self, "_sel_pending", None)
+            exp_pending = getattr(self, "_exp_pending", None)
             self.rejected_steps = getattr(self, "rejected_steps", 0) + 1
             if not (st1 & 0xFF):
                 self.format_rejected = True  # (a clean stage-1 verdict and still rejected: the separators)
@@ -152,6 +176,8 @@ class BatchShard:
                 self.step(getattr(self, "_last_stream", 0), **entry)
                 if pending is not None:  # the select that was queued behind the rejected step read outputs that were not valid
                     self.select(*pending)
+                if exp_pending is not None:  # ... and so did the explode
+                    self.explode(*exp_pending)
                 if str(self.device) != "cpu":  # (the CPU tests' stub engines are synchronous)
                     torch.cuda.synchronize(self.device)
                 r = self.result.cpu().numpy()
