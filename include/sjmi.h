@@ -228,6 +228,40 @@ int sjmi_stage1_batch(sjmi_ctx* ctx, const uint8_t* buf, uint64_t total_len, con
                       uint32_t* indexes, uint64_t index_capacity, uint64_t* index_offsets, uint64_t* count,
                       uint32_t* status);
 
+/* ---- doc_offsets of a buffer of newline-delimited JSON, made on the device (csrc/ndjson.hip) --------------
+ * NL is 0x0A; BLANK is 0x20, 0x09 and 0x0D and nothing else ('\f', '\v', NUL and a BOM are content).  A LINE is a maximal run
+ * of non-NL bytes plus the NL that ends it; the TAIL, the bytes behind the last NL, is never a line and never a document;
+ * consumed = the index behind the last NL (0 without one).  A line is blank when every byte before its NL is BLANK (empty lines,
+ * "\r\n" lines); n_docs = the lines that are not.  With s_0 < s_1 < ... the start offsets of those lines: doc_offsets[0] = 0,
+ * doc_offsets[k] = s_k for k >= 1, doc_offsets[n_docs] = consumed -- blank lines are trailing whitespace of the document in
+ * front of them, leading ones leading whitespace of document 0, so the documents cover [0, consumed) exactly and each ends in
+ * '\n': what sjmi_parse_batch_device_optimistic accepts.  With n_docs == 0 only doc_offsets[0] = 0 is written.  A raw NL inside
+ * a string is illegal JSON: it splits the document into two malformed ones, as in every NDJSON reader.
+ * d_buf may have ANY alignment and len any value, 0 included; SJMI_PADDING bytes behind len are readable (vector loads reach
+ * into them; they never influence the result), and so are the bytes between d_buf and the 16-byte boundary below it (the same
+ * allocation).  d_doc_offsets: offset_capacity uint64; d_result: a device sjmi_ndjson_result.  n_docs and consumed are ALWAYS
+ * complete; with offset_capacity < n_docs + 1 (SJMI_NDJSON_OVERFLOW) only doc_offsets[0, offset_capacity) are written and nothing
+ * behind them -- offset_capacity == 0 with a NULL d_doc_offsets is legal and is how a caller sizes its array (one read of the
+ * input instead of two).  Asynchronous on `stream` (NULL = the context's), no host synchronisation, nothing queued but the
+ * three kernels -- except that a call with a larger len than any before it on this context grows the context's per-tile scratch,
+ * which waits for the device and may block.  That scratch is one per context: ndjson calls on ONE context must be ordered with
+ * respect to each other (the same stream, or streams the caller orders with events); use a context per stream otherwise.
+ * A caller that streams a large file parses [0, consumed) and carries [consumed, len) to the front of its next chunk; at the end
+ * of the file it appends one '\n' if the last byte is not one (this call does not; the Python helper parse_ndjson does). */
+#define SJMI_NDJSON_TAIL_BLANK 1u  /* every byte of [consumed, len) is BLANK (an empty tail included) */
+#define SJMI_NDJSON_OVERFLOW   2u  /* offset_capacity < n_docs + 1 */
+typedef struct sjmi_ndjson_result {
+    uint64_t n_docs, consumed;
+    uint32_t flags, reserved;
+} sjmi_ndjson_result;
+int sjmi_ndjson_offsets_device(sjmi_ctx* ctx, const void* d_buf, uint64_t len, void* d_doc_offsets, uint64_t offset_capacity,
+                               void* d_result, void* stream);
+/* Host form: copies buf[0, len) in (len <= the context's capacity), runs the device form, returns doc_offsets[0, min(n_docs + 1,
+ * offset_capacity)), *n_docs, *consumed and *flags. */
+int sjmi_ndjson_offsets(sjmi_ctx* ctx, const uint8_t* buf, uint64_t len, uint64_t* doc_offsets, uint64_t offset_capacity,
+                        uint64_t* n_docs, uint64_t* consumed, uint32_t* flags);
+uint64_t sjmi_ndjson_tile_bytes(void); /* the kernels' tile; tests place their edge cases by it */
+
 /* ISOLATED batch: exact per document whatever the other documents contain.  One wave per document, every carry
  * (in-string parity, escape run, previous scalar, UTF-8 continuation) starts from zero at the document's first byte.
  * doc_status[k] = the SJMI_ST_* bits document k would get from sjmi_stage1 on its own; a document with a non-zero

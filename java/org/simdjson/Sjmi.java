@@ -80,6 +80,13 @@ final class Sjmi {
     //                               uint64_t row_capacity, d_types, d_values, stream)
     static final MethodHandle EXPLODE_BATCH_DEVICE = h("sjmi_explode_batch_device",
             FunctionDescriptor.of(JAVA_INT, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS, JAVA_LONG, ADDRESS, JAVA_LONG, ADDRESS, ADDRESS, ADDRESS));
+    // int sjmi_ndjson_offsets_device(ctx, d_buf, uint64_t len, d_doc_offsets, uint64_t offset_capacity, d_result, stream)
+    static final MethodHandle NDJSON_OFFSETS_DEVICE = h("sjmi_ndjson_offsets_device",
+            FunctionDescriptor.of(JAVA_INT, ADDRESS, ADDRESS, JAVA_LONG, ADDRESS, JAVA_LONG, ADDRESS, ADDRESS));
+    // int sjmi_ndjson_offsets(ctx, const uint8_t* buf, uint64_t len, uint64_t* doc_offsets, uint64_t offset_capacity, uint64_t* n_docs,
+    //                         uint64_t* consumed, uint32_t* flags)
+    static final MethodHandle NDJSON_OFFSETS = h("sjmi_ndjson_offsets",
+            FunctionDescriptor.of(JAVA_INT, ADDRESS, ADDRESS, JAVA_LONG, ADDRESS, JAVA_LONG, ADDRESS, ADDRESS, ADDRESS));
     // const char* sjmi_last_error(const sjmi_ctx* ctx)
     static final MethodHandle LAST_ERROR = critical("sjmi_last_error", FunctionDescriptor.of(ADDRESS, ADDRESS));
 

@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_HERE)
 _CSRC = os.path.join(_HERE, "csrc")
 _LIB = os.path.join(_HERE, "libsjmi.so")
-SOURCES = ["stage1.hip", "strings.hip", "batch.hip", "walk.hip", "coop_walk.hip", "masks.hip", "select.hip", "explode.hip", "sjmi_api.hip", "host/simdjson_parser.cpp"]
+SOURCES = ["stage1.hip", "strings.hip", "batch.hip", "walk.hip", "coop_walk.hip", "masks.hip", "select.hip", "explode.hip", "ndjson.hip", "sjmi_api.hip", "host/simdjson_parser.cpp"]
 
 ST_UTF8, ST_UNCLOSED, ST_UNESCAPED, ST_CAPACITY, ST_INTERNAL = 1, 2, 4, 0x100, 0x200
 PADDING = 64
@@ -107,7 +107,8 @@ EXPORTS = ["sjmi_create", "sjmi_destroy", "sjmi_last_error", "sjmi_version", "sj
            "sjmi_od_start_object", "sjmi_od_next_object_field", "sjmi_od_move_to_field_value", "sjmi_od_assert_no_more_values",
            "sjmi_od_depth", "sjmi_od_peek",
            "sjmi_select_plan_compile", "sjmi_select_plan_destroy", "sjmi_select_batch_device",
-           "sjmi_explode_plan_compile", "sjmi_explode_plan_destroy", "sjmi_explode_batch_device"]
+           "sjmi_explode_plan_compile", "sjmi_explode_plan_destroy", "sjmi_explode_batch_device",
+           "sjmi_ndjson_offsets_device", "sjmi_ndjson_offsets", "sjmi_ndjson_tile_bytes"]
 
 
 # Handles that are still open when the interpreter exits are closed HERE, in an atexit hook -- i.e. while the HIP runtime
@@ -265,6 +266,12 @@ def lib():
         L.sjmi_explode_batch_device.restype = C.c_int
         L.sjmi_explode_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
                                                 C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.sjmi_ndjson_offsets_device.restype = C.c_int
+        L.sjmi_ndjson_offsets_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+        L.sjmi_ndjson_offsets.restype = C.c_int
+        L.sjmi_ndjson_offsets.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.sjmi_ndjson_tile_bytes.restype = C.c_uint64
+        L.sjmi_ndjson_tile_bytes.argtypes = []
         L.sjmi_select_batch_device.restype = C.c_int
         L.sjmi_select_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
                                                C.c_void_p, C.c_void_p, C.c_void_p]
@@ -496,6 +503,23 @@ class Context:
         columns strided by row_capacity (both None / 0 with row_capacity 0: the offsets only).  Asynchronous on `stream`."""
         self._check(lib().sjmi_explode_batch_device(self._h, plan._h, d_tape, d_tape_offsets, d_doc_errors, d_sb, n_docs, d_row_offsets,
                                                     row_capacity, d_types or None, d_values or None, stream), "sjmi_explode_batch_device")
+
+    def ndjson_offsets_device(self, d_buf, length, d_doc_offsets, offset_capacity, d_result, stream=0):
+        """sjmi_ndjson_offsets_device: the doc_offsets of a device-resident buffer of newline-delimited JSON (any alignment),
+        d_doc_offsets = offset_capacity uint64 (None / 0 with capacity 0: size only), d_result = device sjmi_ndjson_result
+        (3 x int64: n_docs, consumed, flags in the low half of the third).  Asynchronous on `stream`."""
+        self._check(lib().sjmi_ndjson_offsets_device(self._h, d_buf or None, length, d_doc_offsets or None, offset_capacity, d_result,
+                                                     stream), "sjmi_ndjson_offsets_device")
+
+    def ndjson_offsets(self, data):
+        """sjmi_ndjson_offsets (host form) -> (doc_offsets np.uint64 [n_docs + 1], consumed, flags): the documents are the
+        non-blank lines of data[0, consumed), blank lines absorbed by the document in front of them."""
+        a = np.frombuffer(bytes(data), dtype=np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, np.uint8)
+        offs = np.zeros(a.size // 2 + 1, dtype=np.uint64)
+        n, consumed, flags = C.c_uint64(0), C.c_uint64(0), C.c_uint32(0)
+        self._check(lib().sjmi_ndjson_offsets(self._h, a.ctypes.data if a.size else None, a.size, offs.ctypes.data, offs.size,
+                                              C.addressof(n), C.addressof(consumed), C.addressof(flags)), "sjmi_ndjson_offsets")
+        return offs[:n.value + 1].copy(), consumed.value, flags.value
 
     def stage1_batch_device(self, d_buf, total_len, d_doc_offsets, n_docs, d_indexes, index_capacity, d_index_offsets,
                             d_result, stream=0):
@@ -761,11 +785,15 @@ class SimdJsonParser:
         if rc != 0:
             self._h = C.c_void_p()
             raise SjmiError("sjmi_parser_create failed (rc=%d): no usable MI355X; there is no CPU fallback" % rc)
+        self._device = device
         if gpu_walk is not None:  # stage 2 on the GPU (True) / on the host (False); None: the library's default, by size
             lib().sjmi_parser_set_gpu_walk(self._h, 1 if gpu_walk else 0)
         _live.add(self)
 
     def close(self):
+        if getattr(self, "_ndjson_ctx", None) is not None:  # (parse_ndjson's splitter)
+            self._ndjson_ctx.close()
+            self._ndjson_ctx = None
         if self._h:
             lib().sjmi_parser_destroy(self._h)
             self._h = C.c_void_p()
@@ -825,6 +853,21 @@ class SimdJsonParser:
         if rc < 0:
             raise SjmiError("sjmi_parser_batch_root failed (rc=%d)" % rc)
         return JsonValue(self, v)
+
+    def parse_ndjson(self, data):
+        """A buffer of newline-delimited JSON: one '\\n' is appended if the last byte is not one, the GPU splits it into its
+        documents (sjmi_ndjson_offsets; blank lines belong to the document in front of them), and parse_batch parses them.
+        -> what parse_batch returns."""
+        data = bytes(data)
+        if data and not data.endswith(b"\n"):
+            data += b"\n"
+        ctx = getattr(self, "_ndjson_ctx", None)
+        if ctx is None or ctx.capacity < len(data):
+            if ctx is not None:
+                ctx.close()
+            ctx = self._ndjson_ctx = Context(self._device, max(len(data), 1 << 20))
+        offs, consumed, _ = ctx.ndjson_offsets(data)
+        return self.parse_batch(data[:consumed], offs)
 
     def parse_batch(self, buffer, doc_offsets):
         """-> (list of per-document tapes (np.uint64) or None where errors[k] != 0, shared strings bytes, errors)."""

@@ -119,6 +119,9 @@ struct sjmi_ctx {
     DevBuf<void> d_explode_plan;             // sjmi_explode_batch_device: a plan slot of its own (select and explode calls alternate)
     uint64_t explode_serial = 0;
     DevBuf<void> d_ws_explode;               // ... and its per-document scratch: row counts, base tape indexes, chunk sums
+    DevBuf<void> d_ws_ndjson;                // sjmi_ndjson_offsets_device: a state and a count per tile
+    DevBuf<unsigned long long> d_nd_offsets; // sjmi_ndjson_offsets (host form): the offsets and the result record on the device
+    DevBuf<sjmi_ndjson_result> d_nd_result;
     std::string err;
 };
 
@@ -963,6 +966,53 @@ int sjmi_explode_batch_device(sjmi_ctx* c, const sjmi_explode_plan* plan, const 
                                                           d_values, st))
                ? SJMI_ERR_HIP
                : SJMI_OK;
+}
+
+uint64_t sjmi_ndjson_tile_bytes(void) { return sjmi::ndjson_tile_bytes(); }
+
+int sjmi_ndjson_offsets_device(sjmi_ctx* c, const void* d_buf, uint64_t len, void* d_doc_offsets, uint64_t offset_capacity,
+                               void* d_result, void* stream) {
+    if (!c || !d_result || (len && !d_buf) || (offset_capacity && !d_doc_offsets) || len >= (1ull << 46)) return SJMI_ERR_ARG;
+    if (((uintptr_t)d_doc_offsets & 7) || ((uintptr_t)d_result & 7)) return SJMI_ERR_ARG;
+    if (fail(c, "hipSetDevice", hipSetDevice(c->device))) return SJMI_ERR_HIP;
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    const size_t ws = sjmi::ndjson_workspace_bytes(len);
+    if (ws > c->d_ws_ndjson.bytes) {
+        // the scratch grows: a launch of an earlier call may still be using the old one
+        if (c->d_ws_ndjson.p && fail(c, "sync", hipDeviceSynchronize())) return SJMI_ERR_HIP;
+        if (!grow(c, c->d_ws_ndjson, ws, "hipMalloc(ws_ndjson)")) return SJMI_ERR_HIP;
+    }
+    return fail(c, "ndjson launch", sjmi::ndjson_launch(d_buf, len, d_doc_offsets, offset_capacity, d_result, c->d_ws_ndjson, st))
+               ? SJMI_ERR_HIP
+               : SJMI_OK;
+}
+
+int sjmi_ndjson_offsets(sjmi_ctx* c, const uint8_t* buf, uint64_t len, uint64_t* doc_offsets, uint64_t offset_capacity,
+                        uint64_t* n_docs, uint64_t* consumed, uint32_t* flags) {
+    if (!c || (!buf && len) || (!doc_offsets && offset_capacity) || !n_docs || !consumed || !flags) return SJMI_ERR_ARG;
+    if (too_large(c, len, "buffer")) return SJMI_ERR_CAPACITY;
+    if (fail(c, "hipSetDevice", hipSetDevice(c->device))) return SJMI_ERR_HIP;
+    // a document is at least one byte and its NL: more than len / 2 + 1 entries are never written
+    const uint64_t cap = offset_capacity < len / 2 + 1 ? offset_capacity : len / 2 + 1;
+    if (!grow(c, c->d_nd_offsets, (size_t)(cap ? cap : 1) * sizeof(unsigned long long), "hipMalloc(ndjson offsets)") ||
+        !grow(c, c->d_nd_result, sizeof(sjmi_ndjson_result), "hipMalloc(ndjson result)"))
+        return SJMI_ERR_HIP;
+    c->last_valid = false;  // (the context's input buffer no longer holds the document of the last stage-1 call)
+    c->par_valid = false;
+    c->accept_valid = false;
+    if (len && fail(c, "H2D", hipMemcpyAsync(c->d_in, buf, len, hipMemcpyHostToDevice, c->stream))) return SJMI_ERR_HIP;
+    const int rc = sjmi_ndjson_offsets_device(c, c->d_in, len, cap ? c->d_nd_offsets.p : nullptr, cap, c->d_nd_result, c->stream);
+    if (rc != SJMI_OK) return rc;
+    sjmi_ndjson_result r;
+    if (fail(c, "D2H", hipMemcpyAsync(&r, c->d_nd_result, sizeof r, hipMemcpyDeviceToHost, c->stream)) ||
+        fail(c, "sync", hipStreamSynchronize(c->stream)))
+        return SJMI_ERR_HIP;
+    const uint64_t n = r.n_docs + 1 < cap ? r.n_docs + 1 : cap;
+    if (n && fail(c, "D2H", hipMemcpy(doc_offsets, c->d_nd_offsets, (size_t)n * sizeof(uint64_t), hipMemcpyDeviceToHost))) return SJMI_ERR_HIP;
+    *n_docs = r.n_docs;
+    *consumed = r.consumed;
+    *flags = r.flags;
+    return SJMI_OK;
 }
 
 int sjmi_stage1_device(sjmi_ctx* c, const void* d_buf, uint64_t len, void* d_indexes, uint64_t index_capacity,

@@ -389,4 +389,13 @@ hipError_t explode_launch(const void* d_plan, size_t plan_bytes, size_t base_byt
                           const void* d_tape_offsets, const void* d_doc_errors, const void* d_string_buffer, uint64_t n_docs, void* d_ws,
                           void* d_row_offsets, uint64_t row_capacity, void* d_types, void* d_values, hipStream_t stream);
 
+// ---- NDJSON document offsets (ndjson.hip) ----
+uint64_t ndjson_tile_bytes();
+// per-tile scratch of one call over len bytes: a state and a count per tile
+size_t ndjson_workspace_bytes(uint64_t len);
+// k_ndjson_summary, k_ndjson_scan (the sjmi_ndjson_result at d_result, doc_offsets[0] and [n_docs]) and, with offset_capacity > 1,
+// k_ndjson_emit (doc_offsets[1 ..] below the capacity); d_buf of any alignment
+hipError_t ndjson_launch(const void* d_buf, uint64_t len, void* d_doc_offsets, uint64_t offset_capacity, void* d_result, void* d_ws,
+                         hipStream_t stream);
+
 }  // namespace sjmi

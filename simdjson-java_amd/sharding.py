@@ -52,21 +52,26 @@ class BatchShard:
     a stub with the same parse_batch_device signature); tensors are plain torch tensors on `device`."""
 
     def __init__(self, engine, shard_bytes, local_offsets, device, max_depth=1024, index_ratio=1, string_ratio=1.0,
-                 tape_ratio=1.0):
+                 tape_ratio=1.0, device_offsets=None):
+        """device_offsets: the documents' offsets as an int64 tensor of n_docs + 1 entries that is already on `device` (from_ndjson:
+        they were made there and never leave it); local_offsets is then not looked at.  They must cover the shard exactly."""
         import torch
         self.engine = engine
         self.device = device
         self.n = int(shard_bytes.numel()) if hasattr(shard_bytes, "numel") else len(shard_bytes)
-        offs = np.ascontiguousarray(local_offsets, dtype=np.uint64)
-        assert offs[0] == 0 and int(offs[-1]) == self.n  # (the documents cover the shard exactly: include/sjmi.h, sjmi_parse_batch_device)
-        self.n_docs = offs.size - 1
+        if device_offsets is None:
+            offs = np.ascontiguousarray(local_offsets, dtype=np.uint64)
+            assert offs[0] == 0 and int(offs[-1]) == self.n  # (the documents cover the shard exactly: include/sjmi.h, sjmi_parse_batch_device)
+            self.n_docs = offs.size - 1
+        else:
+            self.n_docs = int(device_offsets.numel()) - 1
         if hasattr(shard_bytes, "numel"):
             self.buf = torch.zeros(self.n + 128, dtype=torch.uint8, device=device)
             self.buf[:self.n] = shard_bytes
         else:
             self.buf = torch.zeros(self.n + 128, dtype=torch.uint8, device=device)
             self.buf[:self.n] = torch.frombuffer(bytearray(shard_bytes), dtype=torch.uint8).to(device)
-        self.offs = torch.from_numpy(offs.view(np.int64).copy()).to(device)
+        self.offs = torch.from_numpy(offs.view(np.int64).copy()).to(device) if device_offsets is None else device_offsets
         # the defaults cover the worst cases (one structural per byte: "[[[[", one tape word per byte: "[1,1,1"); real
         # JSON has one structural per 5-11 bytes, so a caller that knows its data passes tighter ratios (bench.py) -- a
         # shortfall is reported by the kernels (never overrun) and check() raises
@@ -84,6 +89,36 @@ class BatchShard:
         self.result = torch.zeros(9, dtype=torch.int64, device=device)  # sjmi_batch_result
         self.max_depth = max_depth
         self._ndocs = torch.tensor([self.n_docs], dtype=torch.int64, device=device)
+
+    @classmethod
+    def from_ndjson(cls, engine, shard_bytes, device, **kwargs):
+        """A shard from the bytes of a file of newline-delimited JSON (bytes or a uint8 tensor): the bytes are uploaded and split
+        into documents ON the device (sjmi_ndjson_offsets_device; blank lines belong to the document in front of them), the
+        24-byte result record is read back -- the one host synchronisation of the path -- and the shard is built over
+        [0, consumed) with the offsets never leaving the device.  The unterminated tail, if any, is not part of the shard:
+        .ndjson_consumed says where it begins and .ndjson_flags bit 0 (SJMI_NDJSON_TAIL_BLANK) whether it is blank; a caller
+        at the end of its file appends one '\\n' first.  kwargs as for the constructor."""
+        import torch
+        n = int(shard_bytes.numel()) if hasattr(shard_bytes, "numel") else len(shard_bytes)
+        raw = shard_bytes.to(device) if hasattr(shard_bytes, "numel") else \
+            torch.frombuffer(bytearray(shard_bytes) + bytearray(64), dtype=torch.uint8).to(device)
+        if hasattr(shard_bytes, "numel"):
+            raw = torch.cat([raw, torch.zeros(64, dtype=torch.uint8, device=device)])  # (SJMI_PADDING readable bytes)
+        result = torch.zeros(3, dtype=torch.int64, device=device)  # sjmi_ndjson_result
+        offs = torch.empty(n // 2 + 1, dtype=torch.int64, device=device)  # (a document is at least one byte and its NL)
+        stream = torch.cuda.current_stream(device).cuda_stream if str(device) != "cpu" else 0
+        if not stream and str(device) != "cpu":
+            torch.cuda.synchronize(device)  # (handle 0 names the engine's own stream: the upload has to be done before it starts)
+        engine.ndjson_offsets_device(raw.data_ptr(), n, offs.data_ptr(), offs.numel(), result.data_ptr(), stream)
+        if not stream and str(device) != "cpu":
+            torch.cuda.synchronize(device)
+        r = result.cpu().numpy()
+        n_docs, consumed, flags = int(r[0]), int(r[1]), int(r[2]) & 0xFFFFFFFF
+        assert not (flags & 2), "n // 2 + 1 offsets always suffice"
+        # (without a document, blank lines have nothing in front of them to belong to: the shard is empty)
+        shard = cls(engine, raw[:consumed if n_docs else 0], None, device, device_offsets=offs[:n_docs + 1], **kwargs)
+        shard.ndjson_consumed, shard.ndjson_flags = consumed, flags
+        return shard
 
     def step(self, stream=0, exact=False, rejected=False):
         """One step, queued on `stream`.  Default: sjmi_parse_batch_device_optimistic -- only the optimistic pipeline (eight queue

@@ -1,0 +1,59 @@
+// Host simulation of the NDJSON splitter (simdjson-java_amd/csrc/ndjson.hip): sj_ndjson.h, the header the kernels compile
+// verbatim, with the lane primitives in their sequential form (ONE lane: every scan is empty, every total the lane's own value).
+// TEST ONLY: lets the CPU suite check the three passes -- tile summaries, their scan, the emit -- against the reference of
+// tests/ndjson_common.py without a GPU, at any tile size.  Built by tests/test_host_ndjson.py with g++.
+#include <string.h>
+
+#include <vector>
+
+#include "../../simdjson-java_amd/csrc/sj_ndjson.h"
+
+struct SeqLane {
+    uint32_t lanes() const { return 1; }
+    uint32_t lane() const { return 0; }
+    void load(const uint8_t* p, uint32_t w[16]) const { memcpy(w, p, 64); }  // (little-endian host)
+    NdState scan_state(NdState v, NdState* total) const {
+        *total = v;
+        return 0;
+    }
+    sj_u64 scan_add(sj_u64 v, sj_u64* total) const {
+        *total = v;
+        return 0;
+    }
+    bool any(bool flag) const { return flag; }
+};
+
+extern "C" {
+
+uint32_t sim_ndjson_tile_blocks() { return ND_TILE_BLOCKS; }
+
+// buf[0, len) placed `shift` (0..15) bytes behind a 16-byte boundary, with `fill`-patterned bytes in front of it and 64 behind
+// it; tile_bytes a multiple of 64.  offsets holds capacity entries plus whatever canaries the caller put behind them.
+// result = {n_docs, consumed, flags}.  -> 0, or -2 for a bad argument
+int sim_ndjson(const uint8_t* buf, uint64_t len, uint32_t shift, uint32_t tile_bytes, const uint8_t* fill, uint32_t fill_len,
+               uint64_t* offsets, uint64_t capacity, uint64_t* result) {
+    if (shift > 15 || !tile_bytes || tile_bytes % 64 || !fill_len) return -2;
+    std::vector<uint8_t> store(len + 16 + 64 + 16);
+    uint8_t* base = store.data() + ((16 - ((uintptr_t)store.data() & 15)) & 15);
+    for (size_t i = 0; base + i < store.data() + store.size(); ++i) base[i] = fill[i % fill_len];
+    if (len) memcpy(base + shift, buf, len);
+    const SeqLane g;
+    const NdGeom ge = nd_geom(base + shift, len, tile_bytes / 64);
+    const sj_u64 ntiles = nd_tiles(ge);
+    std::vector<NdTile> tiles(ntiles + 1);
+    for (sj_u64 t = 0; t < ntiles; ++t) tiles[t] = nd_tile_summary(g, ge, t);
+    const NdTile all = nd_scan_tiles(g, tiles.data(), ntiles);
+    NdResult res;
+    nd_finish(ge, all, (sj_u64*)offsets, capacity, &res);
+    if (capacity > 1)
+        for (sj_u64 t = 0; t < ntiles; ++t) nd_tile_emit(g, ge, t, tiles[t], (sj_u64*)offsets, capacity);
+    result[0] = res.n_docs;
+    result[1] = res.consumed;
+    result[2] = res.flags;
+    return 0;
+}
+
+// nd_combine over packed states, for the associativity check: state = has_nl << 63 | seen << 62 | pos
+uint64_t sim_nd_combine(uint64_t a, uint64_t b) { return nd_combine(a, b); }
+
+}  // extern "C"
