@@ -153,7 +153,9 @@ int sjmi_stage1_shard_device2(sjmi_ctx* ctx, const void* d_buf, uint64_t len, ui
  * repeated with more of them by the call itself).  sjmi_stream_push: chunk = host bytes, every chunk but the last a non-zero
  * multiple of 64 long; indexes[0..*count] = the chunk's structurals RELATIVE to the chunk (+ the sentinel), *base = the
  * chunk's offset in the stream; *status = the document's verdict so far (SJMI_ST_UNCLOSED only behind the last chunk).
- * The in-string parity is carried from chunk to chunk, so every chunk is scanned exactly once. */
+ * The in-string parity is carried from chunk to chunk, so every chunk is scanned exactly once.
+ * A push that returns SJMI_ERR_ARG or SJMI_ERR_CAPACITY (index_capacity < *count + 1; a backslash run longer than the bytes kept) took
+ * nothing of the chunk and leaves the stream as it was: the same chunk may be pushed again, with a larger array for instance. */
 typedef struct sjmi_stream sjmi_stream;
 int sjmi_stream_open(sjmi_ctx* ctx, uint64_t max_chunk_bytes, uint64_t halo_bytes, sjmi_stream** out);
 int sjmi_stream_push(sjmi_stream* s, const uint8_t* chunk, uint64_t len, int is_last, uint32_t* indexes, uint64_t index_capacity,
