@@ -577,6 +577,48 @@ int sjmi_explode_batch_device(sjmi_ctx* ctx, const sjmi_explode_plan* plan, cons
                               const void* d_doc_errors, const void* d_string_buffer, uint64_t n_docs, void* d_row_offsets,
                               uint64_t row_capacity, void* d_types, void* d_values, void* stream);
 
+/* ---- one string column as Arrow offsets, validity and bytes, gathered on the device -------------------------------------
+ * A string cell of a select or explode column is (length << 32) | offset into the batch's string buffer, which holds every
+ * string of every document with record headers between them.  This call turns ONE such column into Arrow's large_utf8 shape:
+ * int64 offsets, an LSB-first validity bitmap and the strings' bytes back to back (csrc/strcol.hip).  It reads
+ * a finished (types, values) column and the string buffer and nothing else: no tape, no plan.
+ *
+ * INPUT COLUMN.  d_types (uint8, ANY alignment: it is loaded as bytes) and d_values (uint64, 8-byte aligned) are one column of
+ * n_rows cells in the encoding of sjmi_select_batch_device.  A select column is d_types + p * n_docs (and d_values + p *
+ * n_docs) with n_rows = n_docs; an explode column is d_types + p * row_capacity with n_rows = min(total rows, row_capacity).
+ * VALIDITY.  Row r is VALID iff types[r] == '"'; its length is values[r] >> 32 and its bytes are d_string_buffer[values[r] &
+ * 0xFFFFFFFF ...].  Every other row -- MISSING, 'n', numbers, booleans, containers -- is NULL with length 0, and the value word
+ * of a NULL row is never used as an offset or a length (nor read at all), whatever it holds.  n_valid counts the VALID rows;
+ * n_other counts the rows that are neither VALID nor MISSING nor 'n': a schema mismatch the caller sees without a second pass.
+ * OFFSETS.  d_offsets is int64[n_rows + 1], the exclusive prefix sum of the lengths.  It is ALWAYS complete, whatever
+ * byte_capacity is, and d_offsets[n_rows] == total_bytes.
+ * VALIDITY BITMAP.  d_validity is uint64[ceil(n_rows / 64)] (8-byte aligned): bit r & 63 of word r >> 6 is set iff row r is
+ * VALID -- Arrow's LSB-first bitmap on a little-endian host.  Bits at or above n_rows in the last word are 0.  d_validity may
+ * be NULL: nothing is written for it then.
+ * BYTES.  Byte i of the column, offsets[r] <= i < offsets[r + 1], is byte i - offsets[r] of row r.  It is written to d_bytes[i]
+ * iff i < byte_capacity; nothing at or behind d_bytes + byte_capacity is touched.  d_bytes may have any alignment.
+ * byte_capacity == 0 with d_bytes == NULL is the SIZING call: offsets, validity and the result record only, the copy kernel is
+ * not launched.  total_bytes > byte_capacity sets SJMI_STRCOL_OVERFLOW (the sizing call of a column with bytes sets it too).
+ * The bytes are what the string pass wrote: they are not validated again.
+ * THE EMPTY COLUMN.  n_rows == 0 is legal: d_offsets[0] = 0, a zero result record, and no kernel is launched with an empty grid.
+ * ARGUMENTS.  SJMI_ERR_ARG: NULL d_offsets or d_result; NULL d_types or d_values with n_rows > 0; NULL d_bytes with
+ * byte_capacity > 0; d_values, d_offsets, d_validity or d_result not 8-byte aligned; n_rows >= 2^40.
+ * STREAM AND SCRATCH.  Asynchronous on `stream` (NULL = the context's), no host synchronisation, nothing queued but four plain
+ * kernels that the stream orders (chunk sums per 1024 rows, their scan by one workgroup, the offsets, the copy) -- except that
+ * a call with more rows than any string-column call before it on this context grows the context's chunk-sum scratch, which
+ * waits for the device and may block.  That scratch is a slot of its own (not explode's) and one per context: string-column
+ * calls on ONE context must be ordered with respect to each other (the same stream, or streams the caller orders with events).
+ * KNOWN LIMIT.  A wave copies the bytes of its 64 consecutive rows, 64 bytes per trip: one very long string among short ones is
+ * copied by one wave. */
+#define SJMI_STRCOL_OVERFLOW 1u            /* total_bytes > byte_capacity */
+typedef struct sjmi_strcol_result {
+    uint64_t total_bytes, n_valid, n_other;
+    uint32_t flags, reserved;
+} sjmi_strcol_result;
+int sjmi_string_column_device(sjmi_ctx* ctx, const void* d_types, const void* d_values, uint64_t n_rows,
+                              const void* d_string_buffer, void* d_offsets, void* d_validity,
+                              void* d_bytes, uint64_t byte_capacity, void* d_result, void* stream);
+
 /* Optional: page-lock caller-owned host memory that is passed to the host-buffer entry points again and again
  * (SimdJsonParser's padded input, index array and string buffer): H2D / D2H copies of pinned memory skip the
  * driver's staging copy (3-4x faster for the ~1 MB transfers of a single-document parse).  Purely a performance

@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_HERE)
 _CSRC = os.path.join(_HERE, "csrc")
 _LIB = os.path.join(_HERE, "libsjmi.so")
-SOURCES = ["stage1.hip", "strings.hip", "batch.hip", "walk.hip", "coop_walk.hip", "masks.hip", "select.hip", "explode.hip", "ndjson.hip", "sjmi_api.hip", "host/simdjson_parser.cpp"]
+SOURCES = ["stage1.hip", "strings.hip", "batch.hip", "walk.hip", "coop_walk.hip", "masks.hip", "select.hip", "explode.hip", "ndjson.hip", "strcol.hip", "sjmi_api.hip", "host/simdjson_parser.cpp"]
 
 ST_UTF8, ST_UNCLOSED, ST_UNESCAPED, ST_CAPACITY, ST_INTERNAL = 1, 2, 4, 0x100, 0x200
 PADDING = 64
@@ -108,7 +108,7 @@ EXPORTS = ["sjmi_create", "sjmi_destroy", "sjmi_last_error", "sjmi_version", "sj
            "sjmi_od_depth", "sjmi_od_peek",
            "sjmi_select_plan_compile", "sjmi_select_plan_destroy", "sjmi_select_batch_device",
            "sjmi_explode_plan_compile", "sjmi_explode_plan_destroy", "sjmi_explode_batch_device",
-           "sjmi_ndjson_offsets_device", "sjmi_ndjson_offsets", "sjmi_ndjson_tile_bytes"]
+           "sjmi_ndjson_offsets_device", "sjmi_ndjson_offsets", "sjmi_ndjson_tile_bytes", "sjmi_string_column_device"]
 
 
 # Handles that are still open when the interpreter exits are closed HERE, in an atexit hook -- i.e. while the HIP runtime
@@ -272,6 +272,9 @@ def lib():
         L.sjmi_ndjson_offsets.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
         L.sjmi_ndjson_tile_bytes.restype = C.c_uint64
         L.sjmi_ndjson_tile_bytes.argtypes = []
+        L.sjmi_string_column_device.restype = C.c_int
+        L.sjmi_string_column_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
         L.sjmi_select_batch_device.restype = C.c_int
         L.sjmi_select_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
                                                C.c_void_p, C.c_void_p, C.c_void_p]
@@ -510,6 +513,15 @@ class Context:
         (3 x int64: n_docs, consumed, flags in the low half of the third).  Asynchronous on `stream`."""
         self._check(lib().sjmi_ndjson_offsets_device(self._h, d_buf or None, length, d_doc_offsets or None, offset_capacity, d_result,
                                                      stream), "sjmi_ndjson_offsets_device")
+
+    def string_column_device(self, d_types, d_values, n_rows, d_sb, d_offsets, d_validity, d_bytes, byte_capacity, d_result, stream=0):
+        """sjmi_string_column_device: ONE (types, values) column of a select or an explode as Arrow large_utf8 -- d_offsets
+        (int64, n_rows + 1 entries, always complete), d_validity (uint64 words, LSB first; None / 0: not written), d_bytes
+        (byte_capacity bytes; None / 0 with capacity 0: the sizing call), d_result = device sjmi_strcol_result (4 x int64:
+        total_bytes, n_valid, n_other, flags in the low half of the fourth).  Asynchronous on `stream`."""
+        self._check(lib().sjmi_string_column_device(self._h, d_types or None, d_values or None, n_rows, d_sb or None, d_offsets or None,
+                                                    d_validity or None, d_bytes or None, byte_capacity, d_result or None, stream),
+                    "sjmi_string_column_device")
 
     def ndjson_offsets(self, data):
         """sjmi_ndjson_offsets (host form) -> (doc_offsets np.uint64 [n_docs + 1], consumed, flags): the documents are the

@@ -122,6 +122,7 @@ struct sjmi_ctx {
     DevBuf<void> d_ws_ndjson;                // sjmi_ndjson_offsets_device: a state and a count per tile
     DevBuf<unsigned long long> d_nd_offsets; // sjmi_ndjson_offsets (host form): the offsets and the result record on the device
     DevBuf<sjmi_ndjson_result> d_nd_result;
+    DevBuf<void> d_ws_strcol;                // sjmi_string_column_device: three sums per chunk of rows (a slot of its own)
     std::string err;
 };
 
@@ -983,6 +984,25 @@ int sjmi_ndjson_offsets_device(sjmi_ctx* c, const void* d_buf, uint64_t len, voi
         if (!grow(c, c->d_ws_ndjson, ws, "hipMalloc(ws_ndjson)")) return SJMI_ERR_HIP;
     }
     return fail(c, "ndjson launch", sjmi::ndjson_launch(d_buf, len, d_doc_offsets, offset_capacity, d_result, c->d_ws_ndjson, st))
+               ? SJMI_ERR_HIP
+               : SJMI_OK;
+}
+
+int sjmi_string_column_device(sjmi_ctx* c, const void* d_types, const void* d_values, uint64_t n_rows, const void* d_string_buffer,
+                              void* d_offsets, void* d_validity, void* d_bytes, uint64_t byte_capacity, void* d_result, void* stream) {
+    if (!c || !d_offsets || !d_result || (n_rows && (!d_types || !d_values)) || (byte_capacity && !d_bytes)) return SJMI_ERR_ARG;
+    if (((uintptr_t)d_values & 7) || ((uintptr_t)d_offsets & 7) || ((uintptr_t)d_validity & 7) || ((uintptr_t)d_result & 7)) return SJMI_ERR_ARG;
+    if (n_rows >= (1ull << 40)) return SJMI_ERR_ARG;  // (one workgroup per 1024 rows, one wave per 64)
+    if (fail(c, "hipSetDevice", hipSetDevice(c->device))) return SJMI_ERR_HIP;
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    const size_t ws = sjmi::strcol_workspace_bytes(n_rows);
+    if (ws > c->d_ws_strcol.bytes) {
+        // the scratch grows: a launch of an earlier call may still be using the old one
+        if (c->d_ws_strcol.p && fail(c, "sync", hipDeviceSynchronize())) return SJMI_ERR_HIP;
+        if (!grow(c, c->d_ws_strcol, ws, "hipMalloc(ws_strcol)")) return SJMI_ERR_HIP;
+    }
+    return fail(c, "string column launch", sjmi::strcol_launch(d_types, d_values, n_rows, d_string_buffer, d_offsets, d_validity, d_bytes,
+                                                               byte_capacity, d_result, c->d_ws_strcol, st))
                ? SJMI_ERR_HIP
                : SJMI_OK;
 }

@@ -398,4 +398,12 @@ size_t ndjson_workspace_bytes(uint64_t len);
 hipError_t ndjson_launch(const void* d_buf, uint64_t len, void* d_doc_offsets, uint64_t offset_capacity, void* d_result, void* d_ws,
                          hipStream_t stream);
 
+// ---- a string column as Arrow offsets, validity and bytes (strcol.hip) ----
+// scratch of one call over n_rows rows: three sums per chunk
+size_t strcol_workspace_bytes(uint64_t n_rows);
+// k_strcol_chunk_sums (d_validity, may be NULL), k_strcol_chunk_scan (d_offsets[n_rows], the sjmi_strcol_result at d_result),
+// k_strcol_offsets and, with byte_capacity != 0, k_strcol_copy (the bytes below the capacity); d_types and d_bytes of any alignment
+hipError_t strcol_launch(const void* d_types, const void* d_values, uint64_t n_rows, const void* d_string_buffer, void* d_offsets,
+                         void* d_validity, void* d_bytes, uint64_t byte_capacity, void* d_result, void* d_ws, hipStream_t stream);
+
 }  // namespace sjmi

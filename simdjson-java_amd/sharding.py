@@ -187,6 +187,39 @@ class BatchShard:
                                          self.exp_types.data_ptr() if cells else 0, self.exp_values.data_ptr() if cells else 0, stream)
         return self.exp_row_offsets, self.exp_types, self.exp_values
 
+    def string_column(self, types, values, byte_capacity=None, stream=0):
+        """ONE string column as Arrow large_utf8: sjmi_string_column_device on a 1-D (types uint8, values int64) tensor pair -- a
+        row of sel_types / sel_values, or a row of exp_types / exp_values cut to the rows present -- whose string cells point
+        into self.sb.  -> (offsets [n_rows + 1] int64, validity [ceil(n_rows / 64)] int64 words (LSB first), data uint8, result
+        [4] int64 = total_bytes, n_valid, n_other, flags), new tensors every call.  Rows that are not strings (MISSING -- a
+        failed document's among them --, null, numbers, booleans, containers) are NULL; result[2] counts those of them that are
+        neither MISSING nor null.  byte_capacity=None: a sizing call, the 32-byte record read back -- the one host
+        synchronisation -- `data` allocated exactly and the second call made.  With a byte_capacity nothing synchronises: bytes
+        at or behind it are not written and result[3] & 1 (SJMI_STRCOL_OVERFLOW) says so; the offsets are complete either way.
+        Call it on a step that check() has accepted: unlike select() and explode(), it is not queued again behind a step that
+        check() had to run again."""
+        import torch
+        assert types.dim() == 1 and values.dim() == 1 and types.numel() == values.numel()
+        assert types.dtype == torch.uint8 and values.dtype == torch.int64 and types.is_contiguous() and values.is_contiguous()
+        n_rows = int(types.numel())
+        offsets = torch.empty(n_rows + 1, dtype=torch.int64, device=self.device)
+        validity = torch.empty((n_rows + 63) // 64, dtype=torch.int64, device=self.device)
+        result = torch.empty(4, dtype=torch.int64, device=self.device)  # sjmi_strcol_result (every call writes all of it)
+        call = lambda data, capacity: self.engine.string_column_device(
+            types.data_ptr() if n_rows else 0, values.data_ptr() if n_rows else 0, n_rows, self.sb.data_ptr(), offsets.data_ptr(),
+            validity.data_ptr() if n_rows else 0, data.data_ptr() if capacity else 0, capacity, result.data_ptr(), stream)
+        if byte_capacity is None:
+            call(None, 0)
+            if str(self.device) != "cpu":
+                torch.cuda.synchronize(self.device)  # (`stream` need not be the one torch's copy is queued on)
+            byte_capacity = int(result.cpu()[0])
+            if not byte_capacity:
+                return offsets, validity, torch.empty(0, dtype=torch.uint8, device=self.device), result
+        byte_capacity = int(byte_capacity)
+        data = torch.empty(byte_capacity, dtype=torch.uint8, device=self.device)
+        call(data, byte_capacity)
+        return offsets, validity, data, result
+
     def counts_tensor(self):
         """The per-shard row of the count gather, on the device, without a host copy:
         {documents, structurals, string bytes, failed + handed-back documents}."""
