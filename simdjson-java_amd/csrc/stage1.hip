@@ -456,7 +456,8 @@ union WaveShared {
 
 // BATCH: two more side outputs for the fused batch pipeline (batch.hip k_doc_prepare), per 64-byte block: blkidx = position in
 // the index array of the block's first structural (what a document's index_offsets entry is read from instead of a binary
-// search), blkw = the tape words its structurals make for both entry parities (sj_block_tape_words).
+// search), blkw = the tape words its structurals make for both entry parities (SjBlockMasks::words, the
+// want_words part of sj_block in sj_block.h and of sj_block32 in sj_block32.h).
 template <int S, int LDSW, bool SAFE, bool BATCH>
 __device__ __forceinline__ void
 stage1_body(const uint8_t* __restrict__ buf, sj_u64 len, uint32_t* __restrict__ out, sj_u64 out_cap,
