@@ -619,6 +619,89 @@ int sjmi_string_column_device(sjmi_ctx* ctx, const void* d_types, const void* d_
                               const void* d_string_buffer, void* d_offsets, void* d_validity,
                               void* d_bytes, uint64_t byte_capacity, void* d_result, void* stream);
 
+/* ---- filtering the rows of typed columns on the device and compacting the kept rows ----------------------------------------
+ * Which rows a caller wants, decided between select / explode and the string gather (csrc/filter.hip).  The call
+ * reads finished (types, values) columns and the string buffer and nothing else: no tape, no select plan.
+ *
+ * A FILTER PLAN is a conjunction of at most SJMI_FILTER_MAX_TERMS terms, compiled on the host with no device and no context.  A
+ * term looks at ONE column: the cell of column c, row r is types[c * col_stride + r] / values[c * col_stride + r] in the encoding
+ * of sjmi_select_batch_device.  A term is TRUE only in the cases below; in particular every comparison is FALSE on a cell that
+ * is not of the comparable type -- NE on a MISSING or null cell included, as SQL treats a comparison with NULL.
+ *   TYPE_EQ / TYPE_NE      the type byte equals / differs from the operand (0 = MISSING, so TYPE_NE 0 is "present"; 't' 'f' 'n'
+ *                          are tested this way)
+ *   LONG_* / DOUBLE_*      the cell is 'l' or 'd', and the comparison (EQ NE LT LE GT GE) of the cell with the constant holds for
+ *                          the two numbers AS REAL NUMBERS, exactly: int64 with int64 as integers, double with double as IEEE
+ *                          doubles (-0.0 == 0.0), int64 with double without rounding either side (9007199254740993 is GT
+ *                          9007199254740992.0, not EQ).  +-infinity is a legal constant and a legal cell; a NaN constant does not
+ *                          compile, and NaN cells (the parser makes none) satisfy no comparison.
+ *   STRING_EQ / _NE / _PREFIX   the cell is '"' with len = value >> 32 and its bytes at d_string_buffer + (value & 0xFFFFFFFF).
+ *                          EQ: len == clen and the bytes are equal, byte for byte on the unescaped bytes (Arrays.compare(...) == 0,
+ *                          JsonValue.java:102); NE: a string that is not EQ; PREFIX: len >= clen and the first clen bytes are
+ *                          equal.  An empty constant is legal.
+ * A row is KEPT iff every term is TRUE; a plan without terms keeps every row.
+ * sjmi_filter_plan_compile: the string constants are bytes[offset, offset + length) of `bytes` (n_bytes of them; NULL with 0).
+ * SJMI_ERR_ARG: more than SJMI_FILTER_MAX_TERMS terms, an unknown op, a type operand above 255, a NaN, a string constant outside
+ * `bytes` or longer than SJMI_FILTER_MAX_STRING, n_bytes above SJMI_FILTER_MAX_CONST_BYTES, NULL terms / bytes with a count. */
+#define SJMI_FILTER_MAX_TERMS 16u
+#define SJMI_FILTER_MAX_CONST_BYTES 1024u   /* all string constants of a plan together (n_bytes) */
+#define SJMI_FILTER_MAX_STRING 256u         /* one string constant */
+#define SJMI_F_TYPE_EQ 0x00u
+#define SJMI_F_TYPE_NE 0x01u
+#define SJMI_F_LONG_EQ 0x10u
+#define SJMI_F_LONG_NE 0x11u
+#define SJMI_F_LONG_LT 0x12u
+#define SJMI_F_LONG_LE 0x13u
+#define SJMI_F_LONG_GT 0x14u
+#define SJMI_F_LONG_GE 0x15u
+#define SJMI_F_DOUBLE_EQ 0x20u
+#define SJMI_F_DOUBLE_NE 0x21u
+#define SJMI_F_DOUBLE_LT 0x22u
+#define SJMI_F_DOUBLE_LE 0x23u
+#define SJMI_F_DOUBLE_GT 0x24u
+#define SJMI_F_DOUBLE_GE 0x25u
+#define SJMI_F_STRING_EQ 0x30u
+#define SJMI_F_STRING_NE 0x31u
+#define SJMI_F_STRING_PREFIX 0x36u
+typedef struct sjmi_filter_term {
+    uint32_t column;    /* which of the call's n_cols columns the term looks at */
+    uint32_t op;        /* SJMI_F_<KIND>_<CMP> */
+    uint64_t operand;   /* TYPE: the type byte; LONG: the int64; DOUBLE: the IEEE bits; STRING: (length << 32) | offset into `bytes` */
+} sjmi_filter_term;
+typedef struct sjmi_filter_plan sjmi_filter_plan;
+int sjmi_filter_plan_compile(const sjmi_filter_term* terms, uint64_t n_terms, const uint8_t* bytes, uint64_t n_bytes, sjmi_filter_plan** out);
+void sjmi_filter_plan_destroy(sjmi_filter_plan* plan);
+/* MEMORY.  A cell's value word is used as an offset or a length only behind the test type == '"', and as a number only behind
+ * 'l' / 'd'.  Of a string cell only bytes inside [offset, offset + len) are read, and the length decides before a byte is touched.
+ * OUTPUTS, each optional except d_result:
+ *   d_keep        uint64[ceil(n_rows / 64)], LSB first: bit r is set iff row r is kept; bits at or above n_rows are 0
+ *   d_rows        int64[out_capacity]: d_rows[j] = the index of the j-th kept row, ascending -- the selection vector, with which a
+ *                 caller gathers anything else (a document id, through explode's row offsets, included)
+ *   d_out_types / d_out_values   all n_cols columns compacted: for j < min(n_kept, out_capacity), out_types[c * out_capacity + j] =
+ *                 types[c * col_stride + rows[j]] and the values likewise, word for word -- a (types, values) column set again,
+ *                 of which sjmi_string_column_device takes a row unchanged
+ *   d_result      n_kept is ALWAYS complete, whatever out_capacity is; n_kept > out_capacity sets SJMI_FILTER_OVERFLOW
+ * Entries j >= out_capacity are not written, nor entries between n_kept and out_capacity, and nothing behind out_capacity entries
+ * (times n_cols for the columns) is touched.  d_rows, d_out_types and d_out_values come together or not at all; out_capacity == 0
+ * with all three NULL is the SIZING call (the emit kernel is not launched).  Outputs must not overlap inputs.
+ * n_rows == 0 is legal: a zero result record, and no kernel is launched with an empty grid.
+ * ARGUMENTS.  SJMI_ERR_ARG: a term's column >= n_cols; col_stride < n_rows; NULL d_result; NULL d_types or d_values with n_rows >
+ * 0; NULL d_string_buffer when the plan has a STRING term and n_rows > 0; NULL d_rows, d_out_types or d_out_values with
+ * out_capacity > 0; d_values, d_keep, d_rows, d_out_values or d_result not 8-byte aligned (d_types and d_out_types take any
+ * alignment); n_rows >= 2^40.
+ * STREAM AND STATE.  Asynchronous on `stream` (NULL = the context's), no host synchronisation, nothing queued but three plain
+ * kernels that the stream orders (the terms per 1024 rows, the scan of the chunk counts by one workgroup, the emit).  The plan
+ * is handed to the kernels by value as a launch argument: the call uploads nothing and the context holds no filter plan.  The
+ * only state is a scratch slot of its own (the chunk counts, and the keep words of a call without d_keep), which grows on demand
+ * with a device synchronisation; it is one per context, so filter calls on ONE context must be ordered with respect to each other. */
+#define SJMI_FILTER_OVERFLOW 1u   /* n_kept > out_capacity */
+typedef struct sjmi_filter_result {
+    uint64_t n_kept;
+    uint32_t flags, reserved;
+} sjmi_filter_result;
+int sjmi_filter_columns_device(sjmi_ctx* ctx, const sjmi_filter_plan* plan, const void* d_types, const void* d_values, uint64_t n_cols,
+                               uint64_t col_stride, uint64_t n_rows, const void* d_string_buffer, void* d_keep, void* d_rows,
+                               uint64_t out_capacity, void* d_out_types, void* d_out_values, void* d_result, void* stream);
+
 /* Optional: page-lock caller-owned host memory that is passed to the host-buffer entry points again and again
  * (SimdJsonParser's padded input, index array and string buffer): H2D / D2H copies of pinned memory skip the
  * driver's staging copy (3-4x faster for the ~1 MB transfers of a single-document parse).  Purely a performance

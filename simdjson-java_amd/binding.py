@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_HERE)
 _CSRC = os.path.join(_HERE, "csrc")
 _LIB = os.path.join(_HERE, "libsjmi.so")
-SOURCES = ["stage1.hip", "strings.hip", "batch.hip", "walk.hip", "coop_walk.hip", "masks.hip", "select.hip", "explode.hip", "ndjson.hip", "strcol.hip", "sjmi_api.hip", "host/simdjson_parser.cpp"]
+SOURCES = ["stage1.hip", "strings.hip", "batch.hip", "walk.hip", "coop_walk.hip", "masks.hip", "select.hip", "explode.hip", "ndjson.hip", "strcol.hip", "filter.hip", "sjmi_api.hip", "host/simdjson_parser.cpp"]
 
 ST_UTF8, ST_UNCLOSED, ST_UNESCAPED, ST_CAPACITY, ST_INTERNAL = 1, 2, 4, 0x100, 0x200
 PADDING = 64
@@ -108,7 +108,8 @@ EXPORTS = ["sjmi_create", "sjmi_destroy", "sjmi_last_error", "sjmi_version", "sj
            "sjmi_od_depth", "sjmi_od_peek",
            "sjmi_select_plan_compile", "sjmi_select_plan_destroy", "sjmi_select_batch_device",
            "sjmi_explode_plan_compile", "sjmi_explode_plan_destroy", "sjmi_explode_batch_device",
-           "sjmi_ndjson_offsets_device", "sjmi_ndjson_offsets", "sjmi_ndjson_tile_bytes", "sjmi_string_column_device"]
+           "sjmi_ndjson_offsets_device", "sjmi_ndjson_offsets", "sjmi_ndjson_tile_bytes", "sjmi_string_column_device",
+           "sjmi_filter_plan_compile", "sjmi_filter_plan_destroy", "sjmi_filter_columns_device"]
 
 
 # Handles that are still open when the interpreter exits are closed HERE, in an atexit hook -- i.e. while the HIP runtime
@@ -275,6 +276,13 @@ def lib():
         L.sjmi_string_column_device.restype = C.c_int
         L.sjmi_string_column_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
                                                 C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+        L.sjmi_filter_plan_compile.restype = C.c_int
+        L.sjmi_filter_plan_compile.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p)]
+        L.sjmi_filter_plan_destroy.restype = None
+        L.sjmi_filter_plan_destroy.argtypes = [C.c_void_p]
+        L.sjmi_filter_columns_device.restype = C.c_int
+        L.sjmi_filter_columns_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p,
+                                                 C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.sjmi_select_batch_device.restype = C.c_int
         L.sjmi_select_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
                                                C.c_void_p, C.c_void_p, C.c_void_p]
@@ -523,6 +531,17 @@ class Context:
                                                     d_validity or None, d_bytes or None, byte_capacity, d_result or None, stream),
                     "sjmi_string_column_device")
 
+    def filter_columns_device(self, plan, d_types, d_values, n_cols, col_stride, n_rows, d_sb, d_keep, d_rows, out_capacity, d_out_types,
+                              d_out_values, d_result, stream=0):
+        """sjmi_filter_columns_device: the rows of n_cols (types, values) columns strided by col_stride on which every term of
+        `plan` (a FilterPlan) is true -- d_keep (uint64 words, LSB first), d_rows (int64 [out_capacity], the kept rows' indexes,
+        ascending), d_out_types / d_out_values (the columns compacted, strided by out_capacity); each None / 0: not written, the
+        last three together (with out_capacity 0: the sizing call); d_result = device sjmi_filter_result (2 x int64: n_kept,
+        flags in the low half of the second).  Asynchronous on `stream`."""
+        self._check(lib().sjmi_filter_columns_device(self._h, plan._h, d_types or None, d_values or None, n_cols, col_stride, n_rows,
+                                                     d_sb or None, d_keep or None, d_rows or None, out_capacity, d_out_types or None,
+                                                     d_out_values or None, d_result or None, stream), "sjmi_filter_columns_device")
+
     def ndjson_offsets(self, data):
         """sjmi_ndjson_offsets (host form) -> (doc_offsets np.uint64 [n_docs + 1], consumed, flags): the documents are the
         non-blank lines of data[0, consumed), blank lines absorbed by the document in front of them."""
@@ -641,6 +660,62 @@ class ExplodePlan:
     def close(self):
         if self._h:
             lib().sjmi_explode_plan_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class FilterPlan:
+    """sjmi_filter_plan: a conjunction of at most 16 terms (column, op, constant) compiled once, on the host (no device needed),
+    for Context.filter_columns_device / BatchShard.filter.  op is "<kind>_<cmp>": "type_eq" / "type_ne" with a type byte (an int,
+    or a one-character str or bytes; 0 = MISSING), "long_eq|ne|lt|le|gt|ge" with an int, "double_eq|..." with a float,
+    "string_eq" / "string_ne" / "string_prefix" with bytes or str (UTF-8).  Raises ValueError for what include/sjmi.h lists as
+    SJMI_ERR_ARG: an unknown op, a NaN, a limit exceeded (SJMI_FILTER_MAX_*)."""
+
+    KINDS = {"type": 0, "long": 1, "double": 2, "string": 3}
+    CMPS = {"eq": 0, "ne": 1, "lt": 2, "le": 3, "gt": 4, "ge": 5, "prefix": 6}
+    _TERM = np.dtype([("column", "<u4"), ("op", "<u4"), ("operand", "<u8")])
+
+    def __init__(self, terms):
+        import struct
+        self.terms = [tuple(t) for t in terms]
+        enc = np.zeros(len(self.terms), dtype=self._TERM)
+        blob = b""
+        for k, (column, op, const) in enumerate(self.terms):
+            kind, _, cmp = str(op).partition("_")
+            if kind not in self.KINDS or cmp not in self.CMPS:
+                raise ValueError("filter term %d: unknown op %r" % (k, op))
+            if kind == "type":
+                operand = ord(const) if isinstance(const, (str, bytes)) else int(const)
+            elif kind == "long":
+                operand = int(const) & 0xFFFFFFFFFFFFFFFF
+                if not -(1 << 63) <= int(const) < (1 << 63):
+                    raise ValueError("filter term %d: %r is no int64" % (k, const))
+            elif kind == "double":
+                operand = struct.unpack("<Q", struct.pack("<d", float(const)))[0]
+            else:
+                const = const.encode("utf-8") if isinstance(const, str) else bytes(const)
+                operand = (len(const) << 32) | len(blob)
+                blob += const
+            if not 0 <= operand < (1 << 64) or not 0 <= int(column) < (1 << 32):
+                raise ValueError("filter term %d: operand or column out of range" % k)
+            enc[k] = (int(column), (self.KINDS[kind] << 4) | self.CMPS[cmp], operand)
+        self.n_terms = len(self.terms)
+        consts = np.frombuffer(blob + b"\0", dtype=np.uint8)
+        self._h = C.c_void_p()
+        rc = lib().sjmi_filter_plan_compile(enc.ctypes.data if self.n_terms else None, self.n_terms, consts.ctypes.data if blob else None,
+                                            len(blob), C.byref(self._h))
+        if rc != 0:
+            self._h = C.c_void_p()
+            raise ValueError("sjmi_filter_plan_compile failed (rc=%d): an unknown op, a NaN or a plan limit exceeded" % rc)
+
+    def close(self):
+        if self._h:
+            lib().sjmi_filter_plan_destroy(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):

@@ -123,6 +123,7 @@ struct sjmi_ctx {
     DevBuf<unsigned long long> d_nd_offsets; // sjmi_ndjson_offsets (host form): the offsets and the result record on the device
     DevBuf<sjmi_ndjson_result> d_nd_result;
     DevBuf<void> d_ws_strcol;                // sjmi_string_column_device: three sums per chunk of rows (a slot of its own)
+    DevBuf<void> d_ws_filter;                // sjmi_filter_columns_device: a count per chunk of rows and the keep words (a slot of its own)
     std::string err;
 };
 
@@ -1003,6 +1004,31 @@ int sjmi_string_column_device(sjmi_ctx* c, const void* d_types, const void* d_va
     }
     return fail(c, "string column launch", sjmi::strcol_launch(d_types, d_values, n_rows, d_string_buffer, d_offsets, d_validity, d_bytes,
                                                                byte_capacity, d_result, c->d_ws_strcol, st))
+               ? SJMI_ERR_HIP
+               : SJMI_OK;
+}
+
+int sjmi_filter_columns_device(sjmi_ctx* c, const sjmi_filter_plan* plan, const void* d_types, const void* d_values, uint64_t n_cols,
+                               uint64_t col_stride, uint64_t n_rows, const void* d_string_buffer, void* d_keep, void* d_rows,
+                               uint64_t out_capacity, void* d_out_types, void* d_out_values, void* d_result, void* stream) {
+    if (!c || !plan || !d_result || col_stride < n_rows || (n_rows && (!d_types || !d_values))) return SJMI_ERR_ARG;
+    if (n_rows >= (1ull << 40)) return SJMI_ERR_ARG;  // (one workgroup per 1024 rows)
+    const int strings = sjmi::filter_plan_columns(plan, n_cols);
+    if (strings < 0 || (strings && n_rows && !d_string_buffer)) return SJMI_ERR_ARG;
+    if (out_capacity && (!d_rows || !d_out_types || !d_out_values)) return SJMI_ERR_ARG;
+    if (((uintptr_t)d_values & 7) || ((uintptr_t)d_keep & 7) || ((uintptr_t)d_rows & 7) || ((uintptr_t)d_out_values & 7) || ((uintptr_t)d_result & 7))
+        return SJMI_ERR_ARG;
+    if (n_cols && (col_stride > ~0ull / 8 / n_cols || out_capacity > ~0ull / 8 / n_cols)) return SJMI_ERR_ARG;  // (a column set is addressable)
+    if (fail(c, "hipSetDevice", hipSetDevice(c->device))) return SJMI_ERR_HIP;
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    const size_t ws = sjmi::filter_workspace_bytes(n_rows);
+    if (ws > c->d_ws_filter.bytes) {
+        // the scratch grows: a launch of an earlier call may still be using the old one
+        if (c->d_ws_filter.p && fail(c, "sync", hipDeviceSynchronize())) return SJMI_ERR_HIP;
+        if (!grow(c, c->d_ws_filter, ws, "hipMalloc(ws_filter)")) return SJMI_ERR_HIP;
+    }
+    return fail(c, "filter launch", sjmi::filter_launch(plan, d_types, d_values, n_cols, col_stride, n_rows, d_string_buffer, d_keep, d_rows,
+                                                        out_capacity, d_out_types, d_out_values, d_result, c->d_ws_filter, st))
                ? SJMI_ERR_HIP
                : SJMI_OK;
 }

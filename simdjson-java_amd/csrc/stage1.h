@@ -406,4 +406,15 @@ size_t strcol_workspace_bytes(uint64_t n_rows);
 hipError_t strcol_launch(const void* d_types, const void* d_values, uint64_t n_rows, const void* d_string_buffer, void* d_offsets,
                          void* d_validity, void* d_bytes, uint64_t byte_capacity, void* d_result, void* d_ws, hipStream_t stream);
 
+// ---- a row filter over typed columns (filter.hip) ----
+// -1: a term looks at a column >= n_cols; else 1 when the plan has a STRING term, 0 when it has none
+int filter_plan_columns(const sjmi_filter_plan* plan, uint64_t n_cols);
+// scratch of one call over n_rows rows: a count per chunk and the keep words
+size_t filter_workspace_bytes(uint64_t n_rows);
+// k_filter_eval (the keep words into d_keep, or into the scratch without one), k_filter_scan (the sjmi_filter_result at d_result)
+// and, with out_capacity != 0, k_filter_emit (d_rows and the compacted columns below the capacity); the plan goes by value
+hipError_t filter_launch(const sjmi_filter_plan* plan, const void* d_types, const void* d_values, uint64_t n_cols, uint64_t col_stride,
+                         uint64_t n_rows, const void* d_string_buffer, void* d_keep, void* d_rows, uint64_t out_capacity, void* d_out_types,
+                         void* d_out_values, void* d_result, void* d_ws, hipStream_t stream);
+
 }  // namespace sjmi

@@ -220,6 +220,36 @@ class BatchShard:
         call(data, byte_capacity)
         return offsets, validity, data, result
 
+    def filter(self, plan, types, values, n_rows=None, out_capacity=None, stream=0):
+        """The rows on which every term of `plan` (a binding.FilterPlan) is true, and the columns compacted to them:
+        sjmi_filter_columns_device on a 2-D [n_cols, stride] (types uint8, values int64) tensor pair -- sel_types / sel_values, or
+        exp_types / exp_values with n_rows = the rows present (default: the stride) -- whose string cells point into self.sb.
+        -> (rows [out_capacity] int64, out_types [n_cols, out_capacity] uint8, out_values [n_cols, out_capacity] int64, keep
+        [ceil(n_rows / 64)] int64 words (LSB first), result [2] int64 = n_kept, flags), new tensors every call.  Entries at or
+        behind result[0] are not written: the caller slices by it after its own synchronisation; a row of out_types / out_values
+        so cut is a column for string_column().  out_capacity=None: n_rows, which always suffices -- nothing synchronises either
+        way; with a smaller one result[1] & 1 (SJMI_FILTER_OVERFLOW) says that rows were left out, and 0 is the sizing call.
+        Call it on a step that check() has accepted: like string_column(), it is not queued again behind a step that check() had
+        to run again."""
+        import torch
+        assert types.dim() == 2 and values.dim() == 2 and types.shape == values.shape
+        assert types.dtype == torch.uint8 and values.dtype == torch.int64 and types.is_contiguous() and values.is_contiguous()
+        n_cols, stride = int(types.shape[0]), int(types.shape[1])
+        n_rows = stride if n_rows is None else int(n_rows)
+        assert n_cols >= 1 and 0 <= n_rows <= stride
+        out_capacity = n_rows if out_capacity is None else int(out_capacity)
+        rows = torch.empty(out_capacity, dtype=torch.int64, device=self.device)
+        out_types = torch.empty((n_cols, out_capacity), dtype=torch.uint8, device=self.device)
+        out_values = torch.empty((n_cols, out_capacity), dtype=torch.int64, device=self.device)
+        keep = torch.empty((n_rows + 63) // 64, dtype=torch.int64, device=self.device)
+        result = torch.empty(2, dtype=torch.int64, device=self.device)  # sjmi_filter_result (every call writes all of it)
+        # (an empty tensor's pointer may be anything: the call gets NULL for what has no entries)
+        self.engine.filter_columns_device(plan, types.data_ptr() if n_rows else 0, values.data_ptr() if n_rows else 0, n_cols, stride, n_rows,
+                                          self.sb.data_ptr(), keep.data_ptr() if n_rows else 0, rows.data_ptr() if out_capacity else 0,
+                                          out_capacity, out_types.data_ptr() if out_capacity else 0,
+                                          out_values.data_ptr() if out_capacity else 0, result.data_ptr(), stream)
+        return rows, out_types, out_values, keep, result
+
     def counts_tensor(self):
         """The per-shard row of the count gather, on the device, without a host copy:
         {documents, structurals, string bytes, failed + handed-back documents}."""
