@@ -1,7 +1,8 @@
 // explode.hip -- one array per document of a parsed batch becomes a run of rows (include/sjmi.h, sjmi_explode_*):
 // the array is the value of a BASE pointer, and every path of an element plan is evaluated on every element, into one typed
 // column per path.  The walk is sj_select.h (sel_explode_count / sel_explode_rows, shared with the host simulation,
-// tests/host_sim/explode_sim.cpp); this file is the plan object, the 16-lane form of the group primitives and the kernels:
+// tests/host_sim/explode_sim.cpp), the 16-lane form of its group primitives is Lanes16 of sj_group.h; this file is the plan object
+// and the kernels:
 //   k_explode_count       rows and the base array's tape index of every document
 //   k_explode_chunk_sums / k_explode_chunk_scan / k_explode_offsets   the counts' exclusive scan (block_excl_scan, the chunk-sum
 //                         scheme of walk.hip's tape offsets) -> row_offsets[n_docs + 1]
@@ -11,8 +12,7 @@
 #include <atomic>
 #include <new>
 
-#include "sj_chain.h"
-#include "sj_select.h"
+#include "sj_group.h"
 #include "stage1.h"
 
 struct sjmi_explode_plan {
@@ -34,31 +34,6 @@ constexpr uint32_t EXP_SCAN_DOCS = 1024;  // documents per workgroup of the scan
 constexpr uint32_t EXP_ROWS = 8;
 constexpr uint32_t EXP_CELLS = 96;
 
-// sixteen lanes of a wave that hold one document (select.hip)
-struct Lanes16 {
-    uint32_t lane, shift;
-    __device__ __forceinline__ uint32_t stride_first() const { return lane; }
-    __device__ __forceinline__ uint32_t stride() const { return SEL_GROUP; }
-    __device__ __forceinline__ void fence() const { wave_lds_fence(); }
-    template <class F>
-    __device__ __forceinline__ uint32_t ballot(F f) const {
-        const bool mine = f(lane);
-        return (uint32_t)(__ballot(mine) >> shift) & 0xFFFFu;
-    }
-};
-
-__device__ __forceinline__ Lanes16 group_lanes() {
-    Lanes16 g;
-    g.lane = threadIdx.x % SEL_GROUP;
-    g.shift = (threadIdx.x & 63u) / SEL_GROUP * SEL_GROUP;
-    return g;
-}
-__device__ __forceinline__ uint32_t doc_words(const unsigned long long* tape_offsets, uint64_t doc) {
-    const unsigned long long lo = tape_offsets[doc], hi = tape_offsets[doc + 1];
-    const unsigned long long n = hi > lo ? hi - lo : 0;
-    return n > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)n;
-}
-
 __global__ __launch_bounds__(EXP_BLOCK) void k_explode_count(const sj_u64* __restrict__ plan_image, uint32_t image_words,
                                                               const sj_u64* __restrict__ tape,
                                                               const unsigned long long* __restrict__ tape_offsets,
@@ -66,9 +41,7 @@ __global__ __launch_bounds__(EXP_BLOCK) void k_explode_count(const sj_u64* __res
                                                               uint64_t n_docs, uint32_t* __restrict__ counts, uint32_t* __restrict__ bases) {
     extern __shared__ sj_u64 lds_plan[];
     __shared__ SelScratch scratch[EXP_BLOCK_DOCS];
-    for (uint32_t i = threadIdx.x; i < image_words; i += EXP_BLOCK) lds_plan[i] = plan_image[i];
-    __syncthreads();
-    const SelHeader* plan = (const SelHeader*)lds_plan;
+    const SelHeader* plan = stage_plan<EXP_BLOCK>(lds_plan, plan_image, image_words);
     Lanes16 g = group_lanes();
     SelScratch& s = scratch[threadIdx.x / SEL_GROUP];
     for (uint64_t doc = (uint64_t)blockIdx.x * EXP_BLOCK_DOCS + threadIdx.x / SEL_GROUP; doc < n_docs;
@@ -135,9 +108,7 @@ __global__ __launch_bounds__(EXP_BLOCK) void k_explode_rows(const sj_u64* __rest
     extern __shared__ sj_u64 lds_plan[];
     __shared__ SelScratch scratch[EXP_BLOCK_DOCS];
     __shared__ RowBuf bufs[EXP_BLOCK_DOCS];
-    for (uint32_t i = threadIdx.x; i < image_words; i += EXP_BLOCK) lds_plan[i] = plan_image[i];
-    __syncthreads();
-    const SelHeader* plan = (const SelHeader*)lds_plan;
+    const SelHeader* plan = stage_plan<EXP_BLOCK>(lds_plan, plan_image, image_words);
     const uint32_t n_paths = plan->n_paths;
     Lanes16 g = group_lanes();
     SelScratch& s = scratch[threadIdx.x / SEL_GROUP];

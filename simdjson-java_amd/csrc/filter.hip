@@ -1,7 +1,7 @@
 // filter.hip -- the rows of a set of (type, value) columns filtered by a conjunction of terms and compacted (include/sjmi.h,
 // sjmi_filter_columns_device).  The passes are sj_filter.h (shared with the host simulation, tests/host_sim/
-// filter_sim.cpp); this file is the device form of its lane primitives, three plain kernels that the stream orders -- no
-// workgroup waits for another -- and the host side of a plan:
+// filter_sim.cpp), the device form of its lane group is WgGroup of sj_group.h; this file is three plain kernels that the stream
+// orders -- no workgroup waits for another -- and the host side of a plan:
 //   k_filter_eval   one workgroup per 1024 rows, one lane per row: the terms in plan order, the keep words (a wave is 64
 //                   consecutive rows: its ballot is one word) and the chunk's kept rows
 //   k_filter_scan   ONE workgroup: the kept rows in front of every chunk (in place), the result record
@@ -12,8 +12,8 @@
 
 #include <new>
 
-#include "sj_chain.h"
 #include "sj_filter.h"
+#include "sj_group.h"
 #include "stage1.h"
 
 static_assert(FL_OVERFLOW == SJMI_FILTER_OVERFLOW, "sj_filter.h restates the flag");
@@ -39,41 +39,22 @@ namespace {
 
 static_assert(FL_CHUNK_ROWS == 1024, "block_scan_in_place takes slices of 1024 entries with 1024 threads");
 
-// the waves of a workgroup (sj_filter.h)
-struct WgWaves {
-    unsigned long long* s_wave;  // one entry per wave
-    __device__ __forceinline__ uint32_t waves() const { return blockDim.x >> 6; }
-    __device__ __forceinline__ uint32_t wave() const { return threadIdx.x >> 6; }
-    __device__ __forceinline__ uint32_t lane() const { return threadIdx.x; }
-    __device__ __forceinline__ bool first() const { return (threadIdx.x & 63u) == 0; }
-    template <class F>
-    __device__ __forceinline__ sj_u64 ballot(F f) const {
-        return __ballot(f(threadIdx.x & 63u));
-    }
-    template <class F>
-    __device__ __forceinline__ void each(F f) const {
-        f(threadIdx.x & 63u);
-    }
-    __device__ __forceinline__ sj_u64 scan_add(sj_u64 v, sj_u64* total) const { return block_excl_scan(v, s_wave, total); }
-    __device__ __forceinline__ sj_u64 scan_in_place(sj_u64* sums, sj_u64 n) const { return block_scan_in_place(sums, n, s_wave); }
-};
-
 __global__ __launch_bounds__(FL_CHUNK_ROWS) void k_filter_eval(const FlPlan p, FlCols c, sj_u64* __restrict__ keep, sj_u64* __restrict__ counts) {
     __shared__ unsigned long long s_wave[FL_CHUNK_ROWS / 64];
-    const WgWaves g = {s_wave};
+    const WgGroup g = {s_wave};
     fl_eval_chunk(g, p, c, blockIdx.x, keep, counts);
 }
 
 __global__ __launch_bounds__(1024) void k_filter_scan(sj_u64* __restrict__ counts, uint64_t nchunks, uint64_t out_capacity,
                                                       FlResult* __restrict__ res) {
     __shared__ unsigned long long s_wave[16];
-    const WgWaves g = {s_wave};
+    const WgGroup g = {s_wave};
     fl_chunk_scan(g, counts, nchunks, out_capacity, res);
 }
 
 __global__ __launch_bounds__(FL_CHUNK_ROWS) void k_filter_emit(FlCols c, const sj_u64* __restrict__ keep, const sj_u64* __restrict__ counts,
                                                                FlOut o) {
-    const WgWaves g = {nullptr};  // (no scan in this pass, and no barrier: a chunk behind the capacity leaves at once)
+    const WgGroup g = {nullptr};  // (no scan in this pass, and no barrier: a chunk behind the capacity leaves at once)
     fl_emit_chunk(g, c, blockIdx.x, keep, counts, o);
 }
 

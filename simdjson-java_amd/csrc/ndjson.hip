@@ -1,13 +1,14 @@
 // ndjson.hip -- document offsets of a buffer of newline-delimited JSON, made on the device (include/sjmi.h, sjmi_ndjson_offsets*;
-// DESIGN.md 4.10).  The passes are sj_ndjson.h (shared with the host simulation, tests/host_sim/ndjson_sim.cpp); this file is the
-// workgroup form of its lane primitives and three plain kernels that the stream orders -- no workgroup waits for another:
+// DESIGN.md 4.10).  The passes are sj_ndjson.h (shared with the host simulation, tests/host_sim/ndjson_sim.cpp), the workgroup
+// form of its lane group is WgGroup of sj_group.h; this file adds what is NdState's own to that group (the block load and the scan
+// of the states) and is three plain kernels that the stream orders -- no workgroup waits for another:
 //   k_ndjson_summary   one workgroup per 64 KiB tile: the tile's state and its starts
 //   k_ndjson_scan      ONE workgroup: the states and the starts in front of every tile (in place), the result record
 //   k_ndjson_emit      one workgroup per tile, reading the bytes a second time: doc_offsets[1 ..]
 // The input is read twice at most; a call that only sizes (offset_capacity <= 1) reads it once.
 #include <hip/hip_runtime.h>
 
-#include "sj_chain.h"
+#include "sj_group.h"
 #include "sj_ndjson.h"
 #include "stage1.h"
 
@@ -21,12 +22,9 @@ namespace {
 constexpr uint32_t ND_BLOCK = 256;    // threads of a tile's workgroup: four steps of 256 blocks
 constexpr uint32_t ND_SCAN = 1024;    // threads of the scan's workgroup
 
-// the lanes of a workgroup (sj_ndjson.h)
-struct WgLanes {
-    NdState* s_state;           // one entry per wave
-    unsigned long long* s_add;  // one entry per wave
-    __device__ __forceinline__ uint32_t lanes() const { return blockDim.x; }
-    __device__ __forceinline__ uint32_t lane() const { return threadIdx.x; }
+// the workgroup (sj_group.h) with what sj_ndjson.h asks besides: s_wave is the adder's LDS, s_state the states'
+struct NdGroup : WgGroup {
+    NdState* s_state;  // one entry per wave
     __device__ __forceinline__ void load(const uint8_t* p, uint32_t w[16]) const {
         const uint4* src = reinterpret_cast<const uint4*>(p);
         const uint4 q0 = src[0], q1 = src[1], q2 = src[2], q3 = src[3];
@@ -57,14 +55,12 @@ struct WgLanes {
         *total = t;
         return nd_combine(base, excl);
     }
-    __device__ __forceinline__ sj_u64 scan_add(sj_u64 v, sj_u64* total) const { return block_excl_scan(v, s_add, total); }
-    __device__ __forceinline__ bool any(bool flag) const { return __syncthreads_or(flag ? 1 : 0) != 0; }
 };
 
 __global__ __launch_bounds__(ND_BLOCK) void k_ndjson_summary(NdGeom ge, NdTile* __restrict__ tiles) {
     __shared__ NdState s_state[ND_BLOCK / 64];
     __shared__ unsigned long long s_add[ND_BLOCK / 64];
-    const WgLanes g = {s_state, s_add};
+    const NdGroup g = {{s_add}, s_state};
     const NdTile t = nd_tile_summary(g, ge, blockIdx.x);
     if (threadIdx.x == 0) tiles[blockIdx.x] = t;
 }
@@ -74,7 +70,7 @@ __global__ __launch_bounds__(ND_SCAN) void k_ndjson_scan(NdGeom ge, NdTile* __re
                                                           NdResult* __restrict__ res) {
     __shared__ NdState s_state[ND_SCAN / 64];
     __shared__ unsigned long long s_add[ND_SCAN / 64];
-    const WgLanes g = {s_state, s_add};
+    const NdGroup g = {{s_add}, s_state};
     const NdTile all = nd_scan_tiles(g, tiles, ntiles);
     if (threadIdx.x == 0) nd_finish(ge, all, offsets, capacity, res);
 }
@@ -83,7 +79,7 @@ __global__ __launch_bounds__(ND_BLOCK) void k_ndjson_emit(NdGeom ge, const NdTil
                                                           unsigned long long* __restrict__ offsets, uint64_t capacity) {
     __shared__ NdState s_state[ND_BLOCK / 64];
     __shared__ unsigned long long s_add[ND_BLOCK / 64];
-    const WgLanes g = {s_state, s_add};
+    const NdGroup g = {{s_add}, s_state};
     nd_tile_emit(g, ge, blockIdx.x, tiles[blockIdx.x], offsets, capacity);
 }
 

@@ -1,13 +1,13 @@
 // select.hip -- the device-resident selector (include/sjmi.h, sjmi_select_*): every path of a compiled plan on every
 // document of a parsed batch, into one typed column per path.  The walk itself is sj_select.h (shared with the host
-// simulation, tests/host_sim/sel_sim.cpp); this file is the plan object, the 16-lane form of the group primitives and k_select.
+// simulation, tests/host_sim/sel_sim.cpp), the 16-lane form of its group primitives is Lanes16 of sj_group.h; this file is the
+// plan object and k_select.
 #include <hip/hip_runtime.h>
 
 #include <atomic>
 #include <new>
 
-#include "sj_chain.h"
-#include "sj_select.h"
+#include "sj_group.h"
 #include "stage1.h"
 
 struct sjmi_select_plan {
@@ -23,19 +23,6 @@ constexpr uint32_t SEL_BLOCK = 128;                          // two waves: eight
 constexpr uint32_t SEL_BLOCK_DOCS = SEL_BLOCK / SEL_GROUP;
 constexpr uint32_t SEL_MAX_GRID = 16384;                     // a workgroup loads the plan once and takes documents in a grid stride
 
-// sixteen lanes of a wave that hold one document (a DPP row, like k_doc_pass)
-struct Lanes16 {
-    uint32_t lane, shift;
-    __device__ __forceinline__ uint32_t stride_first() const { return lane; }
-    __device__ __forceinline__ uint32_t stride() const { return SEL_GROUP; }
-    __device__ __forceinline__ void fence() const { wave_lds_fence(); }
-    template <class F>
-    __device__ __forceinline__ uint32_t ballot(F f) const {
-        const bool mine = f(lane);
-        return (uint32_t)(__ballot(mine) >> shift) & 0xFFFFu;
-    }
-};
-
 __global__ __launch_bounds__(SEL_BLOCK) void k_select(const sj_u64* __restrict__ plan_image, uint32_t image_words,
                                                        const sj_u64* __restrict__ tape,
                                                        const unsigned long long* __restrict__ tape_offsets,
@@ -43,14 +30,10 @@ __global__ __launch_bounds__(SEL_BLOCK) void k_select(const sj_u64* __restrict__
                                                        uint64_t n_docs, uint8_t* __restrict__ types, sj_u64* __restrict__ values) {
     extern __shared__ sj_u64 lds_plan[];
     __shared__ SelScratch scratch[SEL_BLOCK_DOCS];
-    for (uint32_t i = threadIdx.x; i < image_words; i += SEL_BLOCK) lds_plan[i] = plan_image[i];
-    __syncthreads();
-    const SelHeader* plan = (const SelHeader*)lds_plan;
+    const SelHeader* plan = stage_plan<SEL_BLOCK>(lds_plan, plan_image, image_words);
     const uint32_t n_paths = plan->n_paths;
     const uint32_t grp = threadIdx.x / SEL_GROUP;
-    Lanes16 g;
-    g.lane = threadIdx.x % SEL_GROUP;
-    g.shift = (threadIdx.x & 63u) / SEL_GROUP * SEL_GROUP;
+    Lanes16 g = group_lanes();
     SelScratch& s = scratch[grp];
     for (uint64_t base = (uint64_t)blockIdx.x * SEL_BLOCK_DOCS; base < n_docs; base += (uint64_t)gridDim.x * SEL_BLOCK_DOCS) {
         for (uint32_t p = g.lane; p < n_paths; p += SEL_GROUP) {  // MISSING until the walk says otherwise
@@ -60,9 +43,7 @@ __global__ __launch_bounds__(SEL_BLOCK) void k_select(const sj_u64* __restrict__
         g.fence();
         const uint64_t doc = base + grp;
         if (doc < n_docs && doc_errors[doc] == 0) {  // (a failed document's tape slot is never read: its contents are unspecified)
-            const unsigned long long lo = tape_offsets[doc], hi = tape_offsets[doc + 1];
-            const unsigned long long n = hi > lo ? hi - lo : 0;
-            sel_document(g, plan, tape + lo, n > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)n, sb, s);
+            sel_document(g, plan, tape + tape_offsets[doc], doc_words(tape_offsets, doc), sb, s);
         }
         __syncthreads();
         // path-major columns: the workgroup's eight documents are neighbours in every column

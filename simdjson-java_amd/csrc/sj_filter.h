@@ -9,17 +9,10 @@
 // selection vector and the compacted columns (pass 3: rank = chunk base + kept rows of the chunk's earlier words + the kept
 // rows below this one in its own word).
 //
-// The lanes come from the caller, a type G (a workgroup of waves of 64 lanes; the chunk is a multiple of 64 rows).  Code outside
-// the functions handed to ballot / each is wave-uniform:
-//   g.waves() / g.wave()       -- how many waves work on a chunk side by side, and which one this is
-//   g.ballot(f)                -- the 64-bit word whose bit t is f(t), f called for every lane t of the wave
-//   g.each(f)                  -- f(t) for every lane t of the wave
-//   g.first()                  -- true in ONE lane of the wave (the one that stores a wave-uniform value)
-//   g.scan_add(v, &total)      -- exclusive + scan of v over all lanes of the group, total = their sum
-//   g.scan_in_place(sums, n)   -- sums[0, n) -> their exclusive + scan, in place; returns the total
-//   g.lane()                   -- this lane among all of the group (lane 0 writes the result record)
-// csrc/filter.hip gives the device forms (a wave is 64 consecutive rows: its ballot IS one keep word), tests/host_sim/
-// filter_sim.cpp the sequential ones: this file is compiled verbatim by both.
+// The lanes come from the caller: takes a workgroup G (sj_group.h; the chunk is a multiple of 64 rows, and a wave is 64
+// consecutive rows: its ballot IS one keep word); uses: waves, wave, ballot, each, first, scan_add, scan_in_place, lane.  Code
+// outside the functions handed to ballot / each is wave-uniform.  csrc/filter.hip runs this file with the device form,
+// tests/host_sim/filter_sim.cpp with the sequential one (tests/host_sim/seq_group.h): it is compiled verbatim by both.
 #pragma once
 #include <stdint.h>
 

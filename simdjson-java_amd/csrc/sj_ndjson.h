@@ -19,14 +19,12 @@
 // with aligned 16-byte loads whatever the pointer's alignment; the bytes in front of the buffer and behind its end (the
 // padding) are masked out of N and B (nd_valid) and read as BLANK.
 //
-// The lanes that share a tile come from the caller as a type G:
-//   g.lanes() / g.lane()          -- how many blocks are worked on side by side, and which one is this lane's
+// The lanes that share a tile come from the caller: takes a workgroup G (sj_group.h; one block per lane); uses: lanes, lane,
+// scan_add, any, and two members that csrc/ndjson.hip and tests/host_sim/ndjson_sim.cpp add to the group:
 //   g.load(p, w)                  -- the 64 bytes at p (16-byte aligned) as 16 little-endian dwords
-//   g.scan_state(v, &total)       -- exclusive nd_combine scan of v over the lanes, total = all of them combined
-//   g.scan_add(v, &total)         -- exclusive + scan
-//   g.any(flag)                   -- is the flag set in any lane
-// csrc/ndjson.hip gives the workgroup form, tests/host_sim/ndjson_sim.cpp the sequential one (one lane): this file is compiled
-// verbatim by both, so the CPU suite checks the passes the kernels run, at any tile size.
+//   g.scan_state(v, &total)       -- exclusive nd_combine scan of v over the lanes, total = all of them combined (a workgroup
+//                                    barrier that begins with one, like scan_add)
+// This file is compiled verbatim by both, so the CPU suite checks the passes the kernels run, at any tile size.
 #pragma once
 #include <stdint.h>
 

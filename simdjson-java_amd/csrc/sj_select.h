@@ -5,12 +5,10 @@
 // A group of SEL_GROUP lanes works on one document.  Everything that decides where the walk goes is the same in all lanes
 // of the group (the computeNextIndex chain, Tape.java:86-98, the frames of the trie descent, the results); only two things
 // are spread over the lanes: the copy of the tape into the group's slice, and the comparison of up to 16 member keys of the
-// object at hand with the names of the trie node (sel_match_round).  The group primitives come from the caller as a type G:
-//   g.stride_first() / g.stride()  -- the lane's first element and the step of a cooperative copy
-//   g.fence()                      -- orders the group's slice / scratch accesses
-//   g.ballot(f)                    -- f(lane) for every lane of the group -> bit j = what lane j returned
-// csrc/select.hip and csrc/explode.hip give the 16-lane form (four groups to a wave), tests/host_sim/sel_sim.cpp and
-// explode_sim.cpp the sequential one: this file is compiled verbatim by all of them, so the CPU suite checks the walk the kernels run.
+// object at hand with the names of the trie node (sel_match_round).  The group primitives come from the caller: takes a group G
+// of SEL_GROUP lanes (sj_group.h, Lanes16); uses: stride_first, stride, fence, ballot.  csrc/select.hip and csrc/explode.hip run
+// this file with the 16-lane form (four groups to a wave), tests/host_sim/sel_sim.cpp and explode_sim.cpp with the sequential one
+// (tests/host_sim/seq_group.h): it is compiled verbatim by all of them, so the CPU suite checks the walk the kernels run.
 //
 // The chain is walked serially, so whether a tape word is a header or the raw second word of an 'l' / 'd' entry is never a
 // question: only words AT chain positions are read as headers (an int64 of 0x5B00000000000005 is a payload, not '[').

@@ -11,17 +11,10 @@
 // one byte.  Short strings share a trip, empty and NULL rows cost nothing, consecutive waves write consecutive bytes.
 // KNOWN LIMIT: one very long string is copied by one wave, 64 bytes per trip.
 //
-// The lanes come from the caller.  Passes 1 to 3 take a type G (a workgroup; the chunk is a multiple of 64 rows):
-//   g.lanes() / g.lane()                 -- how many rows are worked on side by side, and which one is this lane's
-//   g.scan_add(v, &total)                -- exclusive + scan of v over the lanes, total = their sum
-//   g.scan_in_place(sums, n)             -- sums[0, n) -> their exclusive + scan, in place; returns the total
-//   g.validity_bit(words, r, live, flag) -- called by every lane with its row r: bit r & 63 of words[r >> 6] = flag; a row that
-//                                           is not live (r >= n_rows) gives a 0 bit, and a word without a live row is not written
-// and pass 4 a type W (one wave of 64 lanes and its ScWave in LDS):
-//   w.each(f)                            -- f(t) for every lane t of the wave
-//   w.fence()                            -- what the lanes wrote to the ScWave is visible to all of them
-// csrc/strcol.hip gives the device forms (a wave's ballot IS one validity word: one lane stores it), tests/host_sim/
-// strcol_sim.cpp the sequential ones: this file is compiled verbatim by both.
+// The lanes come from the caller.  Passes 1 to 3 take a workgroup G (sj_group.h; the chunk is a multiple of 64 rows, one row per
+// lane); uses: lanes, lane, scan_add, scan_in_place, validity_bit.  Pass 4 takes a wave W (sj_group.h) and its ScWave in LDS;
+// uses: each, fence.  csrc/strcol.hip runs this file with the device forms, tests/host_sim/strcol_sim.cpp with the sequential
+// ones (tests/host_sim/seq_group.h): it is compiled verbatim by both.
 #pragma once
 #include <stdint.h>
 

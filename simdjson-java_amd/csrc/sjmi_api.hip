@@ -36,6 +36,12 @@ struct Buf {
 template <class T> using DevBuf = Buf<T, false>;
 template <class T> using HostBuf = Buf<T, true>;
 
+// a compiled plan on the device and which one it is (its never-reused serial; 0: none)
+struct PlanSlot {
+    DevBuf<void> d;
+    uint64_t serial = 0;
+};
+
 struct sjmi_ctx {
     int device = 0;
     uint64_t capacity = 0;
@@ -114,10 +120,8 @@ struct sjmi_ctx {
     bool profiling = false;  // bracket every stage-1 kernel with HIP events (bench.py roofline)
     std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
     size_t events_used = 0;
-    DevBuf<void> d_plan;                     // sjmi_select_batch_device: the plan the last call used, as k_select reads it
-    uint64_t plan_serial = 0;                // ... and which one it is (0: none)
-    DevBuf<void> d_explode_plan;             // sjmi_explode_batch_device: a plan slot of its own (select and explode calls alternate)
-    uint64_t explode_serial = 0;
+    PlanSlot select_plan;                    // sjmi_select_batch_device: the plan the last call used, as k_select reads it
+    PlanSlot explode_plan;                   // sjmi_explode_batch_device: a slot of its own (select and explode calls alternate)
     DevBuf<void> d_ws_explode;               // ... and its per-document scratch: row counts, base tape indexes, chunk sums
     DevBuf<void> d_ws_ndjson;                // sjmi_ndjson_offsets_device: a state and a count per tile
     DevBuf<unsigned long long> d_nd_offsets; // sjmi_ndjson_offsets (host form): the offsets and the result record on the device
@@ -181,6 +185,28 @@ bool grow(sjmi_ctx* c, Buf<T, Host>& b, size_t need, const char* what) {
     b.bytes = need;
     return true;
 }
+// a per-call scratch of at least `bytes`.  When the scratch grows, a launch of an earlier call may still be using the old
+// one: the device is drained before it is released.
+bool grow_scratch(sjmi_ctx* c, DevBuf<void>& buf, size_t bytes, const char* what) {
+    if (bytes <= buf.bytes) return true;
+    if (buf.p && fail(c, "sync", hipDeviceSynchronize())) return false;
+    return grow(c, buf, bytes, what);
+}
+// `slot` holds the plan `serial` behind this (what: its name in an error).  If that is another plan than the one on the device,
+// a launch of the old one may still be reading it: the device is drained first, and the slot names no plan until the blocking
+// copy has ended.
+bool upload_plan(sjmi_ctx* c, PlanSlot& slot, const void* image, size_t bytes, uint64_t serial, const char* what) {
+    if (slot.serial == serial) return true;
+    slot.serial = 0;
+    if (slot.d.p && fail(c, "sync", hipDeviceSynchronize())) return false;
+    const std::string name = std::string("(") + what + ")";
+    if (!grow(c, slot.d, bytes, ("hipMalloc" + name).c_str()) || fail(c, ("H2D" + name).c_str(), hipMemcpy(slot.d, image, bytes, hipMemcpyHostToDevice)))
+        return false;
+    slot.serial = serial;
+    return true;
+}
+// the caller's stream, or the context's own
+hipStream_t stream_of(const sjmi_ctx* c, void* stream) { return stream ? (hipStream_t)stream : c->stream; }
 // the stage-1 granule (4 KiB steps per workgroup) for `len` bytes: sjmi_set_tile_steps, else the library's choice
 int stage1_steps(const sjmi_ctx* c, uint64_t len) { return c->forced_steps ? c->forced_steps : sjmi::stage1_pick_steps(len); }
 // the index capacity of a host-form call on the device: the context's array holds capacity + 2 entries
@@ -457,7 +483,7 @@ static int stage1_device_impl(sjmi_ctx* c, const void* d_buf, uint64_t len, void
     if (fail(c, "hipSetDevice", hipSetDevice(c->device))) return SJMI_ERR_HIP;
     Stage1Opts none;
     Stage1Opts& o = opts ? *opts : none;
-    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    hipStream_t st = stream_of(c, stream);
     const int steps = stage1_steps(c, len);
     const size_t need = (sjmi::stage1_workspace_bytes(len, steps) + 255) & ~(size_t)255;
     if (2 * need > c->d_ws_dev.bytes) {  // grown outside any timed loop on first use of a given size
@@ -662,7 +688,7 @@ static int unescape_device_impl(sjmi_ctx* c, const void* d_buf, uint64_t len, co
                                 const sjmi::UnescapeBatch& batch) {
     if (!c || !d_buf || !d_indexes || !d_string_buffer || !d_result || len >= (1ull << 32)) return SJMI_ERR_ARG;
     if (fail(c, "hipSetDevice", hipSetDevice(c->device))) return SJMI_ERR_HIP;
-    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    hipStream_t st = stream_of(c, stream);
     if (!batch.d_doc_offsets) {
         if (((uintptr_t)d_buf & 15)) return SJMI_ERR_ARG;
         return strings_device_impl(c, d_buf, len, d_string_buffer, string_capacity, nullptr, 0, nullptr, d_result, st);
@@ -879,7 +905,7 @@ int sjmi_walk_batch_device(sjmi_ctx* c, const void* d_buf, const void* d_doc_off
         return SJMI_ERR_ARG;
     if (fail(c, "hipSetDevice", hipSetDevice(c->device))) return SJMI_ERR_HIP;
     if (!grow(c, c->d_ws_walk, sjmi::walk_workspace_bytes(count, n_docs), "hipMalloc(ws_walk)")) return SJMI_ERR_HIP;
-    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    hipStream_t st = stream_of(c, stream);
     // The cooperative walker takes the offsets of the string records from the record table the string pass of THESE indexes
     // left on this context (sjmi_unescape_batch_device), and the ordinal of every document's first string with it.
     if (!c->soff_idx || c->soff_idx != d_indexes) {
@@ -919,17 +945,10 @@ int sjmi_select_batch_device(sjmi_ctx* c, const sjmi_select_plan* plan, const vo
     const void* image = sjmi::select_plan_image(plan, &bytes, &serial, &n_paths);
     if (n_docs && n_paths && (!d_tape || !d_tape_offsets || !d_doc_errors || !d_string_buffer || !d_types || !d_values)) return SJMI_ERR_ARG;
     if (fail(c, "hipSetDevice", hipSetDevice(c->device))) return SJMI_ERR_HIP;
-    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
-    if (c->plan_serial != serial) {
-        // another plan than the one on the device: a launch of the old one may still be reading it
-        c->plan_serial = 0;
-        if (c->d_plan.p && fail(c, "sync", hipDeviceSynchronize())) return SJMI_ERR_HIP;
-        if (!grow(c, c->d_plan, bytes, "hipMalloc(plan)") || fail(c, "H2D(plan)", hipMemcpy(c->d_plan, image, bytes, hipMemcpyHostToDevice)))
-            return SJMI_ERR_HIP;
-        c->plan_serial = serial;
-    }
+    hipStream_t st = stream_of(c, stream);
+    if (!upload_plan(c, c->select_plan, image, bytes, serial, "plan")) return SJMI_ERR_HIP;
     if (!n_paths) return SJMI_OK;
-    return fail(c, "select launch", sjmi::select_launch(c->d_plan, bytes, d_tape, d_tape_offsets, d_doc_errors, d_string_buffer, n_docs,
+    return fail(c, "select launch", sjmi::select_launch(c->select_plan.d, bytes, d_tape, d_tape_offsets, d_doc_errors, d_string_buffer, n_docs,
                                                         d_types, d_values, st))
                ? SJMI_ERR_HIP
                : SJMI_OK;
@@ -947,23 +966,11 @@ int sjmi_explode_batch_device(sjmi_ctx* c, const sjmi_explode_plan* plan, const 
     if (row_capacity && n_paths && (!d_types || !d_values)) return SJMI_ERR_ARG;
     if (n_paths && row_capacity > ~0ull / 8 / n_paths) return SJMI_ERR_ARG;
     if (fail(c, "hipSetDevice", hipSetDevice(c->device))) return SJMI_ERR_HIP;
-    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
-    if (c->explode_serial != serial) {
-        // another plan than the one on the device: a launch of the old one may still be reading it
-        c->explode_serial = 0;
-        if (c->d_explode_plan.p && fail(c, "sync", hipDeviceSynchronize())) return SJMI_ERR_HIP;
-        if (!grow(c, c->d_explode_plan, bytes, "hipMalloc(explode plan)") ||
-            fail(c, "H2D(explode plan)", hipMemcpy(c->d_explode_plan, image, bytes, hipMemcpyHostToDevice)))
-            return SJMI_ERR_HIP;
-        c->explode_serial = serial;
-    }
-    const size_t ws = sjmi::explode_workspace_bytes(n_docs);
-    if (ws > c->d_ws_explode.bytes) {
-        // the scratch grows: a launch of an earlier call may still be using the old one
-        if (c->d_ws_explode.p && fail(c, "sync", hipDeviceSynchronize())) return SJMI_ERR_HIP;
-        if (!grow(c, c->d_ws_explode, ws, "hipMalloc(ws_explode)")) return SJMI_ERR_HIP;
-    }
-    return fail(c, "explode launch", sjmi::explode_launch(c->d_explode_plan, bytes, base_bytes, n_paths, d_tape, d_tape_offsets, d_doc_errors,
+    hipStream_t st = stream_of(c, stream);
+    if (!upload_plan(c, c->explode_plan, image, bytes, serial, "explode plan") ||
+        !grow_scratch(c, c->d_ws_explode, sjmi::explode_workspace_bytes(n_docs), "hipMalloc(ws_explode)"))
+        return SJMI_ERR_HIP;
+    return fail(c, "explode launch", sjmi::explode_launch(c->explode_plan.d, bytes, base_bytes, n_paths, d_tape, d_tape_offsets, d_doc_errors,
                                                           d_string_buffer, n_docs, c->d_ws_explode, d_row_offsets, row_capacity, d_types,
                                                           d_values, st))
                ? SJMI_ERR_HIP
@@ -977,13 +984,8 @@ int sjmi_ndjson_offsets_device(sjmi_ctx* c, const void* d_buf, uint64_t len, voi
     if (!c || !d_result || (len && !d_buf) || (offset_capacity && !d_doc_offsets) || len >= (1ull << 46)) return SJMI_ERR_ARG;
     if (((uintptr_t)d_doc_offsets & 7) || ((uintptr_t)d_result & 7)) return SJMI_ERR_ARG;
     if (fail(c, "hipSetDevice", hipSetDevice(c->device))) return SJMI_ERR_HIP;
-    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
-    const size_t ws = sjmi::ndjson_workspace_bytes(len);
-    if (ws > c->d_ws_ndjson.bytes) {
-        // the scratch grows: a launch of an earlier call may still be using the old one
-        if (c->d_ws_ndjson.p && fail(c, "sync", hipDeviceSynchronize())) return SJMI_ERR_HIP;
-        if (!grow(c, c->d_ws_ndjson, ws, "hipMalloc(ws_ndjson)")) return SJMI_ERR_HIP;
-    }
+    hipStream_t st = stream_of(c, stream);
+    if (!grow_scratch(c, c->d_ws_ndjson, sjmi::ndjson_workspace_bytes(len), "hipMalloc(ws_ndjson)")) return SJMI_ERR_HIP;
     return fail(c, "ndjson launch", sjmi::ndjson_launch(d_buf, len, d_doc_offsets, offset_capacity, d_result, c->d_ws_ndjson, st))
                ? SJMI_ERR_HIP
                : SJMI_OK;
@@ -995,13 +997,8 @@ int sjmi_string_column_device(sjmi_ctx* c, const void* d_types, const void* d_va
     if (((uintptr_t)d_values & 7) || ((uintptr_t)d_offsets & 7) || ((uintptr_t)d_validity & 7) || ((uintptr_t)d_result & 7)) return SJMI_ERR_ARG;
     if (n_rows >= (1ull << 40)) return SJMI_ERR_ARG;  // (one workgroup per 1024 rows, one wave per 64)
     if (fail(c, "hipSetDevice", hipSetDevice(c->device))) return SJMI_ERR_HIP;
-    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
-    const size_t ws = sjmi::strcol_workspace_bytes(n_rows);
-    if (ws > c->d_ws_strcol.bytes) {
-        // the scratch grows: a launch of an earlier call may still be using the old one
-        if (c->d_ws_strcol.p && fail(c, "sync", hipDeviceSynchronize())) return SJMI_ERR_HIP;
-        if (!grow(c, c->d_ws_strcol, ws, "hipMalloc(ws_strcol)")) return SJMI_ERR_HIP;
-    }
+    hipStream_t st = stream_of(c, stream);
+    if (!grow_scratch(c, c->d_ws_strcol, sjmi::strcol_workspace_bytes(n_rows), "hipMalloc(ws_strcol)")) return SJMI_ERR_HIP;
     return fail(c, "string column launch", sjmi::strcol_launch(d_types, d_values, n_rows, d_string_buffer, d_offsets, d_validity, d_bytes,
                                                                byte_capacity, d_result, c->d_ws_strcol, st))
                ? SJMI_ERR_HIP
@@ -1020,13 +1017,8 @@ int sjmi_filter_columns_device(sjmi_ctx* c, const sjmi_filter_plan* plan, const 
         return SJMI_ERR_ARG;
     if (n_cols && (col_stride > ~0ull / 8 / n_cols || out_capacity > ~0ull / 8 / n_cols)) return SJMI_ERR_ARG;  // (a column set is addressable)
     if (fail(c, "hipSetDevice", hipSetDevice(c->device))) return SJMI_ERR_HIP;
-    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
-    const size_t ws = sjmi::filter_workspace_bytes(n_rows);
-    if (ws > c->d_ws_filter.bytes) {
-        // the scratch grows: a launch of an earlier call may still be using the old one
-        if (c->d_ws_filter.p && fail(c, "sync", hipDeviceSynchronize())) return SJMI_ERR_HIP;
-        if (!grow(c, c->d_ws_filter, ws, "hipMalloc(ws_filter)")) return SJMI_ERR_HIP;
-    }
+    hipStream_t st = stream_of(c, stream);
+    if (!grow_scratch(c, c->d_ws_filter, sjmi::filter_workspace_bytes(n_rows), "hipMalloc(ws_filter)")) return SJMI_ERR_HIP;
     return fail(c, "filter launch", sjmi::filter_launch(plan, d_types, d_values, n_cols, col_stride, n_rows, d_string_buffer, d_keep, d_rows,
                                                         out_capacity, d_out_types, d_out_values, d_result, c->d_ws_filter, st))
                ? SJMI_ERR_HIP
@@ -1088,7 +1080,7 @@ int sjmi_stage1_masks_device(sjmi_ctx* c, const void* d_buf, uint64_t len, void*
     if (mask_capacity_blocks < len / 64 + 1) return SJMI_ERR_CAPACITY;
     if (fail(c, "hipSetDevice", hipSetDevice(c->device))) return SJMI_ERR_HIP;
     if (!grow(c, c->d_ws_masks, sjmi::masks_workspace_bytes(len), "hipMalloc(ws_masks)")) return SJMI_ERR_HIP;
-    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    hipStream_t st = stream_of(c, stream);
     if (fail(c, "masks launch", sjmi::masks_launch((const uint8_t*)d_buf, len, (unsigned long long*)d_masks, c->d_ws_masks, st)))
         return SJMI_ERR_HIP;
     return SJMI_OK;
@@ -1121,7 +1113,7 @@ int sjmi_stage1_batch_device(sjmi_ctx* c, const void* d_buf, uint64_t total_len,
     if (!c || !d_doc_offsets || !d_index_offsets) return SJMI_ERR_ARG;
     int rc = sjmi_stage1_device(c, d_buf, total_len, d_indexes, index_capacity, d_result, stream);
     if (rc != SJMI_OK) return rc;
-    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    hipStream_t st = stream_of(c, stream);
     if (fail(c, "split launch",
              sjmi::split_docs_launch((const uint32_t*)d_indexes, (const sjmi::Stage1Result*)d_result,
                                      (const unsigned long long*)d_doc_offsets, n_docs,
@@ -1185,7 +1177,7 @@ static int stage1_batch_isolated_device_impl(sjmi_ctx* c, const void* d_buf, uin
         c->par_valid = false;
         c->accept_valid = false;
     }
-    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    hipStream_t st = stream_of(c, stream);
     if (fail(c, "isolated batch launch",
              sjmi::batch_isolated_launch((const uint8_t*)d_buf, (const unsigned long long*)d_doc_offsets, n_docs,
                                          (uint32_t*)d_indexes, index_capacity, (unsigned long long*)d_index_offsets,
@@ -1206,7 +1198,7 @@ static int stage1_batch_optimistic(sjmi_ctx* c, const void* d_buf, uint64_t tota
     if (!c || !d_buf || !d_doc_offsets || !d_indexes || !d_index_offsets || !d_doc_status || !d_result) return SJMI_ERR_ARG;
     if (total_len >= (1ull << 32)) return SJMI_ERR_ARG;
     static const bool optimistic = !(getenv("SJMI_BATCH_OPTIMISTIC") && atoi(getenv("SJMI_BATCH_OPTIMISTIC")) == 0);
-    hipStream_t st0 = stream ? (hipStream_t)stream : c->stream;
+    hipStream_t st0 = stream_of(c, stream);
     const uint32_t* d_skip = nullptr;
     c->accept_valid = false;
     if (optimistic && n_docs && total_len && index_capacity >= 1 && !((uintptr_t)d_buf & 15) && !((uintptr_t)d_indexes & 15)) {
@@ -1323,7 +1315,7 @@ static int parse_batch_pipeline(sjmi_ctx* c, const void* d_buf, uint64_t total_l
     if (fail(c, "hipSetDevice", hipSetDevice(c->device))) return SJMI_ERR_HIP;
     const bool optimistic_only = mode == PIPE_OPTIMISTIC;
     sjmi_batch_result* r = (sjmi_batch_result*)d_result;
-    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    hipStream_t st = stream_of(c, stream);
     const uint64_t bound = index_capacity - 1;
     const uint64_t soff_cap = bound + 64;
     static const bool optimistic = !(getenv("SJMI_BATCH_OPTIMISTIC") && atoi(getenv("SJMI_BATCH_OPTIMISTIC")) == 0);
@@ -1950,7 +1942,7 @@ void sjmi_split_close(sjmi_split* s) {
 }
 static int split_scan(sjmi_split* s, int entry_parity, void* stream) {
     sjmi_ctx* c = s->c;
-    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    hipStream_t st = stream_of(c, stream);
     const int rc = sjmi_stage1_shard_device2(c, s->d_shard, s->len, s->halo, s->halo_from_start, s->is_last, entry_parity, s->d_indexes,
                                              s->index_capacity, s->d_res, stream);
     if (rc != SJMI_OK) return rc;

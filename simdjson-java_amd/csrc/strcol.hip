@@ -1,7 +1,7 @@
 // strcol.hip -- one string column of the selector's encoding gathered into Arrow offsets, validity and bytes (include/sjmi.h,
 // sjmi_string_column_device).  The passes are sj_strcol.h (shared with the host simulation, tests/host_sim/
-// strcol_sim.cpp); this file is the device form of its lane primitives and four plain kernels that the stream orders -- no
-// workgroup waits for another:
+// strcol_sim.cpp), the device forms of its lane groups are WgGroup and WaveGroup of sj_group.h; this file is four plain kernels
+// that the stream orders -- no workgroup waits for another:
 //   k_strcol_chunk_sums   one workgroup per 1024 rows: the bytes, the VALID rows and the other-typed rows of the chunk; the
 //                         validity words (a wave is 64 consecutive rows: its ballot is one word)
 //   k_strcol_chunk_scan   ONE workgroup: the bytes in front of every chunk (in place), offsets[n_rows], the result record
@@ -10,7 +10,7 @@
 // The scans are block_excl_scan / block_scan_in_place of sj_chain.h, as in walk.hip and explode.hip.
 #include <hip/hip_runtime.h>
 
-#include "sj_chain.h"
+#include "sj_group.h"
 #include "sj_strcol.h"
 #include "stage1.h"
 
@@ -24,45 +24,22 @@ namespace {
 constexpr uint32_t SC_COPY_BLOCK = 256;  // four waves = 256 rows per workgroup of the copy
 static_assert(SC_CHUNK_ROWS == 1024, "block_scan_in_place takes slices of 1024 entries with 1024 threads");
 
-// the lanes of a workgroup (sj_strcol.h)
-struct WgLanes {
-    unsigned long long* s_wave;  // one entry per wave
-    __device__ __forceinline__ uint32_t lanes() const { return blockDim.x; }
-    __device__ __forceinline__ uint32_t lane() const { return threadIdx.x; }
-    __device__ __forceinline__ sj_u64 scan_add(sj_u64 v, sj_u64* total) const { return block_excl_scan(v, s_wave, total); }
-    __device__ __forceinline__ sj_u64 scan_in_place(sj_u64* sums, sj_u64 n) const { return block_scan_in_place(sums, n, s_wave); }
-    // (r is a multiple of 64 in lane 0 of a wave, and that row is live iff any of the wave's is)
-    __device__ __forceinline__ void validity_bit(sj_u64* words, sj_u64 r, bool live, bool flag) const {
-        const sj_u64 word = __ballot(live && flag);
-        if ((threadIdx.x & 63u) == 0 && live) words[r >> 6] = word;
-    }
-};
-
-// one wave and its LDS (sj_strcol.h)
-struct WaveLanes {
-    template <class F>
-    __device__ __forceinline__ void each(F f) const {
-        f(threadIdx.x & 63u);
-    }
-    __device__ __forceinline__ void fence() const { wave_lds_fence(); }
-};
-
 __global__ __launch_bounds__(SC_CHUNK_ROWS) void k_strcol_chunk_sums(ScColumn c, sj_u64* __restrict__ validity, ScSums sums) {
     __shared__ unsigned long long s_wave[SC_CHUNK_ROWS / 64];
-    const WgLanes g = {s_wave};
+    const WgGroup g = {s_wave};
     sc_chunk_sums(g, c, blockIdx.x, validity, sums);
 }
 
 __global__ __launch_bounds__(1024) void k_strcol_chunk_scan(ScSums sums, uint64_t nchunks, uint64_t n_rows, sj_u64* __restrict__ offsets,
                                                             uint64_t byte_capacity, ScResult* __restrict__ res) {
     __shared__ unsigned long long s_wave[16];
-    const WgLanes g = {s_wave};
+    const WgGroup g = {s_wave};
     sc_chunk_scan(g, sums, nchunks, n_rows, offsets, byte_capacity, res);
 }
 
 __global__ __launch_bounds__(SC_CHUNK_ROWS) void k_strcol_offsets(ScColumn c, ScSums sums, sj_u64* __restrict__ offsets) {
     __shared__ unsigned long long s_wave[SC_CHUNK_ROWS / 64];
-    const WgLanes g = {s_wave};
+    const WgGroup g = {s_wave};
     sc_offsets(g, c, blockIdx.x, sums, offsets);
 }
 
@@ -72,7 +49,7 @@ __global__ __launch_bounds__(SC_COPY_BLOCK) void k_strcol_copy(ScColumn c, uint6
     __shared__ ScWave s_waves[SC_COPY_BLOCK / 64];
     const uint64_t wave = (uint64_t)blockIdx.x * (SC_COPY_BLOCK / 64) + (threadIdx.x >> 6);
     if (wave >= nwaves) return;  // (wave-uniform; the kernel has no workgroup barrier)
-    const WaveLanes w;
+    const WaveGroup w;
     sc_copy_wave(w, c, wave, offsets, sb, bytes, byte_capacity, s_waves[threadIdx.x >> 6]);
 }
 

@@ -1,52 +1,14 @@
 // Host simulation of explode (simdjson-java_amd/csrc/explode.hip): sj_select.h, the header the kernels compile verbatim, with
-// the group primitives in their sequential form.  TEST ONLY: lets the CPU suite check what k_explode_count and k_explode_rows
-// run per document (the base pointer's walk, the iterator chain's count, the element plan from every element) against the
-// oracle without a GPU.  The prefix sum and the capacity rule are restated here in plain loops.
+// the group primitives in their sequential form (seq_group.h).  TEST ONLY: lets the CPU suite check what k_explode_count and
+// k_explode_rows run per document (the base pointer's walk, the iterator chain's count, the element plan from every element)
+// against the oracle without a GPU.  The prefix sum and the capacity rule are restated here in plain loops.
 // sim_explode_guarded runs the same with every tape and every document's last string record placed against a PROT_NONE page.
 // Built by tests/test_host_explode.py with g++.
-#include <sys/mman.h>
-#include <unistd.h>
-
 #include <vector>
 #include "../../simdjson-java_amd/csrc/sj_select.h"
-
-struct SeqLanes {
-    uint32_t stride_first() const { return 0; }
-    uint32_t stride() const { return 1; }
-    void fence() const {}
-    template <class F>
-    uint32_t ballot(F f) const {
-        uint32_t m = 0;
-        for (uint32_t j = SEL_GROUP; j-- > 0;)  // (any order must do: the lanes are independent)
-            m |= (f(j) ? 1u : 0u) << j;
-        return m;
-    }
-};
+#include "seq_group.h"
 
 namespace {
-struct Guarded {
-    uint8_t* map = nullptr;
-    size_t bytes = 0;  // readable bytes in front of the guard page
-    size_t page = 0;
-    bool open(size_t need) {
-        page = (size_t)sysconf(_SC_PAGESIZE);
-        bytes = (need + page - 1) / page * page + page;
-        void* m = mmap(nullptr, bytes + page, PROT_READ | PROT_WRITE, MAP_PRIVATE | MAP_ANONYMOUS, -1, 0);
-        if (m == MAP_FAILED) return false;
-        map = (uint8_t*)m;
-        return mprotect(map + bytes, page, PROT_NONE) == 0;
-    }
-    uint8_t* place(const void* src, size_t n) {  // -> the copy, ending at the guard page
-        memset(map, 0xA5, bytes);
-        uint8_t* at = map + bytes - n;
-        if (n) memcpy(at, src, n);
-        return at;
-    }
-    ~Guarded() {
-        if (map) munmap(map, bytes + page);
-    }
-};
-
 // sb_offsets != nullptr: the guarded form
 int explode(const uint8_t* base, uint64_t base_len, const uint8_t* pointers, const uint64_t* pointer_offsets, uint64_t n_paths,
             const uint64_t* tape, const uint64_t* tape_offsets, const int32_t* doc_errors, const uint8_t* sb, const uint64_t* sb_offsets,
@@ -65,7 +27,7 @@ int explode(const uint8_t* base, uint64_t base_len, const uint8_t* pointers, con
         }
         if (!gt.open(max_words * 8) || !gs.open(max_sb)) return -3;
     }
-    SeqLanes g;
+    SeqLanes<SEL_GROUP> g;
     SelScratch* s = new SelScratch;
     std::vector<uint32_t> counts(n_docs), bases(n_docs);
     // the document's memory for one pass: a copy of exactly its words (a read outside them is a read outside an allocation),

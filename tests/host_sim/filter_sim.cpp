@@ -1,72 +1,14 @@
 // Host simulation of the row filter (simdjson-java_amd/csrc/filter.hip): sj_filter.h, the header the kernels compile verbatim,
-// with the lane primitives in their sequential form -- ONE wave per chunk whose 64 lanes run one after the other (a ballot
+// with the lane primitives in their sequential form (seq_group.h) -- ONE wave per chunk whose 64 lanes run one after the other (a ballot
 // collects their answers, every scan is empty and every total the wave's own value).
 // TEST ONLY: lets the CPU suite check the three passes against the reference of tests/filter_common.py without a GPU, at any
 // chunk size.  The string buffer is placed so that it ENDS at a page that cannot be read: one use of a value word that is no
 // string's as an offset, or one byte read behind a string that ends the buffer, is a SIGSEGV here and not a fault on a GPU.
 // Built by tests/test_host_filter.py with g++.
-#include <string.h>
-#include <sys/mman.h>
-#include <unistd.h>
-
 #include <vector>
 
 #include "../../simdjson-java_amd/csrc/sj_filter.h"
-
-struct SeqWaves {
-    uint32_t waves() const { return 1; }
-    uint32_t wave() const { return 0; }
-    uint32_t lane() const { return 0; }
-    bool first() const { return true; }
-    template <class F>
-    sj_u64 ballot(F f) const {
-        sj_u64 w = 0;
-        for (uint32_t t = 64; t-- > 0;)  // (any order must do: the lanes of a ballot are independent)
-            if (f(t)) w |= 1ull << t;
-        return w;
-    }
-    template <class F>
-    void each(F f) const {
-        for (uint32_t t = 64; t-- > 0;) f(t);
-    }
-    sj_u64 scan_add(sj_u64 v, sj_u64* total) const {
-        *total = v;
-        return 0;
-    }
-    sj_u64 scan_in_place(sj_u64* sums, sj_u64 n) const {
-        sj_u64 run = 0;
-        for (sj_u64 i = 0; i < n; ++i) {
-            const sj_u64 v = sums[i];
-            sums[i] = run;
-            run += v;
-        }
-        return run;
-    }
-};
-
-namespace {
-struct Guarded {
-    uint8_t* map = nullptr;
-    size_t bytes = 0, page = 0;
-    bool open(size_t need) {
-        page = (size_t)sysconf(_SC_PAGESIZE);
-        bytes = (need + page - 1) / page * page + page;
-        void* m = mmap(nullptr, bytes + page, PROT_READ | PROT_WRITE, MAP_PRIVATE | MAP_ANONYMOUS, -1, 0);
-        if (m == MAP_FAILED) return false;
-        map = (uint8_t*)m;
-        return mprotect(map + bytes, page, PROT_NONE) == 0;
-    }
-    uint8_t* place(const void* src, size_t n) {  // -> the copy, ending at the guard page
-        memset(map, 0xA5, bytes);
-        uint8_t* at = map + bytes - n;
-        if (n) memcpy(at, src, n);
-        return at;
-    }
-    ~Guarded() {
-        if (map) munmap(map, bytes + page);
-    }
-};
-}  // namespace
+#include "seq_group.h"
 
 extern "C" {
 
@@ -92,7 +34,7 @@ int sim_filter(const void* terms, uint64_t n_terms, const uint8_t* bytes, uint64
     std::vector<sj_u64> ws(nchunks + fl_words(c) + 1, 0xA5A5A5A5A5A5A5A5ull);  // (the scratch is not zero on the device either)
     sj_u64* counts = ws.data();
     sj_u64* words = keep ? (sj_u64*)keep : counts + nchunks;
-    const SeqWaves g;
+    const SeqGroup g;
     for (sj_u64 k = 0; k < nchunks; ++k) fl_eval_chunk(g, plan, c, k, words, counts);
     FlResult res;
     fl_chunk_scan(g, counts, nchunks, out_capacity, &res);

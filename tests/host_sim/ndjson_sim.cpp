@@ -1,26 +1,18 @@
 // Host simulation of the NDJSON splitter (simdjson-java_amd/csrc/ndjson.hip): sj_ndjson.h, the header the kernels compile
-// verbatim, with the lane primitives in their sequential form (ONE lane: every scan is empty, every total the lane's own value).
-// TEST ONLY: lets the CPU suite check the three passes -- tile summaries, their scan, the emit -- against the reference of
-// tests/ndjson_common.py without a GPU, at any tile size.  Built by tests/test_host_ndjson.py with g++.
-#include <string.h>
-
+// verbatim, with the lane primitives in their sequential form (seq_group.h; ONE lane: every scan is empty, every total the
+// lane's own value).  TEST ONLY: lets the CPU suite check the three passes -- tile summaries, their scan, the emit -- against
+// the reference of tests/ndjson_common.py without a GPU, at any tile size.  Built by tests/test_host_ndjson.py with g++.
 #include <vector>
 
 #include "../../simdjson-java_amd/csrc/sj_ndjson.h"
+#include "seq_group.h"
 
-struct SeqLane {
-    uint32_t lanes() const { return 1; }
-    uint32_t lane() const { return 0; }
+struct NdSeq : SeqGroup {  // ... and what is NdState's own
     void load(const uint8_t* p, uint32_t w[16]) const { memcpy(w, p, 64); }  // (little-endian host)
     NdState scan_state(NdState v, NdState* total) const {
         *total = v;
         return 0;
     }
-    sj_u64 scan_add(sj_u64 v, sj_u64* total) const {
-        *total = v;
-        return 0;
-    }
-    bool any(bool flag) const { return flag; }
 };
 
 extern "C" {
@@ -37,7 +29,7 @@ int sim_ndjson(const uint8_t* buf, uint64_t len, uint32_t shift, uint32_t tile_b
     uint8_t* base = store.data() + ((16 - ((uintptr_t)store.data() & 15)) & 15);
     for (size_t i = 0; base + i < store.data() + store.size(); ++i) base[i] = fill[i % fill_len];
     if (len) memcpy(base + shift, buf, len);
-    const SeqLane g;
+    const NdSeq g;
     const NdGeom ge = nd_geom(base + shift, len, tile_bytes / 64);
     const sj_u64 ntiles = nd_tiles(ge);
     std::vector<NdTile> tiles(ntiles + 1);

@@ -1,24 +1,12 @@
 // Host simulation of the device-resident selector (simdjson-java_amd/csrc/select.hip): sj_select.h, the header the kernel
-// compiles verbatim, with the group primitives in their sequential form -- the cooperative copy done by one "lane", the
-// ballot a loop over the sixteen lanes.  TEST ONLY: lets the CPU suite check the walk the kernel runs (the trie, the chain,
-// first-match, the slice and the global path) against the oracle's JsonValue walk without a GPU.
+// compiles verbatim, with the group primitives in their sequential form (seq_group.h) -- the cooperative copy done by one
+// "lane", the ballot a loop over the sixteen lanes.  TEST ONLY: lets the CPU suite check the walk the kernel runs (the trie,
+// the chain, first-match, the slice and the global path) against the oracle's JsonValue walk without a GPU.
 // sim_select_guarded (below) runs the same walk with every tape and string record placed against a PROT_NONE page.
 // Built by tests/test_host_select.py with g++.
 #include <vector>
 #include "../../simdjson-java_amd/csrc/sj_select.h"
-
-struct SeqLanes {
-    uint32_t stride_first() const { return 0; }
-    uint32_t stride() const { return 1; }
-    void fence() const {}
-    template <class F>
-    uint32_t ballot(F f) const {
-        uint32_t m = 0;
-        for (uint32_t j = SEL_GROUP; j-- > 0;)  // (any order must do: the lanes are independent)
-            m |= (f(j) ? 1u : 0u) << j;
-        return m;
-    }
-};
+#include "seq_group.h"
 
 extern "C" uint32_t sim_select_slice_words(void) { return SEL_SLICE_WORDS; }
 
@@ -30,7 +18,7 @@ extern "C" int sim_select(const uint8_t* pointers, const uint64_t* pointer_offse
     std::vector<sj_u64> image;
     if (!sel_compile(pointers, pointer_offsets, n_paths, &image)) return -2;
     const SelHeader* plan = (const SelHeader*)image.data();
-    SeqLanes g;
+    SeqLanes<SEL_GROUP> g;
     SelScratch* s = new SelScratch;
     for (uint64_t k = 0; k < n_docs; ++k) {
         memset(s, 0xA5, sizeof *s);  // (LDS is not zero on the device either)
@@ -57,34 +45,6 @@ extern "C" int sim_select(const uint8_t* pointers, const uint64_t* pointer_offse
 // string buffer, [sb_offsets[k], sb_ends[k]), so that its LAST RECORD ends at one: a load that leaves the tape or the key it
 // belongs to by a single byte is a SIGSEGV.  (What lies in front of the copies is readable: the walk only ever moves forward.)
 // Host only; tests/test_host_select_fuzz.py runs it in a child process and asserts on how that ends.
-#include <sys/mman.h>
-#include <unistd.h>
-
-namespace {
-struct Guarded {
-    uint8_t* map = nullptr;
-    size_t bytes = 0;   // readable bytes in front of the guard page
-    size_t page = 0;
-    bool open(size_t need) {
-        page = (size_t)sysconf(_SC_PAGESIZE);
-        bytes = (need + page - 1) / page * page + page;
-        void* m = mmap(nullptr, bytes + page, PROT_READ | PROT_WRITE, MAP_PRIVATE | MAP_ANONYMOUS, -1, 0);
-        if (m == MAP_FAILED) return false;
-        map = (uint8_t*)m;
-        return mprotect(map + bytes, page, PROT_NONE) == 0;
-    }
-    uint8_t* place(const void* src, size_t n) {  // -> the copy, ending at the guard page
-        memset(map, 0xA5, bytes);
-        uint8_t* at = map + bytes - n;
-        if (n) memcpy(at, src, n);
-        return at;
-    }
-    ~Guarded() {
-        if (map) munmap(map, bytes + page);
-    }
-};
-}  // namespace
-
 // as sim_select; document k's string records are sb[sb_offsets[k], sb_ends[k]).  -> 0, -2 (the plan), -3 (no memory)
 extern "C" int sim_select_guarded(const uint8_t* pointers, const uint64_t* pointer_offsets, uint64_t n_paths, const uint64_t* tape,
                                   const uint64_t* tape_offsets, const int32_t* doc_errors, const uint8_t* sb, const uint64_t* sb_offsets,
@@ -99,7 +59,7 @@ extern "C" int sim_select_guarded(const uint8_t* pointers, const uint64_t* point
     }
     Guarded gt, gs;
     if (!gt.open(max_words * 8) || !gs.open(max_sb)) return -3;
-    SeqLanes g;
+    SeqLanes<SEL_GROUP> g;
     SelScratch* s = new SelScratch;
     for (uint64_t k = 0; k < n_docs; ++k) {
         memset(s, 0xA5, sizeof *s);

@@ -1,72 +1,14 @@
 // Host simulation of the string-column gather (simdjson-java_amd/csrc/strcol.hip): sj_strcol.h, the header the kernels compile
-// verbatim, with the lane primitives in their sequential form -- ONE lane for the three scan passes (every scan is empty, every
+// verbatim, with the lane primitives in their sequential form (seq_group.h) -- ONE lane for the three scan passes (every scan is empty, every
 // total the lane's own value, a validity bit is set on its own), and for the copy a wave whose 64 lanes run one after the other.
 // TEST ONLY: lets the CPU suite check the four passes against the reference of tests/strcol_common.py without a GPU, at any
 // chunk size.  The string buffer is placed so that it ENDS at a page that cannot be read: one dereference of a NULL row's value
 // word, or one byte read behind a string that ends the buffer, is a SIGSEGV here and not a fault on a GPU.
 // Built by tests/test_host_strcol.py with g++.
-#include <string.h>
-#include <sys/mman.h>
-#include <unistd.h>
-
 #include <vector>
 
 #include "../../simdjson-java_amd/csrc/sj_strcol.h"
-
-struct SeqLane {
-    uint32_t lanes() const { return 1; }
-    uint32_t lane() const { return 0; }
-    sj_u64 scan_add(sj_u64 v, sj_u64* total) const {
-        *total = v;
-        return 0;
-    }
-    sj_u64 scan_in_place(sj_u64* sums, sj_u64 n) const {
-        sj_u64 run = 0;
-        for (sj_u64 i = 0; i < n; ++i) {
-            const sj_u64 v = sums[i];
-            sums[i] = run;
-            run += v;
-        }
-        return run;
-    }
-    void validity_bit(sj_u64* words, sj_u64 r, bool live, bool flag) const {
-        if (!live) return;
-        if (!(r & 63)) words[r >> 6] = 0;  // (rows come in order: the first live row of a word clears it)
-        if (flag) words[r >> 6] |= 1ull << (r & 63);
-    }
-};
-
-struct SeqWave {
-    template <class F>
-    void each(F f) const {
-        for (uint32_t t = 64; t-- > 0;) f(t);  // (any order must do: between two fences the lanes are independent)
-    }
-    void fence() const {}
-};
-
-namespace {
-struct Guarded {
-    uint8_t* map = nullptr;
-    size_t bytes = 0, page = 0;
-    bool open(size_t need) {
-        page = (size_t)sysconf(_SC_PAGESIZE);
-        bytes = (need + page - 1) / page * page + page;
-        void* m = mmap(nullptr, bytes + page, PROT_READ | PROT_WRITE, MAP_PRIVATE | MAP_ANONYMOUS, -1, 0);
-        if (m == MAP_FAILED) return false;
-        map = (uint8_t*)m;
-        return mprotect(map + bytes, page, PROT_NONE) == 0;
-    }
-    uint8_t* place(const void* src, size_t n) {  // -> the copy, ending at the guard page
-        memset(map, 0xA5, bytes);
-        uint8_t* at = map + bytes - n;
-        if (n) memcpy(at, src, n);
-        return at;
-    }
-    ~Guarded() {
-        if (map) munmap(map, bytes + page);
-    }
-};
-}  // namespace
+#include "seq_group.h"
 
 extern "C" {
 
@@ -86,7 +28,7 @@ int sim_strcol(const uint8_t* types, const uint64_t* values, uint64_t n_rows, co
     const sj_u64 nchunks = sc_chunks(c);
     std::vector<sj_u64> ws(3 * nchunks + 1, 0xA5A5A5A5A5A5A5A5ull);
     const ScSums sums = sc_sums(ws.data(), nchunks);
-    const SeqLane g;
+    const SeqGroup g;
     for (sj_u64 k = 0; k < nchunks; ++k) sc_chunk_sums(g, c, k, (sj_u64*)validity, sums);
     ScResult res;
     sc_chunk_scan(g, sums, nchunks, n_rows, (sj_u64*)offsets, byte_capacity, &res);

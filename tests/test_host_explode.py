@@ -14,24 +14,16 @@ if __name__ == "__main__":
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from oracle import oracle as O
+from tests import host_sim_lib
 from tests import explode_common as EC
 from tests import select_common as SC
 from tests import select_fuzz as F
 from tests.conftest import ROOT
 
-SIM_DIR = os.path.join(ROOT, "tests", "host_sim")
-
 
 def load_sim():
-    """tests/host_sim/explode_sim.cpp as a shared library, built when it is older than its sources"""
-    so = os.path.join(SIM_DIR, "libexplodesim.so")
-    src = os.path.join(SIM_DIR, "explode_sim.cpp")
-    hdrs = [os.path.join(ROOT, "simdjson-java_amd", "csrc", h) for h in ("sj_block.h", "sj_select.h")]
-    if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(f) for f in [src] + hdrs):
-        tmp = "%s.%d.tmp" % (so, os.getpid())
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", tmp, src])
-        os.replace(tmp, so)
-    lib = C.CDLL(so)
+    """tests/host_sim/explode_sim.cpp (tests/host_sim_lib.py builds it) with its signatures"""
+    lib = host_sim_lib.load("explode", ("sj_select.h",))
     lib.sim_explode.restype = C.c_int
     lib.sim_explode.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                 C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]

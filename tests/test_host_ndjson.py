@@ -3,29 +3,19 @@ against the reference of tests/ndjson_common.py: tests/host_sim/ndjson_sim.cpp r
 sequentially, at tiles of 64 and 128 bytes and at the kernels' own, with the buffer at every alignment and '\\n' / 'a' bytes
 around it."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+from tests import host_sim_lib
 from tests import ndjson_common as NC
-from tests.conftest import ROOT
 
-SIM_DIR = os.path.join(ROOT, "tests", "host_sim")
 SHIFTS = (0, 1, 7, 15)
 
 
 def load_sim():
-    """tests/host_sim/ndjson_sim.cpp as a shared library, built when it is older than its sources"""
-    so = os.path.join(SIM_DIR, "libndjsonsim.so")
-    src = os.path.join(SIM_DIR, "ndjson_sim.cpp")
-    hdrs = [os.path.join(ROOT, "simdjson-java_amd", "csrc", h) for h in ("sj_block.h", "sj_block32.h", "sj_ndjson.h")]
-    if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(f) for f in [src] + hdrs):
-        tmp = "%s.%d.tmp" % (so, os.getpid())
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", tmp, src])
-        os.replace(tmp, so)
-    lib = C.CDLL(so)
+    """tests/host_sim/ndjson_sim.cpp (tests/host_sim_lib.py builds it) with its signatures"""
+    lib = host_sim_lib.load("ndjson", ("sj_block32.h", "sj_ndjson.h"))
     lib.sim_ndjson.restype = C.c_int
     lib.sim_ndjson.argtypes = [C.c_char_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_char_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p]
     lib.sim_ndjson_tile_blocks.restype = C.c_uint32

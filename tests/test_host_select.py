@@ -4,29 +4,20 @@ string buffers made by oracle.parse; tests/select_common.py says what every (pat
 import ctypes as C
 import json
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from oracle import oracle as O
+from tests import host_sim_lib
 from tests import select_common as SC
 from tests.conftest import ROOT, load_fixture
 from tests.golden.vectors import TWITTER_DEFAULT_PROFILE_USERS
 
-SIM_DIR = os.path.join(ROOT, "tests", "host_sim")
-
 
 def load_sim():
-    """tests/host_sim/sel_sim.cpp as a shared library, built when it is older than its sources"""
-    so = os.path.join(SIM_DIR, "libselsim.so")
-    src = os.path.join(SIM_DIR, "sel_sim.cpp")
-    hdrs = [os.path.join(ROOT, "simdjson-java_amd", "csrc", h) for h in ("sj_block.h", "sj_select.h")]
-    if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(f) for f in [src] + hdrs):
-        tmp = "%s.%d.tmp" % (so, os.getpid())
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", tmp, src])
-        os.replace(tmp, so)
-    lib = C.CDLL(so)
+    """tests/host_sim/sel_sim.cpp (tests/host_sim_lib.py builds it) with its signatures"""
+    lib = host_sim_lib.load("sel", ("sj_select.h",))
     lib.sim_select.restype = C.c_int
     lib.sim_select.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
                                C.c_void_p, C.c_void_p]

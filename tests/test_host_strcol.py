@@ -3,30 +3,20 @@ against the numpy reference of tests/strcol_common.py: tests/host_sim/strcol_sim
 offsets and the copy sequentially, at chunks of 64 and 128 rows and at the kernels' own.  The string buffer ends at a page that
 cannot be read and NULL rows carry wild value words, so one dereference of such a word ends the test process."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+from tests import host_sim_lib
 from tests import strcol_common as SC
-from tests.conftest import ROOT
 
-SIM_DIR = os.path.join(ROOT, "tests", "host_sim")
 SB_SIZE = 5000
 CHUNKS = pytest.mark.parametrize("chunk", (64, 128, 0), ids=("chunk64", "chunk128", "chunk_of_the_kernels"))
 
 
 def load_sim():
-    """tests/host_sim/strcol_sim.cpp as a shared library, built when it is older than its sources"""
-    so = os.path.join(SIM_DIR, "libstrcolsim.so")
-    src = os.path.join(SIM_DIR, "strcol_sim.cpp")
-    hdrs = [os.path.join(ROOT, "simdjson-java_amd", "csrc", h) for h in ("sj_block.h", "sj_strcol.h")]
-    if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(f) for f in [src] + hdrs):
-        tmp = "%s.%d.tmp" % (so, os.getpid())
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", tmp, src])
-        os.replace(tmp, so)
-    lib = C.CDLL(so)
+    """tests/host_sim/strcol_sim.cpp (tests/host_sim_lib.py builds it) with its signatures"""
+    lib = host_sim_lib.load("strcol", ("sj_strcol.h",))
     lib.sim_strcol.restype = C.c_int
     lib.sim_strcol.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
                                C.c_uint64, C.c_void_p]
