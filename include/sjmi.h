@@ -702,6 +702,72 @@ int sjmi_filter_columns_device(sjmi_ctx* ctx, const sjmi_filter_plan* plan, cons
                                uint64_t col_stride, uint64_t n_rows, const void* d_string_buffer, void* d_keep, void* d_rows,
                                uint64_t out_capacity, void* d_out_types, void* d_out_values, void* d_result, void* stream);
 
+/* ---- typed columns as Arrow int64, float64 and bool arrays, made on the device ------------------------------------------------
+ * The end of the device-side pipeline for everything that is not a string: one call turns a set of finished (types, values)
+ * columns into Arrow arrays -- a data buffer and an LSB-first validity bitmap per FIELD -- with a record of counts per field
+ * (csrc/arrowcol.hip).  It reads the columns and nothing else: no tape, no string buffer, no plan object.
+ *
+ * INPUT.  The column set of sjmi_filter_columns_device: the cell of column c, row r is types[c * col_stride + r] / values[c *
+ * col_stride + r] in the encoding of sjmi_select_batch_device; d_types is loaded as bytes and takes ANY alignment.  `fields` is a
+ * HOST array of n_fields (1 .. SJMI_ARROW_MAX_FIELDS) entries: field f makes one output array of kind `kind` from column
+ * `column`.  Two fields may name the same column (the same path once as INT64 and once as FLOAT64).
+ * LIVE ROWS.  live = n_rows when d_row_count is NULL, else min(n_rows, *(const uint64_t*)d_row_count), read ON THE DEVICE by the
+ * kernels: pointing d_row_count at sjmi_filter_result.n_kept, or at d_row_offsets + n_docs of an explode, chains the calls
+ * without a host synchronisation.  n_rows only sizes the grid and the buffers.  Rows at or above live are not read, not counted
+ * and not written.
+ * CELLS.  VALID = the validity bit is 1.  A NULL row's data slot is written as 0.  A cell's value word is used only behind the
+ * type tests named here; whatever it holds in other cells never shows in an output.
+ *   INT64     'l' -> the int64.  With SJMI_ARROW_F_INTEGRAL_DOUBLES a 'd' cell converts too when its double is finite, has no
+ *             fraction and lies in [-2^63, 2^63) -- exactly: -0.0 -> 0, -9223372036854775808.0 is VALID, 9223372036854775808.0
+ *             is not.  Every other 'd' cell is NULL and counted in n_other.
+ *   FLOAT64   'd' -> its IEEE bits unchanged (NaN and the infinities pass through); 'l' -> the int64 converted round to nearest,
+ *             ties to even.  n_inexact counts the 'l' cells whose conversion is not exact (2^53 + 1 -> 2^53 is inexact, 2^53
+ *             is exact, INT64_MIN is exact, INT64_MAX -> 2^63 is inexact).
+ *   BOOL      't' / 'f' -> VALID; the data is a BITMAP in the first ceil(live / 64) words of the field's data row, LSB first, the
+ *             bit set iff 't'.  NULL rows' bits and the bits at or above live in the last word are 0.  The value word of a
+ *             boolean cell is not read: the type byte says it.
+ *   NULL      in every kind: MISSING (0), 'n' and every type not named above.  n_other counts the NULL rows that are neither
+ *             MISSING nor 'n' -- the schema mismatch, as in sjmi_strcol_result.
+ * OUTPUTS.
+ *   d_data      uint64[n_fields * data_stride]: field f, row r at f * data_stride + r (BOOL: word w of the bitmap at f *
+ *               data_stride + w).  NULL together with data_stride == 0 is the COUNTING call: validity and records only.
+ *   d_validity  uint64[n_fields * validity_stride]: field f owns the words f * validity_stride ...; bit r & 63 of word r >> 6 is
+ *               set iff row r is VALID, bits at or above live in the last written word are 0 (the bitmap of
+ *               sjmi_string_column_device).  May be NULL: nothing is written for it, the records alone give the null counts.
+ *   d_results   sjmi_arrow_field_result[n_fields], ALWAYS complete.  n_rows of a record is live: the consumer learns the row
+ *               count with the same readback.
+ * Of a field exactly the data words [0, live) -- BOOL: [0, ceil(live / 64)) -- and the validity words [0, ceil(live / 64)) are
+ * written; nothing else in the two blocks is touched, and nothing behind them.  Outputs must not overlap inputs.
+ * THE EMPTY CASES.  n_rows == 0 or live == 0 is legal: records of zeros, no data or validity word written, and no kernel is
+ * launched with an empty grid.  n_fields == 0 is SJMI_ERR_ARG.
+ * ARGUMENTS.  SJMI_ERR_ARG: n_fields 0 or above SJMI_ARROW_MAX_FIELDS; a field with an unknown kind, a flag that is not defined
+ * for its kind, reserved != 0 or column >= n_cols; col_stride < n_rows; data_stride < n_rows with d_data, or a data_stride
+ * without one; validity_stride < ceil(n_rows / 64) with d_validity; NULL d_results; NULL d_types or d_values with n_rows > 0;
+ * d_values, d_row_count, d_data, d_validity or d_results not 8-byte aligned; n_rows >= 2^40.
+ * STREAM AND STATE.  Asynchronous on `stream` (NULL = the context's), no host synchronisation, nothing queued but two plain
+ * kernels that the stream orders (the conversion per 1024 rows and field, the sum of the chunk counts per field).  The fields are
+ * validated and handed to the kernels by value as a launch argument: the call uploads nothing and the context holds no schema.
+ * The only state is a scratch slot of its own (one packed count word per field and 1024-row chunk), which grows on demand with
+ * a device synchronisation; it is one per context, so arrow-column calls on ONE context must be ordered with respect to each
+ * other. */
+#define SJMI_ARROW_MAX_FIELDS 64u          /* = SJMI_SELECT_MAX_PATHS */
+#define SJMI_ARROW_INT64   1u
+#define SJMI_ARROW_FLOAT64 2u
+#define SJMI_ARROW_BOOL    3u
+#define SJMI_ARROW_F_INTEGRAL_DOUBLES 1u   /* INT64 fields only */
+typedef struct sjmi_arrow_field {
+    uint32_t column;    /* which of the call's n_cols columns the field is made of */
+    uint32_t kind;      /* SJMI_ARROW_<KIND> */
+    uint32_t flags;     /* SJMI_ARROW_F_* */
+    uint32_t reserved;  /* 0 */
+} sjmi_arrow_field;
+typedef struct sjmi_arrow_field_result {
+    uint64_t n_rows, n_valid, n_other, n_inexact;
+} sjmi_arrow_field_result;
+int sjmi_arrow_columns_device(sjmi_ctx* ctx, const sjmi_arrow_field* fields, uint64_t n_fields, const void* d_types, const void* d_values,
+                              uint64_t n_cols, uint64_t col_stride, uint64_t n_rows, const void* d_row_count, void* d_data,
+                              uint64_t data_stride, void* d_validity, uint64_t validity_stride, void* d_results, void* stream);
+
 /* Optional: page-lock caller-owned host memory that is passed to the host-buffer entry points again and again
  * (SimdJsonParser's padded input, index array and string buffer): H2D / D2H copies of pinned memory skip the
  * driver's staging copy (3-4x faster for the ~1 MB transfers of a single-document parse).  Purely a performance

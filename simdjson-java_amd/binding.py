@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_HERE)
 _CSRC = os.path.join(_HERE, "csrc")
 _LIB = os.path.join(_HERE, "libsjmi.so")
-SOURCES = ["stage1.hip", "strings.hip", "batch.hip", "walk.hip", "coop_walk.hip", "masks.hip", "select.hip", "explode.hip", "ndjson.hip", "strcol.hip", "filter.hip", "sjmi_api.hip", "host/simdjson_parser.cpp"]
+SOURCES = ["stage1.hip", "strings.hip", "batch.hip", "walk.hip", "coop_walk.hip", "masks.hip", "select.hip", "explode.hip", "ndjson.hip", "strcol.hip", "filter.hip", "arrowcol.hip", "sjmi_api.hip", "host/simdjson_parser.cpp"]
 
 ST_UTF8, ST_UNCLOSED, ST_UNESCAPED, ST_CAPACITY, ST_INTERNAL = 1, 2, 4, 0x100, 0x200
 PADDING = 64
@@ -109,7 +109,7 @@ EXPORTS = ["sjmi_create", "sjmi_destroy", "sjmi_last_error", "sjmi_version", "sj
            "sjmi_select_plan_compile", "sjmi_select_plan_destroy", "sjmi_select_batch_device",
            "sjmi_explode_plan_compile", "sjmi_explode_plan_destroy", "sjmi_explode_batch_device",
            "sjmi_ndjson_offsets_device", "sjmi_ndjson_offsets", "sjmi_ndjson_tile_bytes", "sjmi_string_column_device",
-           "sjmi_filter_plan_compile", "sjmi_filter_plan_destroy", "sjmi_filter_columns_device"]
+           "sjmi_filter_plan_compile", "sjmi_filter_plan_destroy", "sjmi_filter_columns_device", "sjmi_arrow_columns_device"]
 
 
 # Handles that are still open when the interpreter exits are closed HERE, in an atexit hook -- i.e. while the HIP runtime
@@ -283,11 +283,36 @@ def lib():
         L.sjmi_filter_columns_device.restype = C.c_int
         L.sjmi_filter_columns_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p,
                                                  C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.sjmi_arrow_columns_device.restype = C.c_int
+        L.sjmi_arrow_columns_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64,
+                                                C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
         L.sjmi_select_batch_device.restype = C.c_int
         L.sjmi_select_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
                                                C.c_void_p, C.c_void_p, C.c_void_p]
         _lib = L
     return _lib
+
+
+ARROW_KINDS = {"int64": 1, "float64": 2, "bool": 3}     # SJMI_ARROW_<KIND>
+ARROW_FLAGS = {"integral_doubles": 1}                   # SJMI_ARROW_F_*
+ARROW_FIELD = np.dtype([("column", "<u4"), ("kind", "<u4"), ("flags", "<u4"), ("reserved", "<u4")])  # sjmi_arrow_field
+
+
+def arrow_fields(fields):
+    """(column, kind[, flag ...]) tuples -> the sjmi_arrow_field array of Context.arrow_columns_device (an array of that dtype is
+    taken as it is: the library validates it).  ValueError for a kind or a flag that has no name here."""
+    if isinstance(fields, np.ndarray) and fields.dtype == ARROW_FIELD:
+        return np.ascontiguousarray(fields)
+    enc = np.zeros(len(fields), dtype=ARROW_FIELD)
+    for k, field in enumerate(fields):
+        column, kind, flags = field[0], field[1], field[2:]
+        if kind not in ARROW_KINDS or any(f not in ARROW_FLAGS for f in flags) or not 0 <= int(column) < 1 << 32:
+            raise ValueError("arrow field %d: unknown kind or flag, or column out of range: %r" % (k, (field,)))
+        bits = 0
+        for f in flags:
+            bits |= ARROW_FLAGS[f]
+        enc[k] = (int(column), ARROW_KINDS[kind], bits, 0)
+    return enc
 
 
 class Context:
@@ -541,6 +566,20 @@ class Context:
         self._check(lib().sjmi_filter_columns_device(self._h, plan._h, d_types or None, d_values or None, n_cols, col_stride, n_rows,
                                                      d_sb or None, d_keep or None, d_rows or None, out_capacity, d_out_types or None,
                                                      d_out_values or None, d_result or None, stream), "sjmi_filter_columns_device")
+
+    def arrow_columns_device(self, fields, d_types, d_values, n_cols, col_stride, n_rows, d_row_count, d_data, data_stride, d_validity,
+                             validity_stride, d_results, stream=0):
+        """sjmi_arrow_columns_device: n_cols (types, values) columns strided by col_stride as Arrow arrays, one per field.  fields:
+        tuples (column, kind[, flag ...]) with kind "int64" / "float64" / "bool" and the flag "integral_doubles" (see
+        arrow_fields()), or an encoded array.  d_row_count (None / 0: every row) = a device uint64 that holds the live rows;
+        d_data (uint64 [n_fields * data_stride]; None / 0 with stride 0: the counting call), d_validity (uint64 words, LSB first,
+        [n_fields * validity_stride]; None / 0: not written), d_results = device sjmi_arrow_field_result (n_fields x 4 int64:
+        n_rows, n_valid, n_other, n_inexact).  Asynchronous on `stream`."""
+        enc = arrow_fields(fields)
+        self._check(lib().sjmi_arrow_columns_device(self._h, enc.ctypes.data if enc.size else None, enc.size, d_types or None, d_values or None,
+                                                    n_cols, col_stride, n_rows, d_row_count or None, d_data or None, data_stride,
+                                                    d_validity or None, validity_stride, d_results or None, stream),
+                    "sjmi_arrow_columns_device")
 
     def ndjson_offsets(self, data):
         """sjmi_ndjson_offsets (host form) -> (doc_offsets np.uint64 [n_docs + 1], consumed, flags): the documents are the

@@ -417,4 +417,16 @@ hipError_t filter_launch(const sjmi_filter_plan* plan, const void* d_types, cons
                          uint64_t n_rows, const void* d_string_buffer, void* d_keep, void* d_rows, uint64_t out_capacity, void* d_out_types,
                          void* d_out_values, void* d_result, void* d_ws, hipStream_t stream);
 
+// ---- typed columns as Arrow int64 / float64 / bool arrays (arrowcol.hip) ----
+constexpr size_t ARROWCOL_PLAN_BYTES = 16 + 64 * 16;  // sizeof(AcPlan): the validated fields, a launch argument
+// the fields validated into plan_out (ARROWCOL_PLAN_BYTES, 8-byte aligned): 0, or -2 for a schema the call refuses
+int arrowcol_plan(const sjmi_arrow_field* fields, uint64_t n_fields, uint64_t n_cols, void* plan_out);
+// scratch of one call: one packed count word per field and chunk of 1024 rows
+size_t arrowcol_workspace_bytes(uint64_t n_fields, uint64_t n_rows);
+// k_arrow_convert (n_rows != 0: data, validity, the chunk words) and k_arrow_finish (the sjmi_arrow_field_result per field); the
+// plan goes by value, d_row_count (may be NULL) is read by the kernels
+hipError_t arrowcol_launch(const void* plan, const void* d_types, const void* d_values, uint64_t col_stride, uint64_t n_rows,
+                           const void* d_row_count, void* d_data, uint64_t data_stride, void* d_validity, uint64_t validity_stride,
+                           void* d_results, void* d_ws, hipStream_t stream);
+
 }  // namespace sjmi
