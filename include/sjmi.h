@@ -768,6 +768,80 @@ int sjmi_arrow_columns_device(sjmi_ctx* ctx, const sjmi_arrow_field* fields, uin
                               uint64_t n_cols, uint64_t col_stride, uint64_t n_rows, const void* d_row_count, void* d_data,
                               uint64_t data_stride, void* d_validity, uint64_t validity_stride, void* d_results, void* stream);
 
+/* ---- RFC 3339 string columns as Arrow timestamp arrays, made on the device ----------------------------------------------------
+ * JSON has no time type: a timestamp arrives as a string ("created_at":"2015-01-01T15:00:00Z").  This call parses the string
+ * cells of finished (types, values) columns into Arrow timestamp arrays -- an int64 per row at the field's unit, counted from
+ * 1970-01-01T00:00:00Z, an LSB-first validity bitmap and a record of counts per FIELD (csrc/timecol.hip).  It
+ * reads the columns and the string buffer and nothing else: no tape, no plan object.
+ * EPOCH NUMBERS need no call of their own: a column of 'l' cells is served by sjmi_arrow_columns_device's INT64, and an int64
+ * array IS a timestamp array, by reinterpretation at the caller's unit (Arrow's timestamp is an int64 with a unit and a zone
+ * in the type).  'l' and 'd' cells under a time field are therefore NULL and counted in n_other.
+ *
+ * INPUT, LIVE ROWS.  As sjmi_arrow_columns_device: the column set of sjmi_filter_columns_device, d_types loaded as bytes at ANY
+ * alignment, `fields` a HOST array of n_fields (1 .. SJMI_TIME_MAX_FIELDS) entries of which two may name one column (the same
+ * path at two units); live = n_rows when d_row_count is NULL, else min(n_rows, *(const uint64_t*)d_row_count) read ON THE
+ * DEVICE, so that a filter's n_kept or an explode's last row offset chains the calls without a host synchronisation.  Rows at
+ * or above live are not read, not counted and not written.  d_string_buffer is the buffer the string cells point into.
+ * CELLS.  A cell's value word is read only behind type == '"'; the bytes of a string only behind that AND the test of its
+ * length.  A '"' cell is the unescaped bytes [offset, offset + len) of d_string_buffer, value = (len << 32) | offset, which
+ * must match the WHOLE of
+ *       YYYY-MM-DD sep hh:mm:ss [ '.' 1 to 9 digits ] zone
+ *   sep: 'T', 't' or ONE space.  zone: 'Z', 'z', or +hh:mm / -hh:mm.  Every digit is an ASCII digit.  Year 0000..9999, month
+ *   01..12, a day that the month has in the proleptic Gregorian calendar (0000, 2000, 2024 are leap years; 1900, 2023 are not),
+ *   hour 00..23, minute and second 00..59 (":60", a leap second, is malformed), offset hour 00..23 and offset minute 00..59;
+ *   -00:00 is UTC.  Nothing may precede or follow, so len is 20..35.  With SJMI_TIME_F_NAIVE_UTC the zone may be absent -- the
+ *   time is then taken as UTC -- and len is 19..35.  A string of any other length is malformed WITHOUT A BYTE OF IT BEING READ;
+ *   date-only strings are malformed.
+ *   VALUE  (days_from_civil(Y, M, D) * 86400 + hh * 3600 + mm * 60 + ss - offset_seconds) * 10^k + fraction, k = 0, 3, 6, 9 by
+ *          unit, the fraction scaled to the unit with its surplus digits DROPPED -- a floor, since the fraction is positive:
+ *          1969-12-31T23:59:59.5Z at SECOND is -1.  A VALID cell with a non-zero dropped digit counts in n_inexact.
+ *   RANGE  a value that is not an int64 makes the cell NULL and counts in n_range; only NANO can do this:
+ *          2262-04-11T23:47:16.854775807Z is INT64_MAX and VALID, 1677-09-21T00:12:43.145224192Z is INT64_MIN and VALID, one
+ *          nanosecond further out is a range error.  Decided in integers on the seconds; nothing overflows on the way.
+ *   NULL   a string that fails the grammar: counted in n_malformed.  MISSING (0) and 'n': counted nowhere.  Every other type --
+ *          'l' and 'd' included --: counted in n_other, the schema mismatch as in sjmi_arrow_field_result.
+ * OUTPUTS.  As sjmi_arrow_columns_device, every field an int64 one:
+ *   d_data      uint64[n_fields * data_stride]: field f, row r at f * data_stride + r, a NULL row's word written as 0.  NULL
+ *               together with data_stride == 0 is the COUNTING call: validity and records only.
+ *   d_validity  uint64[n_fields * validity_stride], LSB first: bit r & 63 of word f * validity_stride + (r >> 6) is set iff row
+ *               r of field f is VALID; bits at or above live in the last written word are 0.  May be NULL.
+ *   d_results   sjmi_time_field_result[n_fields], ALWAYS complete, n_rows = live.
+ * Of a field exactly the data words [0, live) and the validity words [0, ceil(live / 64)) are written; nothing else in the two
+ * blocks is touched, and nothing behind them.  Outputs must not overlap inputs.
+ * THE EMPTY CASES.  n_rows == 0 or live == 0 is legal: records of zeros, no data or validity word written, and no kernel is
+ * launched with an empty grid.  n_fields == 0 is SJMI_ERR_ARG.
+ * ARGUMENTS.  SJMI_ERR_ARG: n_fields 0 or above SJMI_TIME_MAX_FIELDS; a field with a unit above SJMI_TIME_NANO, a flag other
+ * than SJMI_TIME_F_NAIVE_UTC, reserved != 0 or column >= n_cols; col_stride < n_rows; data_stride < n_rows with d_data, or a
+ * data_stride without one; validity_stride < ceil(n_rows / 64) with d_validity; NULL d_results; NULL d_types, d_values or
+ * d_string_buffer with n_rows > 0; d_values, d_row_count, d_data, d_validity or d_results not 8-byte aligned; n_rows >= 2^40.
+ * MEMORY.  The string bytes are fetched as the naturally aligned 8-byte words that hold at least one byte of the string: such
+ * a word lies in the same page, and so in the same allocation, as that byte, and what else it carries reaches no output.
+ * STREAM AND STATE.  Asynchronous on `stream` (NULL = the context's), no host synchronisation, nothing queued but two plain
+ * kernels that the stream orders (the parse per 256 rows and field, the sum of the chunk counts per field).  The fields are
+ * validated and handed to the kernels by value as a launch argument: the call uploads nothing and the context holds no schema.
+ * The only state is a scratch slot of its own (one packed count word per field and 256-row chunk), which grows on demand with
+ * a device synchronisation; it is one per context, so time-column calls on ONE context must be ordered with respect to each
+ * other.
+ * NOT HERE.  date32 and time-of-day kinds, named zones, leap seconds, other formats. */
+#define SJMI_TIME_MAX_FIELDS 64u           /* = SJMI_SELECT_MAX_PATHS */
+#define SJMI_TIME_SECOND 0u
+#define SJMI_TIME_MILLI  1u
+#define SJMI_TIME_MICRO  2u
+#define SJMI_TIME_NANO   3u
+#define SJMI_TIME_F_NAIVE_UTC 1u           /* a string without an offset is taken as UTC */
+typedef struct sjmi_time_field {
+    uint32_t column;    /* which of the call's n_cols columns the field is made of */
+    uint32_t unit;      /* SJMI_TIME_<UNIT> */
+    uint32_t flags;     /* SJMI_TIME_F_* */
+    uint32_t reserved;  /* 0 */
+} sjmi_time_field;
+typedef struct sjmi_time_field_result {
+    uint64_t n_rows, n_valid, n_other, n_malformed, n_range, n_inexact;
+} sjmi_time_field_result;
+int sjmi_time_columns_device(sjmi_ctx* ctx, const sjmi_time_field* fields, uint64_t n_fields, const void* d_types, const void* d_values,
+                             uint64_t n_cols, uint64_t col_stride, uint64_t n_rows, const void* d_row_count, const void* d_string_buffer,
+                             void* d_data, uint64_t data_stride, void* d_validity, uint64_t validity_stride, void* d_results, void* stream);
+
 /* Optional: page-lock caller-owned host memory that is passed to the host-buffer entry points again and again
  * (SimdJsonParser's padded input, index array and string buffer): H2D / D2H copies of pinned memory skip the
  * driver's staging copy (3-4x faster for the ~1 MB transfers of a single-document parse).  Purely a performance

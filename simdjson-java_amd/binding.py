@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_HERE)
 _CSRC = os.path.join(_HERE, "csrc")
 _LIB = os.path.join(_HERE, "libsjmi.so")
-SOURCES = ["stage1.hip", "strings.hip", "batch.hip", "walk.hip", "coop_walk.hip", "masks.hip", "select.hip", "explode.hip", "ndjson.hip", "strcol.hip", "filter.hip", "arrowcol.hip", "sjmi_api.hip", "host/simdjson_parser.cpp"]
+SOURCES = ["stage1.hip", "strings.hip", "batch.hip", "walk.hip", "coop_walk.hip", "masks.hip", "select.hip", "explode.hip", "ndjson.hip", "strcol.hip", "filter.hip", "arrowcol.hip", "timecol.hip", "sjmi_api.hip", "host/simdjson_parser.cpp"]
 
 ST_UTF8, ST_UNCLOSED, ST_UNESCAPED, ST_CAPACITY, ST_INTERNAL = 1, 2, 4, 0x100, 0x200
 PADDING = 64
@@ -109,7 +109,8 @@ EXPORTS = ["sjmi_create", "sjmi_destroy", "sjmi_last_error", "sjmi_version", "sj
            "sjmi_select_plan_compile", "sjmi_select_plan_destroy", "sjmi_select_batch_device",
            "sjmi_explode_plan_compile", "sjmi_explode_plan_destroy", "sjmi_explode_batch_device",
            "sjmi_ndjson_offsets_device", "sjmi_ndjson_offsets", "sjmi_ndjson_tile_bytes", "sjmi_string_column_device",
-           "sjmi_filter_plan_compile", "sjmi_filter_plan_destroy", "sjmi_filter_columns_device", "sjmi_arrow_columns_device"]
+           "sjmi_filter_plan_compile", "sjmi_filter_plan_destroy", "sjmi_filter_columns_device", "sjmi_arrow_columns_device",
+           "sjmi_time_columns_device"]
 
 
 # Handles that are still open when the interpreter exits are closed HERE, in an atexit hook -- i.e. while the HIP runtime
@@ -286,6 +287,9 @@ def lib():
         L.sjmi_arrow_columns_device.restype = C.c_int
         L.sjmi_arrow_columns_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64,
                                                 C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+        L.sjmi_time_columns_device.restype = C.c_int
+        L.sjmi_time_columns_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64,
+                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
         L.sjmi_select_batch_device.restype = C.c_int
         L.sjmi_select_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
                                                C.c_void_p, C.c_void_p, C.c_void_p]
@@ -312,6 +316,29 @@ def arrow_fields(fields):
         for f in flags:
             bits |= ARROW_FLAGS[f]
         enc[k] = (int(column), ARROW_KINDS[kind], bits, 0)
+    return enc
+
+
+TIME_UNITS = {"s": 0, "ms": 1, "us": 2, "ns": 3}        # SJMI_TIME_<UNIT>, under Arrow's names
+TIME_FLAGS = {"naive_utc": 1}                           # SJMI_TIME_F_*
+TIME_FIELD = np.dtype([("column", "<u4"), ("unit", "<u4"), ("flags", "<u4"), ("reserved", "<u4")])  # sjmi_time_field
+
+
+def time_fields(fields):
+    """(column, unit[, flag ...]) tuples such as (0, "us") or (2, "ns", "naive_utc") -> the sjmi_time_field array of
+    Context.time_columns_device (an array of that dtype is taken as it is: the library validates it).  ValueError for a unit or a
+    flag that has no name here."""
+    if isinstance(fields, np.ndarray) and fields.dtype == TIME_FIELD:
+        return np.ascontiguousarray(fields)
+    enc = np.zeros(len(fields), dtype=TIME_FIELD)
+    for k, field in enumerate(fields):
+        column, unit, flags = field[0], field[1], field[2:]
+        if unit not in TIME_UNITS or any(f not in TIME_FLAGS for f in flags) or not 0 <= int(column) < 1 << 32:
+            raise ValueError("time field %d: unknown unit or flag, or column out of range: %r" % (k, (field,)))
+        bits = 0
+        for f in flags:
+            bits |= TIME_FLAGS[f]
+        enc[k] = (int(column), TIME_UNITS[unit], bits, 0)
     return enc
 
 
@@ -580,6 +607,21 @@ class Context:
                                                     n_cols, col_stride, n_rows, d_row_count or None, d_data or None, data_stride,
                                                     d_validity or None, validity_stride, d_results or None, stream),
                     "sjmi_arrow_columns_device")
+
+    def time_columns_device(self, fields, d_types, d_values, n_cols, col_stride, n_rows, d_row_count, d_sb, d_data, data_stride, d_validity,
+                            validity_stride, d_results, stream=0):
+        """sjmi_time_columns_device: the RFC 3339 strings of n_cols (types, values) columns strided by col_stride as Arrow timestamp
+        arrays, one per field.  fields: tuples (column, unit[, flag ...]) with unit "s" / "ms" / "us" / "ns" and the flag
+        "naive_utc" (see time_fields()), or an encoded array.  d_row_count (None / 0: every row) = a device uint64 that holds the
+        live rows; d_sb = the string buffer the cells point into; d_data (int64 [n_fields * data_stride]; None / 0 with stride 0:
+        the counting call), d_validity (uint64 words, LSB first, [n_fields * validity_stride]; None / 0: not written), d_results =
+        device sjmi_time_field_result (n_fields x 6 int64: n_rows, n_valid, n_other, n_malformed, n_range, n_inexact).
+        Asynchronous on `stream`."""
+        enc = time_fields(fields)
+        self._check(lib().sjmi_time_columns_device(self._h, enc.ctypes.data if enc.size else None, enc.size, d_types or None, d_values or None,
+                                                   n_cols, col_stride, n_rows, d_row_count or None, d_sb or None, d_data or None, data_stride,
+                                                   d_validity or None, validity_stride, d_results or None, stream),
+                    "sjmi_time_columns_device")
 
     def ndjson_offsets(self, data):
         """sjmi_ndjson_offsets (host form) -> (doc_offsets np.uint64 [n_docs + 1], consumed, flags): the documents are the

@@ -129,6 +129,7 @@ struct sjmi_ctx {
     DevBuf<void> d_ws_strcol;                // sjmi_string_column_device: three sums per chunk of rows (a slot of its own)
     DevBuf<void> d_ws_filter;                // sjmi_filter_columns_device: a count per chunk of rows and the keep words (a slot of its own)
     DevBuf<void> d_ws_arrow;                 // sjmi_arrow_columns_device: a packed count word per field and chunk of rows (a slot of its own)
+    DevBuf<void> d_ws_time;                  // sjmi_time_columns_device: a packed count word per field and chunk of rows (a slot of its own)
     std::string err;
 };
 
@@ -1044,6 +1045,28 @@ int sjmi_arrow_columns_device(sjmi_ctx* c, const sjmi_arrow_field* fields, uint6
     if (!grow_scratch(c, c->d_ws_arrow, sjmi::arrowcol_workspace_bytes(n_fields, n_rows), "hipMalloc(ws_arrow)")) return SJMI_ERR_HIP;
     return fail(c, "arrow columns launch", sjmi::arrowcol_launch(plan, d_types, d_values, col_stride, n_rows, d_row_count, d_data, data_stride,
                                                                  d_validity, validity_stride, d_results, c->d_ws_arrow, st))
+               ? SJMI_ERR_HIP
+               : SJMI_OK;
+}
+
+int sjmi_time_columns_device(sjmi_ctx* c, const sjmi_time_field* fields, uint64_t n_fields, const void* d_types, const void* d_values,
+                             uint64_t n_cols, uint64_t col_stride, uint64_t n_rows, const void* d_row_count, const void* d_string_buffer,
+                             void* d_data, uint64_t data_stride, void* d_validity, uint64_t validity_stride, void* d_results, void* stream) {
+    if (!c || !d_results || col_stride < n_rows || (n_rows && (!d_types || !d_values || !d_string_buffer))) return SJMI_ERR_ARG;
+    if (n_rows >= (1ull << 40)) return SJMI_ERR_ARG;  // (one workgroup per 256 rows)
+    if (d_data ? data_stride < n_rows : data_stride != 0) return SJMI_ERR_ARG;
+    if (d_validity && validity_stride < (n_rows + 63) / 64) return SJMI_ERR_ARG;
+    if (((uintptr_t)d_values & 7) || ((uintptr_t)d_row_count & 7) || ((uintptr_t)d_data & 7) || ((uintptr_t)d_validity & 7) || ((uintptr_t)d_results & 7))
+        return SJMI_ERR_ARG;
+    alignas(8) unsigned char plan[sjmi::TIMECOL_PLAN_BYTES];
+    if (sjmi::timecol_plan(fields, n_fields, n_cols, plan) != 0) return SJMI_ERR_ARG;
+    if (n_cols && col_stride > ~0ull / 8 / n_cols) return SJMI_ERR_ARG;  // (a column set is addressable, and so are the outputs)
+    if (data_stride > ~0ull / 8 / n_fields || validity_stride > ~0ull / 8 / n_fields) return SJMI_ERR_ARG;
+    if (fail(c, "hipSetDevice", hipSetDevice(c->device))) return SJMI_ERR_HIP;
+    hipStream_t st = stream_of(c, stream);
+    if (!grow_scratch(c, c->d_ws_time, sjmi::timecol_workspace_bytes(n_fields, n_rows), "hipMalloc(ws_time)")) return SJMI_ERR_HIP;
+    return fail(c, "time columns launch", sjmi::timecol_launch(plan, d_types, d_values, col_stride, n_rows, d_row_count, d_string_buffer, d_data,
+                                                               data_stride, d_validity, validity_stride, d_results, c->d_ws_time, st))
                ? SJMI_ERR_HIP
                : SJMI_OK;
 }

@@ -429,4 +429,16 @@ hipError_t arrowcol_launch(const void* plan, const void* d_types, const void* d_
                            const void* d_row_count, void* d_data, uint64_t data_stride, void* d_validity, uint64_t validity_stride,
                            void* d_results, void* d_ws, hipStream_t stream);
 
+// ---- RFC 3339 string columns as Arrow timestamp arrays (timecol.hip) ----
+constexpr size_t TIMECOL_PLAN_BYTES = 16 + 64 * 16;  // sizeof(TcPlan): the validated fields, a launch argument
+// the fields validated into plan_out (TIMECOL_PLAN_BYTES, 8-byte aligned): 0, or -2 for a schema the call refuses
+int timecol_plan(const sjmi_time_field* fields, uint64_t n_fields, uint64_t n_cols, void* plan_out);
+// scratch of one call: one packed count word per field and chunk of 256 rows
+size_t timecol_workspace_bytes(uint64_t n_fields, uint64_t n_rows);
+// k_time_parse (n_rows != 0: data, validity, the chunk words) and k_time_finish (the sjmi_time_field_result per field); the plan
+// goes by value, d_row_count (may be NULL) is read by the kernels
+hipError_t timecol_launch(const void* plan, const void* d_types, const void* d_values, uint64_t col_stride, uint64_t n_rows,
+                          const void* d_row_count, const void* d_string_buffer, void* d_data, uint64_t data_stride, void* d_validity,
+                          uint64_t validity_stride, void* d_results, void* d_ws, hipStream_t stream);
+
 }  // namespace sjmi

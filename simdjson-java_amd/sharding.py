@@ -280,6 +280,36 @@ class BatchShard:
                                          validity.data_ptr() if n_rows else 0, words, results.data_ptr(), stream)
         return data, validity, results
 
+    def timestamp_columns(self, fields, types, values, n_rows=None, row_count=None, stream=0):
+        """RFC 3339 string columns as Arrow timestamp arrays: sjmi_time_columns_device on a 2-D [n_cols, stride] (types uint8,
+        values int64) tensor pair -- sel_types / sel_values, exp_types / exp_values, or the compacted pair of filter() -- whose
+        string cells point into self.sb.  fields: tuples (column, "s" | "ms" | "us" | "ns"[, "naive_utc"]), at most 64; two may
+        name one column.  n_rows sizes the launch and the outputs (default: the stride); row_count is an optional 1-element int64
+        DEVICE tensor -- result[0:1] of filter(), exp_row_offsets[n_docs:] of explode() -- that the kernels read: the live rows
+        are min(n_rows, row_count[0]) and nothing synchronises.  -> (data [n_fields, n_rows] int64 at the field's unit since
+        1970-01-01T00:00:00Z, validity [n_fields, ceil(n_rows / 64)] int64 words (LSB first), results [n_fields, 6] int64 = live
+        rows, n_valid, n_other, n_malformed, n_range, n_inexact), new tensors every call.  Rows at or above the live rows, and
+        the words behind them, are not written: the caller slices by results[:, 0] after its own synchronisation.  Call it on a
+        step that check() has accepted: like arrow_columns(), it is not queued again behind a step that check() had to run
+        again."""
+        import torch
+        assert types.dim() == 2 and values.dim() == 2 and types.shape == values.shape
+        assert types.dtype == torch.uint8 and values.dtype == torch.int64 and types.is_contiguous() and values.is_contiguous()
+        n_cols, stride = int(types.shape[0]), int(types.shape[1])
+        n_rows = stride if n_rows is None else int(n_rows)
+        assert n_cols >= 1 and 0 <= n_rows <= stride
+        if row_count is not None:
+            assert row_count.dtype == torch.int64 and row_count.numel() == 1 and row_count.device == types.device
+        n_fields, words = len(fields), (n_rows + 63) // 64
+        data = torch.empty((n_fields, n_rows), dtype=torch.int64, device=self.device)
+        validity = torch.empty((n_fields, words), dtype=torch.int64, device=self.device)
+        results = torch.empty((n_fields, 6), dtype=torch.int64, device=self.device)  # (every call writes all of it)
+        # (an empty tensor's pointer may be anything: the call gets NULL for what has no entries)
+        self.engine.time_columns_device(fields, types.data_ptr() if n_rows else 0, values.data_ptr() if n_rows else 0, n_cols, stride, n_rows,
+                                        row_count.data_ptr() if row_count is not None else 0, self.sb.data_ptr(), data.data_ptr() if n_rows else 0,
+                                        n_rows, validity.data_ptr() if n_rows else 0, words, results.data_ptr(), stream)
+        return data, validity, results
+
     def counts_tensor(self):
         """The per-shard row of the count gather, on the device, without a host copy:
         {documents, structurals, string bytes, failed + handed-back documents}."""
