@@ -842,6 +842,61 @@ int sjmi_time_columns_device(sjmi_ctx* ctx, const sjmi_time_field* fields, uint6
                              uint64_t n_cols, uint64_t col_stride, uint64_t n_rows, const void* d_row_count, const void* d_string_buffer,
                              void* d_data, uint64_t data_stride, void* d_validity, uint64_t validity_stride, void* d_results, void* stream);
 
+/* ---- one string column as an Arrow dictionary array, encoded on the device -----------------------------------------------
+ * Most string columns of real JSON are categorical.  This call turns ONE (types, values) column into Arrow's dictionary shape:
+ * an int32 index per row, an LSB-first validity bitmap, and the dictionary -- one entry per distinct value -- as int64 offsets
+ * and bytes (csrc/dictcol.hip).  It reads a finished column and the string buffer and nothing else.
+ *
+ * INPUT COLUMN.  d_types / d_values / d_string_buffer exactly as sjmi_string_column_device takes them: d_types is loaded as
+ * bytes at any alignment, a value word is read only behind type == '"', and of a string only the naturally aligned 8-byte words
+ * that hold at least one of its bytes are read (each lies in the page, and so in the allocation, of such a byte).
+ * LIVE ROWS, as in sjmi_arrow_columns_device.  d_row_count == NULL: live = n_rows.  Else it points to a uint64 in DEVICE memory
+ * that the kernels read: live = min(n_rows, *d_row_count) -- a filter's n_kept, an explode's last row offset.  Rows at or above
+ * `live` are not read, counted or written.
+ * MEANING.  Row r is VALID iff types[r] == '"'.  Two VALID rows are EQUAL iff they have the same length and the same bytes; the
+ * empty string is a value of its own.  The dictionary holds one entry per distinct value IN THE ORDER OF FIRST OCCURRENCE:
+ * entry j is the value whose first VALID row is the j-th smallest among the first rows -- the order of pyarrow's
+ * dictionary_encode() and of pandas.factorize.  The output is therefore a function of the input alone, whatever the scheduling.
+ * OUTPUTS.  d_indices: int32[n_rows], 4-byte aligned: the entry number of a VALID row, 0 for a NULL row; exactly [0, live) is
+ * written.  d_validity: the bitmap of sjmi_string_column_device, may be NULL; words [0, ceil(live / 64)) are written, bits at or
+ * above `live` are 0.  d_dict_rows: int64[dict_capacity], may be NULL: the row of each entry's first occurrence, ascending.
+ * d_dict_offsets: int64[dict_capacity + 1], the exclusive scan of the entries' lengths; entries [0, n_distinct] are written.
+ * d_dict_bytes (any alignment): the entries' bytes back to back, below dict_byte_capacity.  dict_byte_capacity == 0 with NULL
+ * d_dict_bytes is the SIZING call: indices, offsets, rows and the record are complete, the copy is not launched.
+ * d_result: sjmi_dict_result; n_rows = live, n_other as in sjmi_strcol_result.  SJMI_DICT_BYTES_OVERFLOW is set iff dict_bytes >
+ * dict_byte_capacity (the sizing call of a dictionary with bytes sets it), SJMI_DICT_OVERFLOW iff there are more distinct
+ * values than dict_capacity.
+ * UNDER SJMI_DICT_OVERFLOW n_rows, n_valid, n_other, the validity bitmap and the flag are still exact; n_distinct is some number
+ * above dict_capacity; the indices and the dictionary buffers hold unspecified values inside their stated extents (d_indices
+ * [0, live), d_dict_rows [0, dict_capacity), d_dict_offsets[0]), nothing outside them is written, no dictionary byte is copied
+ * (dict_bytes = 0), and the call completes.  dict_capacity == 0 is legal: an overflow unless no row is VALID.
+ * THE EMPTY CASES.  n_rows == 0, or live == 0, is legal: d_dict_offsets[0] = 0, a zero record; no kernel is launched with an
+ * empty grid.
+ * ARGUMENTS.  SJMI_ERR_ARG: dict_capacity > SJMI_DICT_MAX_ENTRIES; NULL d_indices, d_dict_offsets or d_result; NULL d_types,
+ * d_values or d_string_buffer with n_rows > 0; NULL d_dict_bytes with dict_byte_capacity > 0; d_values, d_row_count,
+ * d_validity, d_dict_rows, d_dict_offsets or d_result not 8-byte aligned, d_indices not 4-byte aligned; n_rows >= 2^40.
+ * STREAM AND SCRATCH.  Asynchronous on `stream` (NULL = the context's), no host synchronisation, nothing queued but plain
+ * kernels that the stream orders: one that clears the hash table (no memset node), the insert -- the only kernel with atomics:
+ * agent-scope relaxed load / compare-exchange / fetch-min on the table's words; nothing spins or waits for another workgroup,
+ * and a probe is bounded by the table's slots --, the count of first rows per 1024 rows, their scan by one workgroup (the
+ * record), the ranks, the indices, and the four string-gather kernels over the dictionary (the copy only with a byte capacity).
+ * With n_rows == 0 only the two one-workgroup kernels are queued.  The context owns a scratch slot of its own for this call: the
+ * table (32 bytes per entry of dict_capacity, rounded up to a power of two), 4 bytes per row, the chunk counts and the compacted
+ * dictionary column.  A call that needs more of it than any before it on this context grows it, which waits for the device and
+ * may block.  It is one per context: dictionary calls on ONE context must be ordered with respect to each other.
+ * KNOWN LIMITS.  One lane hashes and compares one row's string, eight bytes per trip: very long strings are slow.  A dictionary's
+ * bytes are copied by the string gather's kernel, with its known limit. */
+#define SJMI_DICT_MAX_ENTRIES (1u << 20)
+#define SJMI_DICT_OVERFLOW 1u              /* more distinct values than dict_capacity */
+#define SJMI_DICT_BYTES_OVERFLOW 2u        /* dict_bytes > dict_byte_capacity */
+typedef struct sjmi_dict_result {
+    uint64_t n_rows, n_valid, n_other, n_distinct, dict_bytes;
+    uint32_t flags, reserved;
+} sjmi_dict_result;
+int sjmi_dictionary_column_device(sjmi_ctx* ctx, const void* d_types, const void* d_values, uint64_t n_rows, const void* d_row_count,
+                                  const void* d_string_buffer, void* d_indices, void* d_validity, uint64_t dict_capacity, void* d_dict_rows,
+                                  void* d_dict_offsets, void* d_dict_bytes, uint64_t dict_byte_capacity, void* d_result, void* stream);
+
 /* Optional: page-lock caller-owned host memory that is passed to the host-buffer entry points again and again
  * (SimdJsonParser's padded input, index array and string buffer): H2D / D2H copies of pinned memory skip the
  * driver's staging copy (3-4x faster for the ~1 MB transfers of a single-document parse).  Purely a performance

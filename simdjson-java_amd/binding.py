@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_HERE)
 _CSRC = os.path.join(_HERE, "csrc")
 _LIB = os.path.join(_HERE, "libsjmi.so")
-SOURCES = ["stage1.hip", "strings.hip", "batch.hip", "walk.hip", "coop_walk.hip", "masks.hip", "select.hip", "explode.hip", "ndjson.hip", "strcol.hip", "filter.hip", "arrowcol.hip", "timecol.hip", "sjmi_api.hip", "host/simdjson_parser.cpp"]
+SOURCES = ["stage1.hip", "strings.hip", "batch.hip", "walk.hip", "coop_walk.hip", "masks.hip", "select.hip", "explode.hip", "ndjson.hip", "strcol.hip", "filter.hip", "arrowcol.hip", "timecol.hip", "dictcol.hip", "sjmi_api.hip", "host/simdjson_parser.cpp"]
 
 ST_UTF8, ST_UNCLOSED, ST_UNESCAPED, ST_CAPACITY, ST_INTERNAL = 1, 2, 4, 0x100, 0x200
 PADDING = 64
@@ -110,7 +110,7 @@ EXPORTS = ["sjmi_create", "sjmi_destroy", "sjmi_last_error", "sjmi_version", "sj
            "sjmi_explode_plan_compile", "sjmi_explode_plan_destroy", "sjmi_explode_batch_device",
            "sjmi_ndjson_offsets_device", "sjmi_ndjson_offsets", "sjmi_ndjson_tile_bytes", "sjmi_string_column_device",
            "sjmi_filter_plan_compile", "sjmi_filter_plan_destroy", "sjmi_filter_columns_device", "sjmi_arrow_columns_device",
-           "sjmi_time_columns_device"]
+           "sjmi_time_columns_device", "sjmi_dictionary_column_device"]
 
 
 # Handles that are still open when the interpreter exits are closed HERE, in an atexit hook -- i.e. while the HIP runtime
@@ -290,6 +290,9 @@ def lib():
         L.sjmi_time_columns_device.restype = C.c_int
         L.sjmi_time_columns_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64,
                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+        L.sjmi_dictionary_column_device.restype = C.c_int
+        L.sjmi_dictionary_column_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                    C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
         L.sjmi_select_batch_device.restype = C.c_int
         L.sjmi_select_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
                                                C.c_void_p, C.c_void_p, C.c_void_p]
@@ -622,6 +625,19 @@ class Context:
                                                    n_cols, col_stride, n_rows, d_row_count or None, d_sb or None, d_data or None, data_stride,
                                                    d_validity or None, validity_stride, d_results or None, stream),
                     "sjmi_time_columns_device")
+
+    def dictionary_column_device(self, d_types, d_values, n_rows, d_row_count, d_sb, d_indices, d_validity, dict_capacity, d_dict_rows,
+                                 d_dict_offsets, d_dict_bytes, dict_byte_capacity, d_result, stream=0):
+        """sjmi_dictionary_column_device: ONE (types, values) column as an Arrow dictionary array, the dictionary in the order of
+        first occurrence.  d_row_count (None / 0: every row) = a device uint64 that holds the live rows; d_indices (int32
+        [n_rows]), d_validity (uint64 words, LSB first; None / 0: not written), d_dict_rows (int64 [dict_capacity]; None / 0: not
+        written), d_dict_offsets (int64 [dict_capacity + 1]), d_dict_bytes (dict_byte_capacity bytes; None / 0 with capacity 0:
+        the sizing call), d_result = device sjmi_dict_result (6 x int64: live rows, n_valid, n_other, n_distinct, dict_bytes,
+        flags in the low half of the sixth).  Asynchronous on `stream`."""
+        self._check(lib().sjmi_dictionary_column_device(self._h, d_types or None, d_values or None, n_rows, d_row_count or None, d_sb or None,
+                                                        d_indices or None, d_validity or None, dict_capacity, d_dict_rows or None,
+                                                        d_dict_offsets or None, d_dict_bytes or None, dict_byte_capacity, d_result or None,
+                                                        stream), "sjmi_dictionary_column_device")
 
     def ndjson_offsets(self, data):
         """sjmi_ndjson_offsets (host form) -> (doc_offsets np.uint64 [n_docs + 1], consumed, flags): the documents are the

@@ -130,6 +130,7 @@ struct sjmi_ctx {
     DevBuf<void> d_ws_filter;                // sjmi_filter_columns_device: a count per chunk of rows and the keep words (a slot of its own)
     DevBuf<void> d_ws_arrow;                 // sjmi_arrow_columns_device: a packed count word per field and chunk of rows (a slot of its own)
     DevBuf<void> d_ws_time;                  // sjmi_time_columns_device: a packed count word per field and chunk of rows (a slot of its own)
+    DevBuf<void> d_ws_dict;                  // sjmi_dictionary_column_device: the hash table, a slot per row, the chunk counts, the compacted dictionary column (a slot of its own)
     std::string err;
 };
 
@@ -1067,6 +1068,25 @@ int sjmi_time_columns_device(sjmi_ctx* c, const sjmi_time_field* fields, uint64_
     if (!grow_scratch(c, c->d_ws_time, sjmi::timecol_workspace_bytes(n_fields, n_rows), "hipMalloc(ws_time)")) return SJMI_ERR_HIP;
     return fail(c, "time columns launch", sjmi::timecol_launch(plan, d_types, d_values, col_stride, n_rows, d_row_count, d_string_buffer, d_data,
                                                                data_stride, d_validity, validity_stride, d_results, c->d_ws_time, st))
+               ? SJMI_ERR_HIP
+               : SJMI_OK;
+}
+
+int sjmi_dictionary_column_device(sjmi_ctx* c, const void* d_types, const void* d_values, uint64_t n_rows, const void* d_row_count,
+                                  const void* d_string_buffer, void* d_indices, void* d_validity, uint64_t dict_capacity, void* d_dict_rows,
+                                  void* d_dict_offsets, void* d_dict_bytes, uint64_t dict_byte_capacity, void* d_result, void* stream) {
+    if (!c || !d_indices || !d_dict_offsets || !d_result || (n_rows && (!d_types || !d_values || !d_string_buffer))) return SJMI_ERR_ARG;
+    if (dict_capacity > SJMI_DICT_MAX_ENTRIES || (dict_byte_capacity && !d_dict_bytes)) return SJMI_ERR_ARG;
+    if (n_rows >= (1ull << 40)) return SJMI_ERR_ARG;  // (one workgroup per 1024 rows; a row fits the 40 bits of a table word)
+    if (((uintptr_t)d_values & 7) || ((uintptr_t)d_row_count & 7) || ((uintptr_t)d_validity & 7) || ((uintptr_t)d_dict_rows & 7) ||
+        ((uintptr_t)d_dict_offsets & 7) || ((uintptr_t)d_result & 7) || ((uintptr_t)d_indices & 3))
+        return SJMI_ERR_ARG;
+    if (fail(c, "hipSetDevice", hipSetDevice(c->device))) return SJMI_ERR_HIP;
+    hipStream_t st = stream_of(c, stream);
+    if (!grow_scratch(c, c->d_ws_dict, sjmi::dictcol_workspace_bytes(n_rows, dict_capacity), "hipMalloc(ws_dict)")) return SJMI_ERR_HIP;
+    return fail(c, "dictionary column launch",
+                sjmi::dictcol_launch(d_types, d_values, n_rows, d_row_count, d_string_buffer, d_indices, d_validity, dict_capacity, d_dict_rows,
+                                     d_dict_offsets, d_dict_bytes, dict_byte_capacity, d_result, c->d_ws_dict, st))
                ? SJMI_ERR_HIP
                : SJMI_OK;
 }

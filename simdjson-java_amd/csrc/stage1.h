@@ -441,4 +441,15 @@ hipError_t timecol_launch(const void* plan, const void* d_types, const void* d_v
                           const void* d_row_count, const void* d_string_buffer, void* d_data, uint64_t data_stride, void* d_validity,
                           uint64_t validity_stride, void* d_results, void* d_ws, hipStream_t stream);
 
+// ---- a string column as an Arrow dictionary array (dictcol.hip) ----
+// scratch of one call: the hash table for dict_capacity entries, a slot per row, two counts per chunk of 1024 rows, the compacted
+// dictionary column and the string gather's sums over it
+size_t dictcol_workspace_bytes(uint64_t n_rows, uint64_t dict_capacity);
+// k_dict_clear, k_dict_insert (d_validity, may be NULL), k_dict_count, k_dict_scan (the sjmi_dict_result at d_result), k_dict_emit
+// (d_dict_rows, may be NULL), k_dict_index and the string gather's four kernels over the dictionary (the copy with
+// dict_byte_capacity != 0); n_rows == 0: the two scans only.  d_row_count (may be NULL) is read by the kernels
+hipError_t dictcol_launch(const void* d_types, const void* d_values, uint64_t n_rows, const void* d_row_count, const void* d_string_buffer,
+                          void* d_indices, void* d_validity, uint64_t dict_capacity, void* d_dict_rows, void* d_dict_offsets, void* d_dict_bytes,
+                          uint64_t dict_byte_capacity, void* d_result, void* d_ws, hipStream_t stream);
+
 }  // namespace sjmi

@@ -310,6 +310,49 @@ class BatchShard:
                                         n_rows, validity.data_ptr() if n_rows else 0, words, results.data_ptr(), stream)
         return data, validity, results
 
+    def dictionary_column(self, types, values, dict_capacity, byte_capacity=None, row_count=None, stream=0):
+        """ONE string column as an Arrow dictionary array: sjmi_dictionary_column_device on a 1-D (types uint8, values int64)
+        tensor pair, as string_column() takes it, whose string cells point into self.sb.  The dictionary holds at most
+        dict_capacity distinct values (at most 2^20), in the order of their first occurrence.  row_count is an optional 1-element
+        int64 DEVICE tensor -- result[0:1] of filter(), exp_row_offsets[n_docs:] of explode() -- that the kernels read: the live
+        rows are min(n_rows, row_count[0]).  -> (indices [n_rows] int32, validity [ceil(n_rows / 64)] int64 words (LSB first),
+        dict_rows [dict_capacity] int64, dict_offsets [dict_capacity + 1] int64, dict_bytes uint8, result [6] int64 = live rows,
+        n_valid, n_other, n_distinct, dict_bytes, flags), new tensors every call.  Indices and validity words at or above the live
+        rows, and dictionary entries at or above result[3], are not written: the caller slices by the record.  byte_capacity=
+        None: a sizing call, the record read back -- the one host synchronisation -- dict_bytes allocated exactly and the second
+        call made.  With a byte_capacity nothing synchronises: bytes at or behind it are not written and result[5] & 2
+        (SJMI_DICT_BYTES_OVERFLOW) says so.  result[5] & 1 (SJMI_DICT_OVERFLOW): more distinct values than dict_capacity; only
+        the counts and the validity mean anything then.  Call it on a step that check() has accepted, like string_column()."""
+        import torch
+        assert types.dim() == 1 and values.dim() == 1 and types.numel() == values.numel()
+        assert types.dtype == torch.uint8 and values.dtype == torch.int64 and types.is_contiguous() and values.is_contiguous()
+        if row_count is not None:
+            assert row_count.dtype == torch.int64 and row_count.numel() == 1 and row_count.device == types.device
+        n_rows, dict_capacity = int(types.numel()), int(dict_capacity)
+        indices = torch.empty(n_rows, dtype=torch.int32, device=self.device)
+        validity = torch.empty((n_rows + 63) // 64, dtype=torch.int64, device=self.device)
+        dict_rows = torch.empty(dict_capacity, dtype=torch.int64, device=self.device)
+        dict_offsets = torch.empty(dict_capacity + 1, dtype=torch.int64, device=self.device)
+        result = torch.empty(6, dtype=torch.int64, device=self.device)  # sjmi_dict_result (every call writes all of it)
+        # (an empty tensor's pointer may be anything: the call gets NULL for what has no entries -- but d_indices must not be NULL)
+        one = torch.empty(1, dtype=torch.int32, device=self.device)
+        call = lambda data, capacity: self.engine.dictionary_column_device(
+            types.data_ptr() if n_rows else 0, values.data_ptr() if n_rows else 0, n_rows, row_count.data_ptr() if row_count is not None else 0,
+            self.sb.data_ptr(), indices.data_ptr() if n_rows else one.data_ptr(), validity.data_ptr() if n_rows else 0, dict_capacity,
+            dict_rows.data_ptr() if dict_capacity else 0, dict_offsets.data_ptr(), data.data_ptr() if capacity else 0, capacity,
+            result.data_ptr(), stream)
+        if byte_capacity is None:
+            call(None, 0)
+            if str(self.device) != "cpu":
+                torch.cuda.synchronize(self.device)  # (`stream` need not be the one torch's copy is queued on)
+            byte_capacity = int(result.cpu()[4])
+            if not byte_capacity:
+                return indices, validity, dict_rows, dict_offsets, torch.empty(0, dtype=torch.uint8, device=self.device), result
+        byte_capacity = int(byte_capacity)
+        data = torch.empty(byte_capacity, dtype=torch.uint8, device=self.device)
+        call(data, byte_capacity)
+        return indices, validity, dict_rows, dict_offsets, data, result
+
     def counts_tensor(self):
         """The per-shard row of the count gather, on the device, without a host copy:
         {documents, structurals, string bytes, failed + handed-back documents}."""
