@@ -300,6 +300,22 @@ def lib():
     return _lib
 
 
+def _fields(fields, dtype, what, whats, flag_bits):
+    """the encoder under arrow_fields() and time_fields(): tuples (column, <what>[, flag ...]) -> the 16-byte field array of `dtype`"""
+    if isinstance(fields, np.ndarray) and fields.dtype == dtype:
+        return np.ascontiguousarray(fields)
+    enc = np.zeros(len(fields), dtype=dtype)
+    for k, field in enumerate(fields):
+        column, name, flags = field[0], field[1], field[2:]
+        if name not in whats or any(f not in flag_bits for f in flags) or not 0 <= int(column) < 1 << 32:
+            raise ValueError("%s field %d: unknown %s or flag, or column out of range: %r" % (what[0], k, what[1], (field,)))
+        bits = 0
+        for f in flags:
+            bits |= flag_bits[f]
+        enc[k] = (int(column), whats[name], bits, 0)
+    return enc
+
+
 ARROW_KINDS = {"int64": 1, "float64": 2, "bool": 3}     # SJMI_ARROW_<KIND>
 ARROW_FLAGS = {"integral_doubles": 1}                   # SJMI_ARROW_F_*
 ARROW_FIELD = np.dtype([("column", "<u4"), ("kind", "<u4"), ("flags", "<u4"), ("reserved", "<u4")])  # sjmi_arrow_field
@@ -308,18 +324,7 @@ ARROW_FIELD = np.dtype([("column", "<u4"), ("kind", "<u4"), ("flags", "<u4"), ("
 def arrow_fields(fields):
     """(column, kind[, flag ...]) tuples -> the sjmi_arrow_field array of Context.arrow_columns_device (an array of that dtype is
     taken as it is: the library validates it).  ValueError for a kind or a flag that has no name here."""
-    if isinstance(fields, np.ndarray) and fields.dtype == ARROW_FIELD:
-        return np.ascontiguousarray(fields)
-    enc = np.zeros(len(fields), dtype=ARROW_FIELD)
-    for k, field in enumerate(fields):
-        column, kind, flags = field[0], field[1], field[2:]
-        if kind not in ARROW_KINDS or any(f not in ARROW_FLAGS for f in flags) or not 0 <= int(column) < 1 << 32:
-            raise ValueError("arrow field %d: unknown kind or flag, or column out of range: %r" % (k, (field,)))
-        bits = 0
-        for f in flags:
-            bits |= ARROW_FLAGS[f]
-        enc[k] = (int(column), ARROW_KINDS[kind], bits, 0)
-    return enc
+    return _fields(fields, ARROW_FIELD, ("arrow", "kind"), ARROW_KINDS, ARROW_FLAGS)
 
 
 TIME_UNITS = {"s": 0, "ms": 1, "us": 2, "ns": 3}        # SJMI_TIME_<UNIT>, under Arrow's names
@@ -331,18 +336,7 @@ def time_fields(fields):
     """(column, unit[, flag ...]) tuples such as (0, "us") or (2, "ns", "naive_utc") -> the sjmi_time_field array of
     Context.time_columns_device (an array of that dtype is taken as it is: the library validates it).  ValueError for a unit or a
     flag that has no name here."""
-    if isinstance(fields, np.ndarray) and fields.dtype == TIME_FIELD:
-        return np.ascontiguousarray(fields)
-    enc = np.zeros(len(fields), dtype=TIME_FIELD)
-    for k, field in enumerate(fields):
-        column, unit, flags = field[0], field[1], field[2:]
-        if unit not in TIME_UNITS or any(f not in TIME_FLAGS for f in flags) or not 0 <= int(column) < 1 << 32:
-            raise ValueError("time field %d: unknown unit or flag, or column out of range: %r" % (k, (field,)))
-        bits = 0
-        for f in flags:
-            bits |= TIME_FLAGS[f]
-        enc[k] = (int(column), TIME_UNITS[unit], bits, 0)
-    return enc
+    return _fields(fields, TIME_FIELD, ("time", "unit"), TIME_UNITS, TIME_FLAGS)
 
 
 class Context:
@@ -605,11 +599,8 @@ class Context:
         d_data (uint64 [n_fields * data_stride]; None / 0 with stride 0: the counting call), d_validity (uint64 words, LSB first,
         [n_fields * validity_stride]; None / 0: not written), d_results = device sjmi_arrow_field_result (n_fields x 4 int64:
         n_rows, n_valid, n_other, n_inexact).  Asynchronous on `stream`."""
-        enc = arrow_fields(fields)
-        self._check(lib().sjmi_arrow_columns_device(self._h, enc.ctypes.data if enc.size else None, enc.size, d_types or None, d_values or None,
-                                                    n_cols, col_stride, n_rows, d_row_count or None, d_data or None, data_stride,
-                                                    d_validity or None, validity_stride, d_results or None, stream),
-                    "sjmi_arrow_columns_device")
+        self._field_columns("sjmi_arrow_columns_device", arrow_fields(fields), d_types, d_values, n_cols, col_stride, n_rows, d_row_count, (), d_data,
+                            data_stride, d_validity, validity_stride, d_results, stream)
 
     def time_columns_device(self, fields, d_types, d_values, n_cols, col_stride, n_rows, d_row_count, d_sb, d_data, data_stride, d_validity,
                             validity_stride, d_results, stream=0):
@@ -620,11 +611,15 @@ class Context:
         the counting call), d_validity (uint64 words, LSB first, [n_fields * validity_stride]; None / 0: not written), d_results =
         device sjmi_time_field_result (n_fields x 6 int64: n_rows, n_valid, n_other, n_malformed, n_range, n_inexact).
         Asynchronous on `stream`."""
-        enc = time_fields(fields)
-        self._check(lib().sjmi_time_columns_device(self._h, enc.ctypes.data if enc.size else None, enc.size, d_types or None, d_values or None,
-                                                   n_cols, col_stride, n_rows, d_row_count or None, d_sb or None, d_data or None, data_stride,
-                                                   d_validity or None, validity_stride, d_results or None, stream),
-                    "sjmi_time_columns_device")
+        self._field_columns("sjmi_time_columns_device", time_fields(fields), d_types, d_values, n_cols, col_stride, n_rows, d_row_count, (d_sb or None,),
+                            d_data, data_stride, d_validity, validity_stride, d_results, stream)
+
+    def _field_columns(self, entry, enc, d_types, d_values, n_cols, col_stride, n_rows, d_row_count, strings, d_data, data_stride, d_validity,
+                       validity_stride, d_results, stream):
+        """the call under arrow_columns_device() and time_columns_device(): `strings` is () or (the string buffer,)"""
+        self._check(getattr(lib(), entry)(self._h, enc.ctypes.data if enc.size else None, enc.size, d_types or None, d_values or None, n_cols, col_stride,
+                                          n_rows, d_row_count or None, *strings, d_data or None, data_stride, d_validity or None, validity_stride,
+                                          d_results or None, stream), entry)
 
     def dictionary_column_device(self, d_types, d_values, n_rows, d_row_count, d_sb, d_indices, d_validity, dict_capacity, d_dict_rows,
                                  d_dict_offsets, d_dict_bytes, dict_byte_capacity, d_result, stream=0):

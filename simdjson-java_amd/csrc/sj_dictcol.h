@@ -37,7 +37,7 @@
 #pragma once
 #include <stdint.h>
 
-#include "sj_block.h"
+#include "sj_fieldcol.h"
 #include "sj_strcol.h"
 
 constexpr uint32_t DC_CHUNK_ROWS = 1024;       // rows of a chunk = threads of its workgroup
@@ -62,12 +62,9 @@ struct DcColumn {
     const uint8_t* sb;
     uint32_t chunk_rows;  // a multiple of 64
 };
-SJ_HD sj_u64 dc_chunks(sj_u64 rows, uint32_t chunk_rows) { return (rows + chunk_rows - 1) / chunk_rows; }
-SJ_HD sj_u64 dc_live(const DcColumn& c) {
-    if (!c.row_count) return c.n_rows;
-    const sj_u64 n = *c.row_count;
-    return n < c.n_rows ? n : c.n_rows;
-}
+// the frame's chunks and live rows (sj_fieldcol.h) on this operator's column
+SJ_HD sj_u64 dc_chunks(sj_u64 rows, uint32_t chunk_rows) { return fc_chunks(rows, chunk_rows); }
+SJ_HD sj_u64 dc_live(const DcColumn& c) { return fc_live(c.n_rows, c.row_count); }
 SJ_HD sj_u64 dc_slots(sj_u64 dict_capacity) {
     sj_u64 s = 2;
     while (s < 2 * dict_capacity) s <<= 1;

@@ -4,7 +4,7 @@
 //
 // The cell of column c, row r is types[c * col_stride + r] / values[c * col_stride + r]; a FIELD is (column, unit, flags).  A
 // row's chain is three dependent loads: the type byte, the value word -- only behind '"' -- and the string's bytes at
-// strings + (value & 0xFFFFFFFF) -- only behind the test of the length value >> 32, which must be 20..35 (19 with NAIVE_UTC).
+// c.strings + (value & 0xFFFFFFFF) -- only behind the test of the length value >> 32, which must be 20..35 (19 with NAIVE_UTC).
 // tc_load_* / tc_string bring those bytes into five register words (byte i of the string = byte i & 7 of word i >> 3, zeros from the
 // length on), in one of two forms:
 //   tc_load_bytes    one byte-wide load per byte of the string
@@ -14,9 +14,9 @@
 // digit ranges and separators of the fixed 19 bytes as SWAR tests, the fraction and the zone on the 16 bytes behind them.
 // Everything is integer arithmetic without a signed overflow: only NANO can leave int64, and that is decided on the seconds.
 //
-// The rows that count are [0, live), live = min(n_rows, *row_count) read HERE, on the device.  Two passes: tc_parse_chunk per
-// (chunk of rows, field) -- the data words, the validity words and the chunk's five counts packed into one scratch word -- and
-// tc_finish per field: the sum of its chunk words, the record.  No atomics, and no group waits for another.
+// One of the two operators in the frame of sj_fieldcol.h -- the field, the plan, the column set, the live rows, the packed chunk
+// counts and the finish pass are written there.  A field's `what` is its UNIT.  The chunk pass is tc_parse_chunk: the data
+// words, the validity words and the chunk's five counts.
 //
 // The lanes come from the caller: takes a workgroup G (sj_group.h; a wave is 64 consecutive rows) and uses lanes, lane, waves,
 // wave, first, scan_add, and group_ballots (sj_group_ballots.h): a lane can work on ROWS rows of as many waves' worth of rows
@@ -28,66 +28,33 @@
 #pragma once
 #include <stdint.h>
 
-#include "sj_block.h"
+#include "sj_fieldcol.h"
 
 constexpr uint32_t TC_CHUNK_ROWS = 256;  // rows of a chunk: TC_LANE_ROWS per thread of its workgroup
 constexpr uint32_t TC_LANE_ROWS = 1;     // rows whose loads one lane has in flight (1, 2, 4, 8 were measured: profiles/r16)
-constexpr uint32_t TC_MAX_FIELDS = 64;    // SJMI_TIME_MAX_FIELDS
 enum : uint32_t { TC_SECOND = 0, TC_MILLI = 1, TC_MICRO = 2, TC_NANO = 3 };  // SJMI_TIME_<UNIT>
 constexpr uint32_t TC_F_NAIVE_UTC = 1u;                                     // SJMI_TIME_F_NAIVE_UTC
 constexpr uint32_t TC_MIN_LEN = 20, TC_MAX_LEN = 35;  // "YYYY-MM-DDThh:mm:ssZ" .. with 9 digits of fraction and "+hh:mm"
 
-struct TcField {  // sjmi_time_field
-    uint32_t column, unit, flags, reserved;
-};
-
-// a validated schema: what the kernels take BY VALUE as a launch argument (nothing of it lives in device memory)
-struct TcPlan {
-    uint32_t n_fields, pad[3];
-    TcField fields[TC_MAX_FIELDS];
-};
-
 struct TcResult {  // sjmi_time_field_result
     sj_u64 n_rows, n_valid, n_other, n_malformed, n_range, n_inexact;
 };
+using TcCounts = FcCounts<5, 12, TC_CHUNK_ROWS>;  // VALID, other, malformed, range, inexact: the five behind n_rows
+// the frame under this operator's names, as its kernel, its simulation and its callers spell them
+using TcField = FcField;  // what = the UNIT
+using TcPlan = FcPlan;
+using TcOut = FcOut;
+SJ_HD sj_u64 tc_chunks(sj_u64 rows, uint32_t chunk_rows) { return fc_chunks(rows, chunk_rows); }
 
-struct TcCols {
-    const uint8_t* types;  // any alignment: loaded as bytes
-    const sj_u64* values;
-    sj_u64 col_stride, n_rows;
-    const sj_u64* row_count;  // NULL, or where the live rows are counted (on the device)
-    const uint8_t* strings;   // the string buffer the '"' cells point into
-    uint32_t chunk_rows;      // a multiple of 64
-};
-SJ_HD sj_u64 tc_chunks(sj_u64 rows, uint32_t chunk_rows) { return (rows + chunk_rows - 1) / chunk_rows; }
-SJ_HD sj_u64 tc_live(const TcCols& c) {
-    if (!c.row_count) return c.n_rows;
-    const sj_u64 n = *c.row_count;
-    return n < c.n_rows ? n : c.n_rows;
-}
-
-struct TcOut {
-    sj_u64* data;  // NULL: the counting call
-    sj_u64 data_stride;
-    sj_u64* validity;  // NULL: not written
-    sj_u64 validity_stride;
+struct TcCols : FcCols {
+    const uint8_t* strings;  // the string buffer the '"' cells point into
+    uint32_t chunk_rows;     // a multiple of 64
 };
 
-// Host only: fields -> a plan.  0, or -2 (SJMI_ERR_ARG): no field or more than 64, a unit above NANO, a flag other than
-// NAIVE_UTC, reserved != 0, a column >= n_cols.
+// Host only: fields -> a plan.  0, or -2 (SJMI_ERR_ARG): what fc_plan_compile refuses, a unit above NANO, a flag other than
+// NAIVE_UTC.
 inline int tc_plan_compile(const TcField* fields, sj_u64 n_fields, sj_u64 n_cols, TcPlan* out) {
-    if (!fields || n_fields == 0 || n_fields > TC_MAX_FIELDS) return -2;
-    out->n_fields = (uint32_t)n_fields;
-    out->pad[0] = out->pad[1] = out->pad[2] = 0;
-    for (uint32_t k = 0; k < TC_MAX_FIELDS; ++k) {
-        const TcField zero = {0, 0, 0, 0};
-        out->fields[k] = k < n_fields ? fields[k] : zero;
-    }
-    for (sj_u64 k = 0; k < n_fields; ++k) {
-        const TcField& f = fields[k];
-        if (f.unit > TC_NANO || (f.flags & ~TC_F_NAIVE_UTC) || f.reserved != 0 || f.column >= n_cols) return -2;
-    }
-    return 0;
+    return fc_plan_compile(fields, n_fields, n_cols, out, [](const FcField& f) { return f.what <= TC_NANO && !(f.flags & ~TC_F_NAIVE_UTC); });
 }
 
 // ---- the fetch: a string of 19..35 bytes as five words, zeros from byte `len` on ----
@@ -252,10 +219,6 @@ SJ_HD TcCell tc_cell(uint32_t unit, uint32_t flags, uint8_t ty, bool wanted, uin
     return cell;
 }
 
-// a chunk's counts in one word: each is at most the chunk's rows
-constexpr uint32_t TC_COUNT_BITS = 12;
-constexpr sj_u64 TC_COUNT_MASK = (1ull << TC_COUNT_BITS) - 1;
-
 // pass 1, per chunk and field: the data words and the validity words of the chunk's live rows, and counts[field * nchunks +
 // chunk].  The chunk IS what the group takes in one go, without a loop: c.chunk_rows = 64 * g.waves() * ROWS, lane t of wave w
 // working on rows 64 * (w + k * waves) + t of the chunk, k < ROWS.  (A loop over more, with its invariants kept in registers
@@ -264,75 +227,56 @@ constexpr sj_u64 TC_COUNT_MASK = (1ull << TC_COUNT_BITS) - 1;
 // tc_load_words, else tc_load_bytes; ROWS: the rows a lane has in flight.
 template <bool WORDS, uint32_t ROWS, class G>
 SJ_HD void tc_parse_chunk(const G& g, const TcPlan& p, const TcCols& c, sj_u64 chunk, uint32_t field, const TcOut& o, sj_u64* counts) {
-    const sj_u64 live = tc_live(c);
+    const sj_u64 live = fc_live(c.n_rows, c.row_count);
     if (chunk * c.chunk_rows >= live) return;
-    const TcField f = p.fields[field];
-    const sj_u64 col = (sj_u64)f.column * c.col_stride;
-    sj_u64* data = o.data ? o.data + field * o.data_stride : nullptr;
-    sj_u64* validity = o.validity ? o.validity + field * o.validity_stride : nullptr;
-    const sj_u64 first = chunk * (c.chunk_rows / 64), end = first + c.chunk_rows / 64;
+    const FcChunk h = fc_chunk_head(p, c, chunk, field, o);
+    const sj_u64 end = h.first + c.chunk_rows / 64;
     sj_u64 mine = 0;  // (what the lanes of this wave count: one lane's on the device)
-    {
-        const sj_u64 at = first;
-        sj_u64 valid[ROWS];
-        group_ballots(g, [&](uint32_t t, bool (&vote)[ROWS]) {
-            sj_u64 r[ROWS], val[ROWS];
-            uint8_t ty[ROWS];
-            bool on[ROWS], wanted[ROWS];
-            TcRaw raw[ROWS];
-#pragma unroll
-            for (uint32_t k = 0; k < ROWS; ++k) {
-                const sj_u64 word = at + (sj_u64)k * g.waves() + g.wave();
-                r[k] = word * 64 + t;
-                on[k] = word < end && r[k] < live;
-                ty[k] = on[k] ? c.types[col + r[k]] : (uint8_t)0;
-            }
-#pragma unroll
-            for (uint32_t k = 0; k < ROWS; ++k) val[k] = ty[k] == '"' ? c.values[col + r[k]] : 0;
-#pragma unroll
-            for (uint32_t k = 0; k < ROWS; ++k) {
-                const TcRaw none = {{0, 0, 0, 0, 0, 0}};
-                const uint8_t* bytes = c.strings + (uint32_t)val[k];
-                const uint32_t len = (uint32_t)(val[k] >> 32);
-                wanted[k] = tc_wants_string(f.flags, ty[k], val[k]);
-                raw[k] = !wanted[k] ? none : WORDS ? tc_load_words(bytes, len) : tc_load_bytes(bytes, len);
-            }
-#pragma unroll
-            for (uint32_t k = 0; k < ROWS; ++k) {
-                const uint32_t len = (uint32_t)(val[k] >> 32);
-                const TcCell cell = tc_cell(f.unit, f.flags, ty[k], wanted[k], len, tc_string<WORDS>(raw[k], c.strings + (uint32_t)val[k], len));
-                vote[k] = on[k] && cell.valid;
-                if (!on[k]) continue;
-                if (data) data[r[k]] = cell.data;
-                mine += (cell.valid ? 1ull : 0ull) | (cell.other ? 1ull << TC_COUNT_BITS : 0ull) | (cell.malformed ? 1ull << (2 * TC_COUNT_BITS) : 0ull) |
-                        (cell.range ? 1ull << (3 * TC_COUNT_BITS) : 0ull) | (cell.inexact ? 1ull << (4 * TC_COUNT_BITS) : 0ull);
-            }
-        }, valid);
+    sj_u64 valid[ROWS];
+    group_ballots(g, [&](uint32_t t, bool (&vote)[ROWS]) {
+        sj_u64 r[ROWS], val[ROWS];
+        uint8_t ty[ROWS];
+        bool on[ROWS], wanted[ROWS];
+        TcRaw raw[ROWS];
 #pragma unroll
         for (uint32_t k = 0; k < ROWS; ++k) {
-            const sj_u64 word = at + (sj_u64)k * g.waves() + g.wave();
-            if (validity && word < end && word * 64 < live && g.first()) validity[word] = valid[k];
+            const sj_u64 word = h.first + (sj_u64)k * g.waves() + g.wave();
+            r[k] = word * 64 + t;
+            on[k] = word < end && r[k] < live;
+            ty[k] = on[k] ? c.types[h.col + r[k]] : (uint8_t)0;
         }
+#pragma unroll
+        for (uint32_t k = 0; k < ROWS; ++k) val[k] = ty[k] == '"' ? c.values[h.col + r[k]] : 0;
+#pragma unroll
+        for (uint32_t k = 0; k < ROWS; ++k) {
+            const TcRaw none = {{0, 0, 0, 0, 0, 0}};
+            const uint8_t* bytes = c.strings + (uint32_t)val[k];
+            const uint32_t len = (uint32_t)(val[k] >> 32);
+            wanted[k] = tc_wants_string(h.f.flags, ty[k], val[k]);
+            raw[k] = !wanted[k] ? none : WORDS ? tc_load_words(bytes, len) : tc_load_bytes(bytes, len);
+        }
+#pragma unroll
+        for (uint32_t k = 0; k < ROWS; ++k) {
+            const uint32_t len = (uint32_t)(val[k] >> 32);
+            const TcCell cell = tc_cell(h.f.what, h.f.flags, ty[k], wanted[k], len, tc_string<WORDS>(raw[k], c.strings + (uint32_t)val[k], len));
+            vote[k] = on[k] && cell.valid;
+            if (!on[k]) continue;
+            if (h.data) h.data[r[k]] = cell.data;
+            mine += TcCounts::of({cell.valid, cell.other, cell.malformed, cell.range, cell.inexact});
+        }
+    }, valid);
+#pragma unroll
+    for (uint32_t k = 0; k < ROWS; ++k) {
+        const sj_u64 word = h.first + (sj_u64)k * g.waves() + g.wave();
+        if (h.validity && word < end && word * 64 < live && g.first()) h.validity[word] = valid[k];
     }
     sj_u64 total;
     (void)g.scan_add(mine, &total);
-    if (g.lane() == 0) counts[(sj_u64)field * tc_chunks(c.n_rows, c.chunk_rows) + chunk] = total;
+    TcCounts::store(g, c, field, chunk, counts, total);
 }
 
-// pass 2, one group per field: the chunk words of the live chunks summed, the record
+// pass 2, one group per field: the frame's, with this operator's counts and record
 template <class G>
 SJ_HD void tc_finish(const G& g, const TcCols& c, uint32_t field, const sj_u64* counts, TcResult* res) {
-    const sj_u64 live = tc_live(c);
-    const sj_u64 nlive = tc_chunks(live, c.chunk_rows);
-    const sj_u64* mine = counts + (sj_u64)field * tc_chunks(c.n_rows, c.chunk_rows);
-    sj_u64 sum[5] = {0, 0, 0, 0, 0}, total[5];
-    for (sj_u64 k = g.lane(); k < nlive; k += g.lanes()) {
-        const sj_u64 w = mine[k];
-        for (uint32_t j = 0; j < 5; ++j) sum[j] += (w >> (j * TC_COUNT_BITS)) & TC_COUNT_MASK;
-    }
-    for (uint32_t j = 0; j < 5; ++j) (void)g.scan_add(sum[j], &total[j]);
-    if (g.lane() == 0) {
-        const TcResult r = {live, total[0], total[1], total[2], total[3], total[4]};
-        res[field] = r;
-    }
+    fc_finish<TcCounts>(g, c, field, counts, (sj_u64*)res);
 }

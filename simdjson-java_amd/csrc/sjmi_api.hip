@@ -1028,48 +1028,42 @@ int sjmi_filter_columns_device(sjmi_ctx* c, const sjmi_filter_plan* plan, const 
                : SJMI_OK;
 }
 
+// sjmi_arrow_columns_device and sjmi_time_columns_device: one frame (sj_fieldcol.h), `time` says which operator
+static int field_columns(sjmi_ctx* c, bool time, const void* fields, uint64_t n_fields, uint64_t n_cols, const sjmi::FieldColArgs& a, void* stream) {
+    if (!c || !a.d_results || a.col_stride < a.n_rows || (a.n_rows && (!a.d_types || !a.d_values || (time && !a.d_string_buffer)))) return SJMI_ERR_ARG;
+    if (a.n_rows >= (1ull << 40)) return SJMI_ERR_ARG;  // (one workgroup per chunk of rows)
+    if (a.d_data ? a.data_stride < a.n_rows : a.data_stride != 0) return SJMI_ERR_ARG;
+    if (a.d_validity && a.validity_stride < (a.n_rows + 63) / 64) return SJMI_ERR_ARG;
+    if (((uintptr_t)a.d_values & 7) || ((uintptr_t)a.d_row_count & 7) || ((uintptr_t)a.d_data & 7) || ((uintptr_t)a.d_validity & 7) ||
+        ((uintptr_t)a.d_results & 7))
+        return SJMI_ERR_ARG;
+    alignas(8) unsigned char plan[sjmi::FIELDCOL_PLAN_BYTES];
+    if ((time ? sjmi::timecol_plan : sjmi::arrowcol_plan)(fields, n_fields, n_cols, plan) != 0) return SJMI_ERR_ARG;
+    if (n_cols && a.col_stride > ~0ull / 8 / n_cols) return SJMI_ERR_ARG;  // (a column set is addressable, and so are the outputs)
+    if (a.data_stride > ~0ull / 8 / n_fields || a.validity_stride > ~0ull / 8 / n_fields) return SJMI_ERR_ARG;
+    if (fail(c, "hipSetDevice", hipSetDevice(c->device))) return SJMI_ERR_HIP;
+    hipStream_t st = stream_of(c, stream);
+    DevBuf<void>& ws = time ? c->d_ws_time : c->d_ws_arrow;
+    if (!grow_scratch(c, ws, (time ? sjmi::timecol_workspace_bytes : sjmi::arrowcol_workspace_bytes)(n_fields, a.n_rows),
+                      time ? "hipMalloc(ws_time)" : "hipMalloc(ws_arrow)"))
+        return SJMI_ERR_HIP;
+    const hipError_t e = (time ? sjmi::timecol_launch : sjmi::arrowcol_launch)(plan, a, ws, st);
+    return fail(c, time ? "time columns launch" : "arrow columns launch", e) ? SJMI_ERR_HIP : SJMI_OK;
+}
+
 int sjmi_arrow_columns_device(sjmi_ctx* c, const sjmi_arrow_field* fields, uint64_t n_fields, const void* d_types, const void* d_values,
                               uint64_t n_cols, uint64_t col_stride, uint64_t n_rows, const void* d_row_count, void* d_data,
                               uint64_t data_stride, void* d_validity, uint64_t validity_stride, void* d_results, void* stream) {
-    if (!c || !d_results || col_stride < n_rows || (n_rows && (!d_types || !d_values))) return SJMI_ERR_ARG;
-    if (n_rows >= (1ull << 40)) return SJMI_ERR_ARG;  // (one workgroup per 1024 rows)
-    if (d_data ? data_stride < n_rows : data_stride != 0) return SJMI_ERR_ARG;
-    if (d_validity && validity_stride < (n_rows + 63) / 64) return SJMI_ERR_ARG;
-    if (((uintptr_t)d_values & 7) || ((uintptr_t)d_row_count & 7) || ((uintptr_t)d_data & 7) || ((uintptr_t)d_validity & 7) || ((uintptr_t)d_results & 7))
-        return SJMI_ERR_ARG;
-    alignas(8) unsigned char plan[sjmi::ARROWCOL_PLAN_BYTES];
-    if (sjmi::arrowcol_plan(fields, n_fields, n_cols, plan) != 0) return SJMI_ERR_ARG;
-    if (n_cols && col_stride > ~0ull / 8 / n_cols) return SJMI_ERR_ARG;  // (a column set is addressable, and so are the outputs)
-    if (data_stride > ~0ull / 8 / n_fields || validity_stride > ~0ull / 8 / n_fields) return SJMI_ERR_ARG;
-    if (fail(c, "hipSetDevice", hipSetDevice(c->device))) return SJMI_ERR_HIP;
-    hipStream_t st = stream_of(c, stream);
-    if (!grow_scratch(c, c->d_ws_arrow, sjmi::arrowcol_workspace_bytes(n_fields, n_rows), "hipMalloc(ws_arrow)")) return SJMI_ERR_HIP;
-    return fail(c, "arrow columns launch", sjmi::arrowcol_launch(plan, d_types, d_values, col_stride, n_rows, d_row_count, d_data, data_stride,
-                                                                 d_validity, validity_stride, d_results, c->d_ws_arrow, st))
-               ? SJMI_ERR_HIP
-               : SJMI_OK;
+    return field_columns(c, false, fields, n_fields, n_cols,
+                         {d_types, d_values, col_stride, n_rows, d_row_count, nullptr, d_data, data_stride, d_validity, validity_stride, d_results}, stream);
 }
 
 int sjmi_time_columns_device(sjmi_ctx* c, const sjmi_time_field* fields, uint64_t n_fields, const void* d_types, const void* d_values,
                              uint64_t n_cols, uint64_t col_stride, uint64_t n_rows, const void* d_row_count, const void* d_string_buffer,
                              void* d_data, uint64_t data_stride, void* d_validity, uint64_t validity_stride, void* d_results, void* stream) {
-    if (!c || !d_results || col_stride < n_rows || (n_rows && (!d_types || !d_values || !d_string_buffer))) return SJMI_ERR_ARG;
-    if (n_rows >= (1ull << 40)) return SJMI_ERR_ARG;  // (one workgroup per 256 rows)
-    if (d_data ? data_stride < n_rows : data_stride != 0) return SJMI_ERR_ARG;
-    if (d_validity && validity_stride < (n_rows + 63) / 64) return SJMI_ERR_ARG;
-    if (((uintptr_t)d_values & 7) || ((uintptr_t)d_row_count & 7) || ((uintptr_t)d_data & 7) || ((uintptr_t)d_validity & 7) || ((uintptr_t)d_results & 7))
-        return SJMI_ERR_ARG;
-    alignas(8) unsigned char plan[sjmi::TIMECOL_PLAN_BYTES];
-    if (sjmi::timecol_plan(fields, n_fields, n_cols, plan) != 0) return SJMI_ERR_ARG;
-    if (n_cols && col_stride > ~0ull / 8 / n_cols) return SJMI_ERR_ARG;  // (a column set is addressable, and so are the outputs)
-    if (data_stride > ~0ull / 8 / n_fields || validity_stride > ~0ull / 8 / n_fields) return SJMI_ERR_ARG;
-    if (fail(c, "hipSetDevice", hipSetDevice(c->device))) return SJMI_ERR_HIP;
-    hipStream_t st = stream_of(c, stream);
-    if (!grow_scratch(c, c->d_ws_time, sjmi::timecol_workspace_bytes(n_fields, n_rows), "hipMalloc(ws_time)")) return SJMI_ERR_HIP;
-    return fail(c, "time columns launch", sjmi::timecol_launch(plan, d_types, d_values, col_stride, n_rows, d_row_count, d_string_buffer, d_data,
-                                                               data_stride, d_validity, validity_stride, d_results, c->d_ws_time, st))
-               ? SJMI_ERR_HIP
-               : SJMI_OK;
+    return field_columns(c, true, fields, n_fields, n_cols,
+                         {d_types, d_values, col_stride, n_rows, d_row_count, d_string_buffer, d_data, data_stride, d_validity, validity_stride, d_results},
+                         stream);
 }
 
 int sjmi_dictionary_column_device(sjmi_ctx* c, const void* d_types, const void* d_values, uint64_t n_rows, const void* d_row_count,

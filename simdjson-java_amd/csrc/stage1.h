@@ -417,29 +417,30 @@ hipError_t filter_launch(const sjmi_filter_plan* plan, const void* d_types, cons
                          uint64_t n_rows, const void* d_string_buffer, void* d_keep, void* d_rows, uint64_t out_capacity, void* d_out_types,
                          void* d_out_values, void* d_result, void* d_ws, hipStream_t stream);
 
-// ---- typed columns as Arrow int64 / float64 / bool arrays (arrowcol.hip) ----
-constexpr size_t ARROWCOL_PLAN_BYTES = 16 + 64 * 16;  // sizeof(AcPlan): the validated fields, a launch argument
-// the fields validated into plan_out (ARROWCOL_PLAN_BYTES, 8-byte aligned): 0, or -2 for a schema the call refuses
-int arrowcol_plan(const sjmi_arrow_field* fields, uint64_t n_fields, uint64_t n_cols, void* plan_out);
-// scratch of one call: one packed count word per field and chunk of 1024 rows
+// ---- fixed-width Arrow columns: int64 / float64 / bool (arrowcol.hip) and timestamps of RFC 3339 strings (timecol.hip) ----
+// Two operators in one frame (sj_fieldcol.h, fieldcol_launch.h): <op> is arrowcol or timecol.
+constexpr size_t FIELDCOL_PLAN_BYTES = 16 + 64 * 16;  // sizeof(FcPlan): the validated fields, a launch argument
+struct FieldColArgs {  // the device pointers and strides of one call, as the entry points of include/sjmi.h name them
+    const void *d_types, *d_values;
+    uint64_t col_stride, n_rows;
+    const void *d_row_count, *d_string_buffer;  // d_row_count may be NULL: the kernels read it; d_string_buffer: timecol only
+    void* d_data;
+    uint64_t data_stride;
+    void* d_validity;
+    uint64_t validity_stride;
+    void* d_results;
+};
+// the fields (sjmi_arrow_field / sjmi_time_field) validated into plan_out (FIELDCOL_PLAN_BYTES, 8-byte aligned): 0, or -2 for a
+// schema the call refuses
+int arrowcol_plan(const void* fields, uint64_t n_fields, uint64_t n_cols, void* plan_out);
+int timecol_plan(const void* fields, uint64_t n_fields, uint64_t n_cols, void* plan_out);
+// scratch of one call: one packed count word per field and chunk of 1024 (arrowcol) or 256 (timecol) rows
 size_t arrowcol_workspace_bytes(uint64_t n_fields, uint64_t n_rows);
-// k_arrow_convert (n_rows != 0: data, validity, the chunk words) and k_arrow_finish (the sjmi_arrow_field_result per field); the
-// plan goes by value, d_row_count (may be NULL) is read by the kernels
-hipError_t arrowcol_launch(const void* plan, const void* d_types, const void* d_values, uint64_t col_stride, uint64_t n_rows,
-                           const void* d_row_count, void* d_data, uint64_t data_stride, void* d_validity, uint64_t validity_stride,
-                           void* d_results, void* d_ws, hipStream_t stream);
-
-// ---- RFC 3339 string columns as Arrow timestamp arrays (timecol.hip) ----
-constexpr size_t TIMECOL_PLAN_BYTES = 16 + 64 * 16;  // sizeof(TcPlan): the validated fields, a launch argument
-// the fields validated into plan_out (TIMECOL_PLAN_BYTES, 8-byte aligned): 0, or -2 for a schema the call refuses
-int timecol_plan(const sjmi_time_field* fields, uint64_t n_fields, uint64_t n_cols, void* plan_out);
-// scratch of one call: one packed count word per field and chunk of 256 rows
 size_t timecol_workspace_bytes(uint64_t n_fields, uint64_t n_rows);
-// k_time_parse (n_rows != 0: data, validity, the chunk words) and k_time_finish (the sjmi_time_field_result per field); the plan
-// goes by value, d_row_count (may be NULL) is read by the kernels
-hipError_t timecol_launch(const void* plan, const void* d_types, const void* d_values, uint64_t col_stride, uint64_t n_rows,
-                          const void* d_row_count, const void* d_string_buffer, void* d_data, uint64_t data_stride, void* d_validity,
-                          uint64_t validity_stride, void* d_results, void* d_ws, hipStream_t stream);
+// the operator's convert kernel (n_rows != 0: data, validity, the chunk words) and the finish kernel (the record per field); the
+// plan goes by value
+hipError_t arrowcol_launch(const void* plan, const FieldColArgs& a, void* d_ws, hipStream_t stream);
+hipError_t timecol_launch(const void* plan, const FieldColArgs& a, void* d_ws, hipStream_t stream);
 
 // ---- a string column as an Arrow dictionary array (dictcol.hip) ----
 // scratch of one call: the hash table for dict_capacity entries, a slot per row, two counts per chunk of 1024 rows, the compacted

@@ -262,23 +262,7 @@ class BatchShard:
         Rows at or above the live rows, and the words behind them, are not written: the caller slices by results[:, 0] after
         its own synchronisation.  Call it on a step that check() has accepted: like string_column() and filter(), it is not
         queued again behind a step that check() had to run again."""
-        import torch
-        assert types.dim() == 2 and values.dim() == 2 and types.shape == values.shape
-        assert types.dtype == torch.uint8 and values.dtype == torch.int64 and types.is_contiguous() and values.is_contiguous()
-        n_cols, stride = int(types.shape[0]), int(types.shape[1])
-        n_rows = stride if n_rows is None else int(n_rows)
-        assert n_cols >= 1 and 0 <= n_rows <= stride
-        if row_count is not None:
-            assert row_count.dtype == torch.int64 and row_count.numel() == 1 and row_count.device == types.device
-        n_fields, words = len(fields), (n_rows + 63) // 64
-        data = torch.empty((n_fields, n_rows), dtype=torch.int64, device=self.device)
-        validity = torch.empty((n_fields, words), dtype=torch.int64, device=self.device)
-        results = torch.empty((n_fields, 4), dtype=torch.int64, device=self.device)  # (every call writes all of it)
-        # (an empty tensor's pointer may be anything: the call gets NULL for what has no entries)
-        self.engine.arrow_columns_device(fields, types.data_ptr() if n_rows else 0, values.data_ptr() if n_rows else 0, n_cols, stride, n_rows,
-                                         row_count.data_ptr() if row_count is not None else 0, data.data_ptr() if n_rows else 0, n_rows,
-                                         validity.data_ptr() if n_rows else 0, words, results.data_ptr(), stream)
-        return data, validity, results
+        return self._field_columns(self.engine.arrow_columns_device, 4, (), fields, types, values, n_rows, row_count, stream)
 
     def timestamp_columns(self, fields, types, values, n_rows=None, row_count=None, stream=0):
         """RFC 3339 string columns as Arrow timestamp arrays: sjmi_time_columns_device on a 2-D [n_cols, stride] (types uint8,
@@ -292,6 +276,11 @@ class BatchShard:
         the words behind them, are not written: the caller slices by results[:, 0] after its own synchronisation.  Call it on a
         step that check() has accepted: like arrow_columns(), it is not queued again behind a step that check() had to run
         again."""
+        return self._field_columns(self.engine.time_columns_device, 6, (self.sb.data_ptr(),), fields, types, values, n_rows, row_count, stream)
+
+    def _field_columns(self, call, record_words, strings, fields, types, values, n_rows, row_count, stream):
+        """arrow_columns() and timestamp_columns(): the checks of the tensor pair, the outputs and the call; `strings` is () or
+        (the string buffer's pointer,), record_words the width of a field's record"""
         import torch
         assert types.dim() == 2 and values.dim() == 2 and types.shape == values.shape
         assert types.dtype == torch.uint8 and values.dtype == torch.int64 and types.is_contiguous() and values.is_contiguous()
@@ -303,11 +292,11 @@ class BatchShard:
         n_fields, words = len(fields), (n_rows + 63) // 64
         data = torch.empty((n_fields, n_rows), dtype=torch.int64, device=self.device)
         validity = torch.empty((n_fields, words), dtype=torch.int64, device=self.device)
-        results = torch.empty((n_fields, 6), dtype=torch.int64, device=self.device)  # (every call writes all of it)
+        results = torch.empty((n_fields, record_words), dtype=torch.int64, device=self.device)  # (every call writes all of it)
         # (an empty tensor's pointer may be anything: the call gets NULL for what has no entries)
-        self.engine.time_columns_device(fields, types.data_ptr() if n_rows else 0, values.data_ptr() if n_rows else 0, n_cols, stride, n_rows,
-                                        row_count.data_ptr() if row_count is not None else 0, self.sb.data_ptr(), data.data_ptr() if n_rows else 0,
-                                        n_rows, validity.data_ptr() if n_rows else 0, words, results.data_ptr(), stream)
+        call(fields, types.data_ptr() if n_rows else 0, values.data_ptr() if n_rows else 0, n_cols, stride, n_rows,
+             row_count.data_ptr() if row_count is not None else 0, *strings, data.data_ptr() if n_rows else 0, n_rows,
+             validity.data_ptr() if n_rows else 0, words, results.data_ptr(), stream)
         return data, validity, results
 
     def dictionary_column(self, types, values, dict_capacity, byte_capacity=None, row_count=None, stream=0):

@@ -1,8 +1,8 @@
 """What the Arrow column export must give (include/sjmi.h, sjmi_arrow_columns_device), in Python alone: shares no code with the
 product.  reference() works cell by cell on Python int / float objects -- float(int) is correctly rounded (to nearest, ties to
 even) and int(float(v)) != v is an exact comparison of integers; numpy's casts are not to be trusted at 2^63.  check() compares
-everything a call owns word for word and, against CANARY-filled buffers, everything it must not touch: the words between the
-live rows and the stride, the slack between fields, the words in front of and behind both blocks.  The *_cases() generators
+everything a call owns word for word and, against CANARY-filled buffers, everything it must not touch (both are
+tests/fieldcol_common.py's, with the live rows and the stride rule of a case).  The *_cases() generators
 are seeded -- a name is a case -- and shared by the host simulation's tests (tests/test_host_arrowcol.py) and the GPU tests
 (tests/test_gpu_arrowcol.py).  A field is the tuple of binding.arrow_fields: (column, kind[, "integral_doubles"])."""
 import math
@@ -11,17 +11,15 @@ from collections import namedtuple
 
 import numpy as np
 
+from tests import fieldcol_common as F
+from tests.fieldcol_common import (ALL_TYPES, BACK, CANARY_WORD, DOUBLE, FALSE, FRONT, INT64_MAX, INT64_MIN, LONG, MASK, MISSING, NULL, STRING, TRUE,
+                                   check, live_counts, live_rows, pack_bits)
 from tests.strcol_common import WILD
 
-MISSING, NULL, LONG, DOUBLE, TRUE, FALSE, STRING = 0, ord("n"), ord("l"), ord("d"), ord("t"), ord("f"), ord('"')
-ALL_TYPES = [MISSING] + [ord(c) for c in 'nldtf"[{']
 KINDS = {"int64": 1, "float64": 2, "bool": 3}           # SJMI_ARROW_<KIND>
 FLAGS = {"integral_doubles": 1}                         # SJMI_ARROW_F_*
 FIELD = np.dtype([("column", "<u4"), ("kind", "<u4"), ("flags", "<u4"), ("reserved", "<u4")])  # sjmi_arrow_field
-MASK = (1 << 64) - 1
-INT64_MIN, INT64_MAX = -(1 << 63), (1 << 63) - 1
-CANARY_WORD = 0xC5C5C5C5C5C5C5C5
-FRONT, BACK = 3, 5                                      # canary words in front of and behind each output block
+RECORD_WORDS = 4                                        # n_rows, n_valid, n_other, n_inexact
 
 # types uint8 / values uint64 [n_cols, col_stride], n_rows <= col_stride; row_count None or what *d_row_count holds;
 # data_stride >= n_rows, validity_stride >= ceil(n_rows / 64)
@@ -39,10 +37,7 @@ def double_of(bits):
 
 def encode(fields):
     """tuples -> the sjmi_arrow_field array: the C form, for the host simulation"""
-    enc = np.zeros(len(fields), dtype=FIELD)
-    for k, field in enumerate(fields):
-        enc[k] = (field[0], KINDS[field[1]], sum(FLAGS[f] for f in field[2:]), 0)
-    return enc
+    return F.encode(fields, FIELD, KINDS, FLAGS)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -73,10 +68,6 @@ def cell(kind, flags, ty, word):
     return data, valid, (not valid) and ty not in (MISSING, NULL), inexact
 
 
-def pack_bits(bits):
-    return [sum(1 << t for t, b in enumerate(bits[w:w + 64]) if b) for w in range(0, len(bits), 64)]
-
-
 def reference_cells(fields, get, live):
     """get(column, row) -> (type byte, value word or anything for a cell that is neither 'l' nor 'd') -> Ref"""
     data, validity, records = [], [], []
@@ -90,10 +81,6 @@ def reference_cells(fields, get, live):
     return Ref(live, data, validity, records)
 
 
-def live_rows(case):
-    return case.n_rows if case.row_count is None else min(case.n_rows, case.row_count)
-
-
 def reference(case):
     t, v = case.types.tolist(), case.values.tolist()
     return reference_cells(case.fields, lambda c, r: (t[c][r], v[c][r]), live_rows(case))
@@ -105,45 +92,8 @@ def reference_from_cells(fields, want, live):
     return reference_cells(fields, lambda c, r: want[c][r], live)
 
 
-# ---------------------------------------------------------------------------------------------------------------------
-# buffers and the comparison
-# ---------------------------------------------------------------------------------------------------------------------
 def out_buffers(case, data=True, validity=True):
-    """the output arrays of one call, canaries all over: (data or None, validity or None, results), the blocks FRONT words
-    behind the beginning of their arrays and BACK words in front of their ends"""
-    n_fields = len(case.fields)
-    d = np.full(FRONT + n_fields * case.data_stride + BACK, CANARY_WORD, dtype=np.uint64) if data else None
-    b = np.full(FRONT + n_fields * case.validity_stride + BACK, CANARY_WORD, dtype=np.uint64) if validity else None
-    return d, b, np.full(4 * n_fields, CANARY_WORD, dtype=np.uint64)
-
-
-def _expect(owned, n_fields, stride):
-    want = np.full(FRONT + n_fields * stride + BACK, CANARY_WORD, dtype=np.uint64)
-    for f, words in enumerate(owned):
-        assert len(words) <= stride
-        want[FRONT + f * stride:FRONT + f * stride + len(words)] = np.array(words, dtype=np.uint64)
-    return want
-
-
-def _same(what, block, got, want, stride):
-    got = np.asarray(got).view(np.uint64).reshape(-1)
-    assert got.size == want.size, (what, block, got.size, want.size)
-    if not np.array_equal(got, want):
-        at = int(np.flatnonzero(got != want)[0])
-        where = "in front of the block" if at < FRONT else "behind the block" if at >= want.size - BACK else \
-            "field %d, word %d" % ((at - FRONT) // max(stride, 1), (at - FRONT) % max(stride, 1))
-        raise AssertionError("%s: %s differs first at %s: got %#x, want %#x (%#x: not to be touched)" % (what, block, where, int(got[at]), int(want[at]), CANARY_WORD))
-
-
-def check(what, got_data, got_validity, got_results, case, ref):
-    """got_*: what a call left in out_buffers() (None: called without it), whole arrays with their canaries"""
-    n_fields = len(case.fields)
-    got = np.asarray(got_results).view(np.uint64).reshape(n_fields, 4).tolist()
-    assert [tuple(r) for r in got] == ref.records, (what, got, ref.records)
-    if got_data is not None:
-        _same(what, "data", got_data, _expect(ref.data, n_fields, case.data_stride), case.data_stride)
-    if got_validity is not None:
-        _same(what, "validity", got_validity, _expect(ref.validity, n_fields, case.validity_stride), case.validity_stride)
+    return F.out_buffers(case, RECORD_WORDS, data, validity)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -174,7 +124,7 @@ def columns(rng, n_cols, n_rows, stride, pool=None):
 def make_case(name, fields, t, v, n_rows, row_count=None, slack=0):
     """slack: how far the output strides lie above their minimum (0: the minimum)"""
     return Case(name, list(fields), np.ascontiguousarray(t, dtype=np.uint8), np.ascontiguousarray(v, dtype=np.uint64), n_rows, row_count,
-                n_rows + (7 if slack else 0), (n_rows + 63) // 64 + (2 if slack else 0))
+                *F.strides(n_rows, slack))
 
 
 def one_column(cells, pad=3):
@@ -186,17 +136,6 @@ def one_column(cells, pad=3):
 
 ROW_COUNTS = (0, 1, 63, 64, 65, 127, 128, 1023, 1024, 1025, 2049)
 MIXED_FIELDS = [(0, "int64", "integral_doubles"), (1, "float64"), (2, "bool"), (1, "int64")]
-
-
-def live_counts(n):
-    """what *d_row_count holds, for n_rows = n: absent, 0, 1, n - 1, n, n + 5 (clamped) and a count that ends inside a wave of a
-    middle chunk (of a middle wave, where there is but one chunk)"""
-    inside = 1024 + 64 + 7 if n > 1100 else n // 128 * 64 + 7 if n >= 128 else None
-    out = [None]
-    for rc in (0, 1, n - 1, n, n + 5, inside):
-        if rc is not None and rc >= 0 and rc not in out:
-            out.append(rc)
-    return out
 
 
 def row_count_cases(n):

@@ -8,9 +8,8 @@
 // GPU.  The passes run a SECOND time with the string buffer BEGINNING on a page boundary behind a page that cannot be touched
 // (its first string is at offset 0), and both runs must give the same.  Built by tests/test_host_timecol.py with g++; the
 // stand-alone sanitizer run of tests/host_sim/timecol_asan_main.cpp includes this file.
-#include <vector>
-
 #include "../../simdjson-java_amd/csrc/sj_timecol.h"
+#include "fieldcol_sim.h"
 #include "seq_ballots.h"
 
 // the other edge: memory that BEGINS where a PROT_NONE page ends
@@ -37,11 +36,7 @@ struct GuardedFront {
 
 template <bool WORDS, uint32_t ROWS>
 static void tc_sim_run(const TcPlan& plan, const TcCols& c, const TcOut& o, sj_u64* ws, TcResult* results) {
-    const SeqGroup g;
-    const sj_u64 nchunks = tc_chunks(c.n_rows, c.chunk_rows);
-    for (uint32_t f = 0; f < plan.n_fields; ++f)
-        for (sj_u64 k = 0; k < nchunks; ++k) tc_parse_chunk<WORDS, ROWS>(g, plan, c, k, f, o, ws);
-    for (uint32_t f = 0; f < plan.n_fields; ++f) tc_finish(g, c, f, ws, results);
+    fc_sim_run(plan, c, o, ws, results, tc_parse_chunk<WORDS, ROWS, SeqGroup>, tc_finish<SeqGroup>);
 }
 template <bool WORDS>
 static bool tc_sim_rows(uint32_t chunk_rows, const TcPlan& plan, const TcCols& c, const TcOut& o, sj_u64* ws, TcResult* results) {
@@ -70,39 +65,29 @@ int sim_timecol(const void* fields, uint64_t n_fields, const uint8_t* types, con
                 uint64_t n_rows, uint64_t cells_readable, const uint64_t* row_count, const uint8_t* sb, uint64_t sb_bytes, uint32_t chunk_rows,
                 int words, uint64_t* data, uint64_t data_stride, uint64_t data_words, uint64_t* validity, uint64_t validity_stride,
                 uint64_t validity_words, uint64_t* results) {
-    if (!results || col_stride < n_rows || (n_rows && (!types || !values || !sb))) return -2;
-    if (data ? data_stride < n_rows : data_stride != 0) return -2;
-    if (validity && validity_stride < (n_rows + 63) / 64) return -2;
+    if (!fc_sim_args(types, values, n_cols, col_stride, n_rows, cells_readable, chunk_rows, data, data_stride, validity, validity_stride, results)) return -2;
+    if (n_rows && !sb) return -2;
     TcPlan plan;
     if (tc_plan_compile((const TcField*)fields, n_fields, n_cols, &plan) != 0) return -2;
-    if (cells_readable > n_cols * col_stride) return -2;
-    Guarded gt, gv, gs, gd, gb, gd2, gb2;
+    FcSimCols in;
+    FcSimOut out, out2;
+    Guarded gs;
     GuardedFront gs2;
-    if (!gt.open(cells_readable + 1) || !gv.open(cells_readable * 8 + 8) || !gs.open(sb_bytes + 1) || !gs2.open(sb_bytes + 1) || !gd.open(data_words * 8 + 8) ||
-        !gb.open(validity_words * 8 + 8) || !gd2.open(data_words * 8 + 8) || !gb2.open(validity_words * 8 + 8))
+    if (!in.open(cells_readable) || !gs.open(sb_bytes + 1) || !gs2.open(sb_bytes + 1) || !out.open(data_words, validity_words) || !out2.open(data_words, validity_words))
         return -3;
-    TcCols c = {gt.place(types, cells_readable), (const sj_u64*)gv.place(values, cells_readable * 8), col_stride, n_rows, (const sj_u64*)row_count,
-                gs.place(sb, sb_bytes), chunk_rows};
-    const TcOut o = {data ? (sj_u64*)gd.place(data, data_words * 8) : nullptr, data_stride, validity ? (sj_u64*)gb.place(validity, validity_words * 8) : nullptr,
-                     validity_stride};
-    const TcOut o2 = {data ? (sj_u64*)gd2.place(data, data_words * 8) : nullptr, data_stride, validity ? (sj_u64*)gb2.place(validity, validity_words * 8) : nullptr,
-                      validity_stride};
-    if (!chunk_rows) return -2;
-    const sj_u64 nchunks = tc_chunks(n_rows, chunk_rows);
-    std::vector<sj_u64> ws(n_fields * nchunks + 1, 0xA5A5A5A5A5A5A5A5ull);  // (the scratch is not zero on the device either)
+    TcCols c = {in.place(types, values, cells_readable, col_stride, n_rows, row_count), gs.place(sb, sb_bytes), chunk_rows};
+    out.place(data, data_stride, validity, validity_stride);
+    out2.place(data, data_stride, validity, validity_stride);
+    std::vector<sj_u64> ws(n_fields * tc_chunks(n_rows, chunk_rows) + 1, 0xA5A5A5A5A5A5A5A5ull);  // (the scratch is not zero on the device either)
     std::vector<TcResult> again(n_fields);
-    if (!(words ? tc_sim_rows<true>(chunk_rows, plan, c, o, ws.data(), (TcResult*)results) : tc_sim_rows<false>(chunk_rows, plan, c, o, ws.data(), (TcResult*)results)))
+    if (!(words ? tc_sim_rows<true>(chunk_rows, plan, c, out.o, ws.data(), (TcResult*)results) : tc_sim_rows<false>(chunk_rows, plan, c, out.o, ws.data(), (TcResult*)results)))
         return -2;
     c.strings = gs2.place(sb, sb_bytes);
     ws.assign(ws.size(), 0x5A5A5A5A5A5A5A5Aull);
-    (void)(words ? tc_sim_rows<true>(chunk_rows, plan, c, o2, ws.data(), again.data()) : tc_sim_rows<false>(chunk_rows, plan, c, o2, ws.data(), again.data()));
+    (void)(words ? tc_sim_rows<true>(chunk_rows, plan, c, out2.o, ws.data(), again.data()) : tc_sim_rows<false>(chunk_rows, plan, c, out2.o, ws.data(), again.data()));
     if (memcmp(again.data(), results, n_fields * sizeof(TcResult)) != 0) return -5;
-    if ((data && memcmp(o.data, o2.data, data_words * 8) != 0) || (validity && memcmp(o.validity, o2.validity, validity_words * 8) != 0)) return -5;
-    if (data) memcpy(data, o.data, data_words * 8);
-    if (validity) memcpy(validity, o.validity, validity_words * 8);
-    for (int i = 1; i <= 64; ++i)  // (place() filled what lies in front of a block with 0xA5)
-        if ((data && ((const uint8_t*)o.data)[-i] != 0xA5) || (validity && ((const uint8_t*)o.validity)[-i] != 0xA5)) return -4;
-    return 0;
+    if ((data && memcmp(out.o.data, out2.o.data, data_words * 8) != 0) || (validity && memcmp(out.o.validity, out2.o.validity, validity_words * 8) != 0)) return -5;
+    return out.copy_back(data, validity) ? 0 : -4;
 }
 
 }  // extern "C"

@@ -20,7 +20,7 @@ SCHEDULES = ((0, 0), (1, 0), (2, 1), (0, 1))  # (order of the chunks, stale load
 
 def load_sim():
     """tests/host_sim/dictcol_sim.cpp (tests/host_sim_lib.py builds it) with its signatures"""
-    lib = host_sim_lib.load("dictcol", ("sj_dictcol.h", "sj_strcol.h"))
+    lib = host_sim_lib.load("dictcol", ("sj_dictcol.h", "sj_strcol.h", "sj_fieldcol.h"))
     lib.sim_dictcol.restype = C.c_int
     lib.sim_dictcol.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
                                 C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]

@@ -11,6 +11,7 @@ import datetime
 import numpy as np
 import pytest
 
+from tests import fieldcol_common as F
 from tests import host_sim_lib
 from tests import timecol_common as TC
 
@@ -20,7 +21,7 @@ FORMS = ((True, True), (True, False), (False, True), (False, False))  # both blo
 
 def load_sim():
     """tests/host_sim/timecol_sim.cpp (tests/host_sim_lib.py builds it) with its signatures"""
-    lib = host_sim_lib.load("timecol", ("sj_timecol.h",))
+    lib = host_sim_lib.load("timecol", ("sj_timecol.h", "sj_fieldcol.h"))
     lib.sim_timecol.restype = C.c_int
     lib.sim_timecol.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p,
                                 C.c_uint64, C.c_uint32, C.c_int, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]
@@ -43,26 +44,8 @@ def reference(case):
     return _REFERENCES[case.name]
 
 
-def run_sim(lib, case, chunk, data=True, validity=True, type_shift=0, words=1, expect=0, fields=None, **over):
-    n_cols, stride = case.types.shape
-    store = np.zeros(n_cols * stride + 16, dtype=np.uint8)  # the type columns at an odd address: a slice of a larger array
-    t = store[type_shift:type_shift + n_cols * stride]
-    t[:] = case.types.reshape(-1)
-    values = np.ascontiguousarray(case.values, dtype=np.uint64)
-    sb = np.ascontiguousarray(case.sb, dtype=np.uint8)
-    enc = TC.encode(case.fields) if fields is None else fields
-    d, b, res = TC.out_buffers(case, data, validity)
-    rc = np.array([0 if case.row_count is None else case.row_count], dtype=np.uint64)
-    args = dict(n_cols=n_cols, col_stride=stride, n_rows=case.n_rows, readable=(n_cols - 1) * stride + TC.live_rows(case),
-                data_stride=case.data_stride if data else 0, validity_stride=case.validity_stride, results=res.ctypes.data, sb=sb.ctypes.data)
-    args.update(over)
-    got = lib.sim_timecol(enc.ctypes.data if len(enc) else None, len(enc), t.ctypes.data, values.ctypes.data, args["n_cols"], args["col_stride"],
-                          args["n_rows"], args["readable"], rc.ctypes.data if case.row_count is not None else None, args["sb"], sb.size, chunk, words,
-                          d[TC.FRONT:].ctypes.data if data else None, args["data_stride"], len(enc) * case.data_stride if data else 0,
-                          b[TC.FRONT:].ctypes.data if validity else None, args["validity_stride"], len(enc) * case.validity_stride if validity else 0,
-                          args["results"])
-    assert got == expect, (case.name, got)
-    return d, b, res
+def run_sim(lib, case, chunk, *how, **over):
+    return F.run_sim(lib.sim_timecol, TC, case, chunk, *how, **over)
 
 
 def check_all(lib, case, chunk, forms=FORMS, shift=1):

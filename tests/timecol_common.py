@@ -2,7 +2,8 @@
 product.  reference() works cell by cell on Python ints: an explicit, state-free test of the RFC 3339 grammar position by
 position, Hinnant's days_from_civil, and exact integer arithmetic for the value, the range and the dropped digits -- no datetime
 in the value path, because datetime has no year 0 (datetime_value() is the cross-check the tests run for years >= 1).  check()
-compares everything a call owns word for word and, against CANARY-filled buffers, everything it must not touch.  The *_case()
+compares everything a call owns word for word and, against CANARY-filled buffers, everything it must not touch (both are
+tests/fieldcol_common.py's, with the live rows and the stride rule of a case).  The *_case()
 generators are seeded -- a name is a case -- and shared by the host simulation's tests (tests/test_host_timecol.py) and the GPU
 tests (tests/test_gpu_timecol.py).  A field is the tuple of binding.time_fields: (column, unit[, "naive_utc"])."""
 import datetime
@@ -10,17 +11,15 @@ from collections import namedtuple
 
 import numpy as np
 
-from tests.arrowcol_common import BACK, CANARY_WORD, FRONT, _expect, _same, pack_bits
+from tests import fieldcol_common as F
+from tests.fieldcol_common import (ALL_TYPES, BACK, CANARY_WORD, DOUBLE, FALSE, FRONT, INT64_MAX, INT64_MIN, LONG, MASK, MISSING, NULL, STRING, TRUE,
+                                   check, live_counts, live_rows, pack_bits)
 from tests.strcol_common import WILD
 
-MISSING, NULL, LONG, DOUBLE, TRUE, FALSE, STRING = 0, ord("n"), ord("l"), ord("d"), ord("t"), ord("f"), ord('"')
-ALL_TYPES = [MISSING] + [ord(c) for c in 'nldtf"[{']
 UNITS = {"s": 0, "ms": 1, "us": 2, "ns": 3}             # SJMI_TIME_<UNIT>
 UNIT_DIGITS = {"s": 0, "ms": 3, "us": 6, "ns": 9}
 FLAGS = {"naive_utc": 1}                                # SJMI_TIME_F_*
 FIELD = np.dtype([("column", "<u4"), ("unit", "<u4"), ("flags", "<u4"), ("reserved", "<u4")])  # sjmi_time_field
-MASK = (1 << 64) - 1
-INT64_MIN, INT64_MAX = -(1 << 63), (1 << 63) - 1
 RECORD_WORDS = 6                                        # n_rows, n_valid, n_other, n_malformed, n_range, n_inexact
 
 # types uint8 / values uint64 [n_cols, col_stride], n_rows <= col_stride; sb: the string buffer (uint8) the '"' cells point into;
@@ -31,10 +30,7 @@ Ref = namedtuple("Ref", "live data validity records")  # data / validity: per fi
 
 def encode(fields):
     """tuples -> the sjmi_time_field array: the C form, for the host simulation"""
-    enc = np.zeros(len(fields), dtype=FIELD)
-    for k, field in enumerate(fields):
-        enc[k] = (field[0], UNITS[field[1]], sum(FLAGS[f] for f in field[2:]), 0)
-    return enc
+    return F.encode(fields, FIELD, UNITS, FLAGS)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -152,10 +148,6 @@ def datetime_value(b, unit):
     return secs * 10 ** k + int((fraction + "0" * 9)[:k] or "0")
 
 
-def live_rows(case):
-    return case.n_rows if case.row_count is None else min(case.n_rows, case.row_count)
-
-
 def reference_cells(fields, get, live, sb):
     """get(column, row) -> (type byte, value word or anything for a cell that is no string) -> Ref"""
     sb = bytes(np.asarray(sb, dtype=np.uint8).tobytes())
@@ -193,27 +185,8 @@ def reference(case):
     return reference_cells(case.fields, lambda c, r: (t[c][r], v[c][r]), live_rows(case), case.sb)
 
 
-# ---------------------------------------------------------------------------------------------------------------------
-# buffers and the comparison
-# ---------------------------------------------------------------------------------------------------------------------
 def out_buffers(case, data=True, validity=True):
-    """the output arrays of one call, canaries all over: (data or None, validity or None, results), the blocks FRONT words
-    behind the beginning of their arrays and BACK words in front of their ends"""
-    n_fields = len(case.fields)
-    d = np.full(FRONT + n_fields * case.data_stride + BACK, CANARY_WORD, dtype=np.uint64) if data else None
-    b = np.full(FRONT + n_fields * case.validity_stride + BACK, CANARY_WORD, dtype=np.uint64) if validity else None
-    return d, b, np.full(RECORD_WORDS * n_fields, CANARY_WORD, dtype=np.uint64)
-
-
-def check(what, got_data, got_validity, got_results, case, ref):
-    """got_*: what a call left in out_buffers() (None: called without it), whole arrays with their canaries"""
-    n_fields = len(case.fields)
-    got = np.asarray(got_results).view(np.uint64).reshape(n_fields, RECORD_WORDS).tolist()
-    assert [tuple(r) for r in got] == ref.records, (what, got, ref.records)
-    if got_data is not None:
-        _same(what, "data", got_data, _expect(ref.data, n_fields, case.data_stride), case.data_stride)
-    if got_validity is not None:
-        _same(what, "validity", got_validity, _expect(ref.validity, n_fields, case.validity_stride), case.validity_stride)
+    return F.out_buffers(case, RECORD_WORDS, data, validity)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -250,7 +223,7 @@ def make_case(name, fields, columns, n_rows=None, row_count=None, slack=0, pad=3
         for r in range(len(col), n):
             t[c, r], v[c, r] = MISSING, WILD[r % len(WILD)]
     sb = np.frombuffer(b"".join(parts) or b"\x00", dtype=np.uint8).copy()
-    return Case(name, list(fields), t, v, sb, n, row_count, n + (7 if slack else 0), (n + 63) // 64 + (2 if slack else 0))
+    return Case(name, list(fields), t, v, sb, n, row_count, *F.strides(n, slack))
 
 
 EVERY_FIELD = [(0, unit) + flag for unit in ("s", "ms", "us", "ns") for flag in ((), ("naive_utc",))]
@@ -375,23 +348,12 @@ ROW_COUNTS = (0, 1, 63, 64, 65, 127, 128, 255, 256, 257, 1023, 1024, 1025, 2049)
 MIXED_FIELDS = [(0, "us"), (1, "ns", "naive_utc"), (2, "s"), (1, "ms")]
 
 
-def live_counts(n):
-    """what *d_row_count holds, for n_rows = n: absent, 0, 1, n - 1, n, n + 5 (clamped) and a count that ends inside a wave of a
-    middle chunk (of a middle wave, where there is but one chunk)"""
-    inside = 1024 + 64 + 7 if n > 1100 else n // 128 * 64 + 7 if n >= 128 else None
-    out = [None]
-    for rc in (0, 1, n - 1, n, n + 5, inside):
-        if rc is not None and rc >= 0 and rc not in out:
-            out.append(rc)
-    return out
-
-
 def row_count_cases(n):
     rng = np.random.default_rng(1000 + n)
     columns = [random_cells(rng, n) for _ in range(3)]
     base = make_case("%d rows" % n, MIXED_FIELDS, columns, n_rows=n, pad=7, rng=rng)
     return [base._replace(name="%d rows, row count %s, strides %s" % (n, rc, "above the minimum" if k % 2 else "at the minimum"), row_count=rc,
-                          data_stride=n + (7 if k % 2 else 0), validity_stride=(n + 63) // 64 + (2 if k % 2 else 0)) for k, rc in enumerate(live_counts(n))]
+                          data_stride=F.strides(n, k % 2)[0], validity_stride=F.strides(n, k % 2)[1]) for k, rc in enumerate(live_counts(n))]
 
 
 def schema_cases():
