@@ -42,6 +42,17 @@ struct PlanSlot {
     uint64_t serial = 0;
 };
 
+// Which bytes something on the context describes -- the block parities in d_blkpar, a batch's acceptance flag: (buf, len) as the
+// launch that made it saw them.  Cleared whenever another launch, or other bytes under the same pointer, take that away.
+struct Described {
+    const void* buf = nullptr;
+    uint64_t len = 0;
+    bool valid = false;
+    bool covers(const void* b, uint64_t n) const { return valid && buf == b && len == n; }
+    void set(const void* b, uint64_t n) { buf = b, len = n, valid = true; }
+    void clear() { valid = false; }
+};
+
 struct sjmi_ctx {
     int device = 0;
     uint64_t capacity = 0;
@@ -68,10 +79,7 @@ struct sjmi_ctx {
     DevBuf<void> d_ws_strm;       // workspace of the streaming string pass (strings.hip)
     DevBuf<void> d_ws_par;        // workspace of a parity-only stage-1 launch (strings of a document this context has not indexed)
     DevBuf<unsigned long long> d_blkpar;  // in-string parity of every 64-byte block, left by the last stage-1 launch
-                                          // ... over (par_buf, par_len): what the string pass starts from
-    const void* par_buf = nullptr;
-    uint64_t par_len = 0;
-    bool par_valid = false;
+    Described par;                        // ... over these bytes: what the string pass starts from
     DevBuf<unsigned long long> d_err_index;  // host forms: position in indexes[] of the first failing string
     // what the cooperative walker takes from the string pass: offset of every record by string ordinal, the ordinal of the
     // first string at or behind every 64-byte block, the ordinal of every document's first string
@@ -104,9 +112,7 @@ struct sjmi_ctx {
     DevBuf<uint32_t> d_blkidx;               // fused batch pipeline: k_stage1's per-block side outputs (stage1.h Stage1Extras)
     DevBuf<uint16_t> d_blkw;
     DevBuf<uint32_t> d_batch_flags;          // the two words of a batch's optimistic plain stage-1 pass ([1] != 0: accepted)
-    const void* accept_buf = nullptr;        // ... which batch they belong to (the string pass of the same batch reads the flag)
-    uint64_t accept_len = 0;
-    bool accept_valid = false;
+    Described accept;                        // ... which batch they belong to (the string pass of the same batch reads the flag)
     DevBuf<unsigned long long> d_tape;       // ... and its tape
     HostBuf<void> h_single;                  // pinned copy of the three result records
     uint64_t last_ndocs = 0;                 // documents of the last batch call (their index offsets are still on the device)
@@ -276,12 +282,10 @@ bool bad_offsets(sjmi_ctx* c, const uint64_t* offs, uint64_t n_docs, uint64_t to
 // Where a plain stage-1 launch over (d_buf, len) leaves its block parities (null: the allocation failed -- the string pass
 // then makes its own).  Shards and the per-document passes of an isolated batch do not record any.
 void* parity_out(sjmi_ctx* c, const void* d_buf, uint64_t len) {
-    c->par_valid = false;
-    c->accept_valid = false;  // (another stage-1 launch: a batch's acceptance flag no longer describes the parities)
+    c->par.clear();
+    c->accept.clear();  // (another stage-1 launch: a batch's acceptance flag no longer describes the parities)
     if (!grow(c, c->d_blkpar, sjmi::strings_parity_words(len) * sizeof(unsigned long long), "hipMalloc(blkpar)")) return nullptr;
-    c->par_buf = d_buf;
-    c->par_len = len;
-    c->par_valid = true;
+    c->par.set(d_buf, len);
     return c->d_blkpar;
 }
 // a stage-1 launch over (d_buf, len) on the workspace c->d_ws_par that writes nothing but what `ex` asks for (no indexes, no
@@ -297,14 +301,22 @@ hipError_t parity_launch(sjmi_ctx* c, const uint8_t* d_buf, uint64_t len, hipStr
 // under the same pointer before the next call (a caching allocator hands the same block out again), and only a stage-1 launch
 // over them describes them (include/sjmi.h, sjmi_unescape_device).
 const unsigned long long* parity_for(sjmi_ctx* c, const void* d_buf, uint64_t len, hipStream_t st) {
-    if (c->par_valid && c->par_buf == d_buf && c->par_len == len) return c->d_blkpar;
+    if (c->par.covers(d_buf, len)) return c->d_blkpar;
     if (!grow(c, c->d_ws_par, sjmi::stage1_workspace_bytes(len, stage1_steps(c, len)), "hipMalloc(ws_par)")) return nullptr;
     sjmi::Stage1Extras ex;
     ex.blkpar = parity_out(c, d_buf, len);
     if (!ex.blkpar) return nullptr;
-    c->par_valid = false;
+    c->par.clear();
     if (fail(c, "parity launch", parity_launch(c, (const uint8_t*)d_buf, len, st, ex))) return nullptr;
     return c->d_blkpar;
+}
+// SJMI_BATCH_OPTIMISTIC=0 switches the plain pass over a whole batch off, SJMI_BATCH_REPAIR=0 the repair stage behind it (read
+// once per process)
+struct BatchSwitches { bool optimistic, repair; };
+const BatchSwitches& batch_switches() {
+    static const BatchSwitches s = {!(getenv("SJMI_BATCH_OPTIMISTIC") && atoi(getenv("SJMI_BATCH_OPTIMISTIC")) == 0),
+                                    !(getenv("SJMI_BATCH_REPAIR") && atoi(getenv("SJMI_BATCH_REPAIR")) == 0)};
+    return s;
 }
 
 }  // namespace
@@ -506,7 +518,7 @@ static int stage1_device_impl(sjmi_ctx* c, const void* d_buf, uint64_t len, void
     ex.zero_bytes = need;
     ex.result_out = fast ? d_result : nullptr;
     ex.blkpar = o.shard_flags ? nullptr : parity_out(c, d_buf, len);
-    if (o.shard_flags) c->par_valid = false;
+    if (o.shard_flags) c->par.clear();
     ex.zero2 = o.zero2;
     ex.zero2_bytes = o.zero2_bytes;
     if (fast) ex.single = o.single;
@@ -644,7 +656,7 @@ static int strings_batch_impl(sjmi_ctx* c, const void* d_buf, uint64_t total_len
     const unsigned long long* par0 = nullptr;
     sjmi::StringsAlt alt;
     if (plain || d_accept) {
-        if (!(c->par_valid && c->par_buf == d_buf && c->par_len == total_len)) {
+        if (!c->par.covers(d_buf, total_len)) {
             c->err = "string pass of a plain batch: the block parities of its stage-1 launch are not on this context";
             return SJMI_ERR_ARG;
         }
@@ -699,8 +711,8 @@ static int unescape_device_impl(sjmi_ctx* c, const void* d_buf, uint64_t len, co
     // a batch: over the batch itself if this context's last stage-1 launch was the plain pass over it, else (documents indexed
     // one by one) over the sanitized copy
     // (indexed by sjmi_stage1_batch_isolated*: whether the plain pass was accepted is a flag on the device)
-    const bool flagged = c->accept_valid && c->accept_buf == d_buf && c->accept_len == len;
-    const bool plain = !flagged && c->par_valid && c->par_buf == d_buf && c->par_len == len;
+    const bool flagged = c->accept.covers(d_buf, len);
+    const bool plain = !flagged && c->par.covers(d_buf, len);
     return strings_batch_impl(c, d_buf, len, d_indexes, count, batch.d_doc_offsets, batch.d_index_offsets, batch.n_docs, plain,
                               flagged ? c->d_batch_flags + 1 : nullptr, d_string_buffer, string_capacity, batch.d_doc_str_offsets,
                               d_result, st);
@@ -1096,8 +1108,8 @@ int sjmi_ndjson_offsets(sjmi_ctx* c, const uint8_t* buf, uint64_t len, uint64_t*
         !grow(c, c->d_nd_result, sizeof(sjmi_ndjson_result), "hipMalloc(ndjson result)"))
         return SJMI_ERR_HIP;
     c->last_valid = false;  // (the context's input buffer no longer holds the document of the last stage-1 call)
-    c->par_valid = false;
-    c->accept_valid = false;
+    c->par.clear();
+    c->accept.clear();
     if (len && fail(c, "H2D", hipMemcpyAsync(c->d_in, buf, len, hipMemcpyHostToDevice, c->stream))) return SJMI_ERR_HIP;
     const int rc = sjmi_ndjson_offsets_device(c, c->d_in, len, cap ? c->d_nd_offsets.p : nullptr, cap, c->d_nd_result, c->stream);
     if (rc != SJMI_OK) return rc;
@@ -1156,8 +1168,8 @@ int sjmi_stage1_masks(sjmi_ctx* c, const uint8_t* buf, uint64_t len, uint64_t* m
     if (!grow(c, c->d_masks, (size_t)nblocks * 48, "hipMalloc(masks)")) return SJMI_ERR_HIP;
     if (len && fail(c, "H2D", hipMemcpyAsync(c->d_in, buf, len, hipMemcpyHostToDevice, c->stream))) return SJMI_ERR_HIP;
     c->last_valid = false;  // (the context's document buffer now holds this document, without indexes)
-    c->par_valid = false;   // (... and without block parities: new bytes under the same pointer)
-    c->accept_valid = false;
+    c->par.clear();   // (... and without block parities: new bytes under the same pointer)
+    c->accept.clear();
     const int rc = sjmi_stage1_masks_device(c, c->d_in, len, c->d_masks, nblocks, c->stream);
     if (rc != SJMI_OK) return rc;
     if (fail(c, "D2H(masks)", hipMemcpyAsync(masks, c->d_masks, (size_t)nblocks * 48, hipMemcpyDeviceToHost, c->stream)) ||
@@ -1234,8 +1246,8 @@ static int stage1_batch_isolated_device_impl(sjmi_ctx* c, const void* d_buf, uin
         // no plain pass in front of these per-document passes (switched off, misaligned buffers, an empty batch): block
         // parities / an acceptance flag recorded for the same pointer and length by an EARLIER launch describe other bytes;
         // the string pass of this batch must take the sanitized copy, not them
-        c->par_valid = false;
-        c->accept_valid = false;
+        c->par.clear();
+        c->accept.clear();
     }
     hipStream_t st = stream_of(c, stream);
     if (fail(c, "isolated batch launch",
@@ -1257,11 +1269,10 @@ static int stage1_batch_optimistic(sjmi_ctx* c, const void* d_buf, uint64_t tota
                                    void* d_result, void* stream, const uint32_t** d_skip_out) {
     if (!c || !d_buf || !d_doc_offsets || !d_indexes || !d_index_offsets || !d_doc_status || !d_result) return SJMI_ERR_ARG;
     if (total_len >= (1ull << 32)) return SJMI_ERR_ARG;
-    static const bool optimistic = !(getenv("SJMI_BATCH_OPTIMISTIC") && atoi(getenv("SJMI_BATCH_OPTIMISTIC")) == 0);
     hipStream_t st0 = stream_of(c, stream);
     const uint32_t* d_skip = nullptr;
-    c->accept_valid = false;
-    if (optimistic && n_docs && total_len && index_capacity >= 1 && !((uintptr_t)d_buf & 15) && !((uintptr_t)d_indexes & 15)) {
+    c->accept.clear();
+    if (batch_switches().optimistic && n_docs && total_len && index_capacity >= 1 && !((uintptr_t)d_buf & 15) && !((uintptr_t)d_indexes & 15)) {
         if (fail(c, "hipSetDevice", hipSetDevice(c->device))) return SJMI_ERR_HIP;
         if (!grow(c, c->d_batch_flags, 64, "hipMalloc(batch flags)")) return SJMI_ERR_HIP;
         if (fail(c, "separator check", sjmi::batch_plain_check_launch((const uint8_t*)d_buf, (const unsigned long long*)d_doc_offsets,
@@ -1288,9 +1299,7 @@ static int stage1_batch_optimistic(sjmi_ctx* c, const void* d_buf, uint64_t tota
                                                      d_index_offsets, d_doc_status, d_result, stream, d_skip);
     if (rc != SJMI_OK) return rc;
     if (d_skip) {  // (set after stage1_device_impl's parity_out, which clears it)
-        c->accept_buf = d_buf;
-        c->accept_len = total_len;
-        c->accept_valid = true;
+        c->accept.set(d_buf, total_len);
     }
     *d_skip_out = d_skip;
     return SJMI_OK;
@@ -1340,263 +1349,302 @@ int sjmi_stage1_batch_isolated(sjmi_ctx* c, const uint8_t* buf, uint64_t total_l
     return SJMI_OK;
 }
 
+// The arguments of sjmi_parse_batch_device* (include/sjmi.h), typed as the launchers take them
+struct BatchCall {
+    const uint8_t* d_buf;
+    uint64_t total_len;
+    const unsigned long long* d_doc_offsets;
+    uint64_t n_docs;
+    uint32_t* d_indexes;
+    uint64_t index_capacity;
+    unsigned long long* d_index_offsets;
+    uint32_t* d_doc_status;
+    uint8_t* d_string_buffer;
+    uint64_t string_capacity;
+    unsigned long long* d_doc_string_offsets;
+    int max_depth;
+    unsigned long long* d_tape;
+    uint64_t tape_capacity;
+    unsigned long long* d_tape_offsets;
+    int32_t* d_doc_errors;
+    sjmi_batch_result* d_result;
+    void* stream;
+    BatchCall(const void* buf, uint64_t len, const void* doc_offsets, uint64_t n, void* indexes, uint64_t index_cap, void* index_offsets,
+              void* doc_status, void* string_buffer, uint64_t string_cap, void* doc_string_offsets, int depth, void* tape, uint64_t tape_cap,
+              void* tape_offsets, void* doc_errors, void* result, void* strm)
+        : d_buf((const uint8_t*)buf), total_len(len), d_doc_offsets((const unsigned long long*)doc_offsets), n_docs(n),
+          d_indexes((uint32_t*)indexes), index_capacity(index_cap), d_index_offsets((unsigned long long*)index_offsets),
+          d_doc_status((uint32_t*)doc_status), d_string_buffer((uint8_t*)string_buffer), string_capacity(string_cap),
+          d_doc_string_offsets((unsigned long long*)doc_string_offsets), max_depth(depth), d_tape((unsigned long long*)tape),
+          tape_capacity(tape_cap), d_tape_offsets((unsigned long long*)tape_offsets), d_doc_errors((int32_t*)doc_errors),
+          d_result((sjmi_batch_result*)result), stream(strm) {}
+    // the three records of d_result as the kernels write them, and the structurals the index array holds besides the sentinel
+    sjmi::Stage1Result* stage1() const { return (sjmi::Stage1Result*)&d_result->stage1; }
+    sjmi::UnescapeResult* strings() const { return (sjmi::UnescapeResult*)&d_result->strings; }
+    sjmi::WalkResult* walk() const { return (sjmi::WalkResult*)&d_result->walk; }
+    uint64_t bound() const { return index_capacity - 1; }
+};
+// the SJMI_ERR_ARG cases of the three entry points: every array is there, a depth, room for the sentinel, 32-bit positions
+static bool batch_call_ok(const sjmi_ctx* c, const BatchCall& b) {
+    return c && b.d_buf && b.d_doc_offsets && b.d_indexes && b.d_index_offsets && b.d_doc_status && b.d_string_buffer &&
+           b.d_doc_string_offsets && b.d_tape && b.d_tape_offsets && b.d_doc_errors && b.d_result && b.max_depth >= 1 &&
+           b.index_capacity >= 1 && b.total_len < (1ull << 32);
+}
+// what the walkers take whichever stage took the batch (made behind the last grow of the context's buffers it names)
+static sjmi::WalkLaunch batch_walk(const sjmi_ctx* c, const BatchCall& b) {
+    sjmi::WalkLaunch w;
+    w.d_buf = b.d_buf;
+    w.d_doc_offsets = b.d_doc_offsets;
+    w.n_docs = b.n_docs;
+    w.d_idx = b.d_indexes;
+    w.count = b.bound();
+    w.d_index_offsets = b.d_index_offsets;
+    w.d_doc_status = b.d_doc_status;
+    w.d_sb = b.d_string_buffer;
+    w.d_doc_str_ordinals = c->d_doc_ord;
+    w.max_depth = b.max_depth;
+    w.d_tape = b.d_tape;
+    w.tape_capacity = b.tape_capacity;
+    w.d_tape_offsets = b.d_tape_offsets;
+    w.d_doc_errors = b.d_doc_errors;
+    w.d_ws = c->d_ws_walk;
+    w.d_res = b.walk();
+    w.dev_count = b.stage1();
+    w.dev_strings = b.strings();
+    w.d_soff = c->d_soff;
+    return w;
+}
+// the two words a batch stage-1 launch keeps in the header of its workspace: [0] reject bits, [1] != 0: accepted
+static uint32_t* batch_flags_of(void* ws) { return reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(ws) + sjmi::WS_BATCH_FLAGS_OFFSET); }
+
 // The fused batch pipeline (round 5: re-ordered so that an ACCEPTED batch costs eight queue entries; round 6: a REPAIR stage
-// between the plain pass and the per-document passes).
-//   stage A   k_stage1_batch   ONE plain launch over the packed batch, per-block side outputs; its workers zero the string pass's
-//                              workspace on their way out, the acceptance flags sit in the header of its own (zeroed) workspace half
+// between the plain pass and the per-document passes).  parse_batch_pipeline decides which stages a call queues
+// and makes each stage's own stage-1 launch; the routines in front of it queue the rest, in this order:
+//   stage A   k_stage1_batch   ONE plain launch over the packed batch (stage1_device_impl: the context's alternating workspace
+//                              halves), per-block side outputs; its workers zero the string pass's workspace on their way out, the
+//                              acceptance flags sit in the header of its own (zeroed) workspace half
+//             batch_plain_stage:
 //             k_strings<true>  over the batch itself, its record inside that workspace (leaves at once behind a stage-1 verdict)
 //             k_doc_prepare    per boundary: the separator check (ORed into flags[0]), index ranges, string ordinals, predicted tape lengths
 //             k_batch_layout   decides: accepted?  zeroes the walk's records, hands the string record over, scans the lengths
 //             k_tape_offsets
 //   stage B   (round 6; every kernel leaves at once when A was accepted)  A batch A rejects -- ONE document in a million fails
 //             stage 1, or the documents are not separated by control characters -- used to fall to stage C, 2.2 x the cost of an
-//             accepted batch.  Now: k_doc_pass<false> gives every document ITS verdict (16 lanes per document, every carry from
-//             zero: StructuralIndexer.java:196-303 per document), the sanitized copy blanks the failing documents, and the SAME
-//             five kernels of stage A run over the copy -- exact there, because every surviving document begins and ends outside a
-//             string whatever separates it from its neighbours; the only thing a missing separator can still do is let a scalar
-//             run on across a boundary, which k_doc_prepare's relaxed rule rules out (else: stage C).  A failing document keeps
-//             its verdict, has no structurals and a two-word tape slot.
-//   stage C   (every kernel leaves at once when A or B was accepted)  the per-document stage-1 passes with their index arrays,
-//             the string pass over the sanitized copy, ordinals, the walk into scratch tapes + packing.
+//             accepted batch.  Now: batch_verdicts (k_doc_pass<false>) gives every document ITS verdict (16 lanes per document,
+//             every carry from zero: StructuralIndexer.java:196-303 per document) and makes the sanitized copy with the failing
+//             documents blank, a stage-1 launch of its own runs over the copy (stage1_launch on c->d_ws_par: a launch that may leave
+//             at once cannot take part in the alternating halves) and batch_plain_stage queues the SAME four kernels behind it --
+//             exact there, because every surviving document begins and ends outside a string whatever separates it from its
+//             neighbours; the only thing a missing separator can still do is let a scalar run on across a boundary, which
+//             k_doc_prepare's relaxed rule rules out (else: stage C).  A failing document keeps its verdict, has no structurals
+//             and a two-word tape slot.
+//   stage C   batch_stage_c (every kernel leaves at once when A or B was accepted)  its own sanitized copy and the copy's
+//             parities, the per-document index arrays, the string pass over the copy, ordinals; the walk is then into scratch
+//             tapes + packing.
 //   k_tok_stream, k_coop_walk (list), k_slow_doubles: ONE set of walkers behind all three (a device flag says where the tapes go).
 // PIPE_OPTIMISTIC: stage A and the walkers, nothing else; a batch that does not qualify comes back with SJMI_ST_REJECTED.
 // PIPE_EXACT: A, B, C.  PIPE_REJECTED: B and the walkers -- the call to make after SJMI_ST_REJECTED; what B cannot take either comes
-// back REJECTED again and is PIPE_EXACT's.  No host round trip inside any of them.
+// back REJECTED again and is PIPE_EXACT's.  No host round trip inside any of them.  A call for which neither A nor B can be tried
+// is batch_three_calls'.
 enum PipeMode { PIPE_OPTIMISTIC, PIPE_EXACT, PIPE_REJECTED };
-static int parse_batch_pipeline(sjmi_ctx* c, const void* d_buf, uint64_t total_len, const void* d_doc_offsets, uint64_t n_docs,
-                                void* d_indexes, uint64_t index_capacity, void* d_index_offsets, void* d_doc_status,
-                                void* d_string_buffer, uint64_t string_capacity, void* d_doc_string_offsets, int max_depth,
-                                void* d_tape, uint64_t tape_capacity, void* d_tape_offsets, void* d_doc_errors, void* d_result,
-                                void* stream, PipeMode mode) {
-    if (!c || !d_buf || !d_doc_offsets || !d_indexes || !d_index_offsets || !d_doc_status || !d_string_buffer ||
-        !d_doc_string_offsets || !d_tape || !d_tape_offsets || !d_doc_errors || !d_result || max_depth < 1 || index_capacity < 1)
-        return SJMI_ERR_ARG;
-    if (total_len >= (1ull << 32)) return SJMI_ERR_ARG;
+
+// Neither the plain pass nor the repair pass can be tried (switched off, misaligned buffers, an empty batch, ...): the
+// per-document passes as the three separate calls would queue them; the optimistic entry says so in the record and queues nothing else
+static int batch_three_calls(sjmi_ctx* c, const BatchCall& b, hipStream_t st, bool optimistic_only) {
+    if (optimistic_only) return fail(c, "reject", sjmi::batch_reject_launch(b.stage1(), st)) ? SJMI_ERR_HIP : SJMI_OK;
+    int rc = stage1_batch_isolated_device_impl(c, b.d_buf, b.total_len, b.d_doc_offsets, b.n_docs, b.d_indexes, b.index_capacity,
+                                               b.d_index_offsets, b.d_doc_status, b.stage1(), b.stream, nullptr);
+    if (rc != SJMI_OK) return rc;
+    rc = strings_batch_impl(c, b.d_buf, b.total_len, b.d_indexes, b.bound(), b.d_doc_offsets, b.d_index_offsets, b.n_docs, false, nullptr,
+                            b.d_string_buffer, b.string_capacity, b.d_doc_string_offsets, b.strings(), st);
+    if (rc != SJMI_OK) return rc;
+    return fail(c, "walk launch", sjmi::walk_launch(batch_walk(c, b), st)) ? SJMI_ERR_HIP : SJMI_OK;
+}
+
+// Stage A (stage 0) and stage B (stage 1) behind their stage-1 launch: the string pass, one pass over the boundaries, the decision
+// and the tape layout.  The parameters are what differs between the two (stage1.h: DocPrepare, BatchLayout): the bytes the stage
+// runs over and their block parities (A: the batch; B: the sanitized copy, with the batch as boundary_buf), the flag words in the
+// header of its stage-1 launch's workspace, B's gate, verdicts and relaxed boundary rule, and the string pass -- A's finds its
+// workspace zeroed by the stage-1 workers and leaves behind a stage-1 verdict, B's zeroes its own and leaves behind an accepted A
+static int batch_plain_stage(sjmi_ctx* c, const BatchCall& b, hipStream_t st, int stage, const uint8_t* buf, const unsigned long long* blkpar,
+                             const uint8_t* boundary_buf, uint32_t* flags, const uint32_t* gate, const uint32_t* status_in, bool relaxed,
+                             bool optimistic_only, uint32_t* pipe_flags, const uint32_t* status_or, bool workspace_is_zero,
+                             const uint32_t* strings_skip) {
+    sjmi::UnescapeResult* const d_u = sjmi::strings_workspace_result(c->d_ws_strm);
+    const sjmi::WalkPrepared wp = sjmi::walk_prepared(c->d_ws_walk, b.bound(), b.n_docs);
+    sjmi::DocPrepare p;
+    p.buf = buf;
+    p.idx = b.d_indexes;
+    p.doc_offsets = b.d_doc_offsets;
+    p.n_docs = b.n_docs;
+    p.total_len = b.total_len;
+    p.blkidx = c->d_blkidx;
+    p.blkw = c->d_blkw;
+    p.blkpar = blkpar;
+    p.blk_ord = c->d_blk_ord;
+    p.soff = c->d_soff;
+    p.strings = d_u;
+    p.stage1 = b.stage1();
+    p.flags = flags;
+    p.index_offsets = b.d_index_offsets;
+    p.doc_status = b.d_doc_status;
+    p.doc_ord = c->d_doc_ord;
+    p.doc_str_offsets = b.d_doc_string_offsets;
+    p.lens = wp.lens;
+    p.chunk_sums = wp.chunk_sums;
+    p.metas = wp.metas;
+    p.gate = gate;
+    p.status_in = status_in;
+    p.boundary_buf = boundary_buf;
+    p.relaxed = relaxed;
+    sjmi::BatchLayout l;
+    l.flags = flags;
+    l.stage1 = b.stage1();
+    l.stage1_out = b.stage1();
+    l.strings_ws = d_u;
+    l.strings_out = b.strings();
+    l.walk = b.walk();
+    l.chunk_sums = wp.chunk_sums;
+    l.n_docs = b.n_docs;
+    l.tape_capacity = b.tape_capacity;
+    l.tape_offsets = b.d_tape_offsets;
+    l.optimistic_only = optimistic_only;
+    l.pipe_flags = pipe_flags;
+    l.stage = stage;
+    l.gate = gate;
+    l.status_or = status_or;
+    if (fail(c, stage ? "repair: strings launch" : "strings launch",
+             sjmi::strings_launch(buf, b.total_len, blkpar, b.d_string_buffer, b.string_capacity, c->d_soff, b.bound() + 64, c->d_blk_ord,
+                                  c->d_ws_strm, d_u, st, nullptr, nullptr, sjmi::StringsAlt(), workspace_is_zero, strings_skip)) ||
+        fail(c, stage ? "repair: prepare launch" : "prepare launch", sjmi::batch_prepare_launch(p, st)) ||
+        fail(c, stage ? "repair: layout launch" : "layout launch",
+             sjmi::batch_layout_launch(l, c->d_ws_walk, b.bound(), wp.lens, wp.metas, b.d_doc_errors, st)))
+        return SJMI_ERR_HIP;
+    return SJMI_OK;
+}
+
+// Every document's own stage-1 verdict (B needs nothing else of the per-document passes; C the rest).  d_copy != nullptr: the
+// same pass makes B's sanitized copy on the way -- the documents' bytes, a failing one blank
+static int batch_verdicts(sjmi_ctx* c, const BatchCall& b, hipStream_t st, const uint32_t* skip, uint8_t* d_copy) {
+    return fail(c, "verdicts launch", sjmi::batch_verdicts_launch(b.d_buf, b.d_doc_offsets, b.n_docs, b.d_doc_status, c->d_doccnt, st,
+                                                                  b.total_len, skip, d_copy))
+               ? SJMI_ERR_HIP
+               : SJMI_OK;
+}
+
+// Stage C, every kernel gated on *skip == 0: its OWN sanitized copy (the whole buffer, failing documents blank, an odd trailing
+// backslash run shortened by one: a batch B does not take may have bytes between its documents and documents that end in a
+// backslash) and the copy's block parities from a parity-only launch; the per-document index arrays, the string pass over the copy
+// (fills the record k_batch_layout zeroed), ordinals
+static int batch_stage_c(sjmi_ctx* c, const BatchCall& b, hipStream_t st, const uint32_t* skip) {
+    sjmi::Stage1Extras ex;
+    ex.blkpar = c->d_blkpar2;
+    ex.skip = skip;
+    if (fail(c, "sanitize", sjmi::strings_sanitize_launch(b.d_buf, b.total_len, b.d_doc_offsets, nullptr, b.n_docs, c->d_copy, skip, st,
+                                                          b.d_doc_status)) ||
+        fail(c, "parity launch", parity_launch(c, c->d_copy, b.total_len, st, ex)) ||
+        fail(c, "indexes launch", sjmi::batch_indexes_launch(b.d_buf, b.d_doc_offsets, b.n_docs, b.d_indexes, b.index_capacity,
+                                                             b.d_index_offsets, b.d_doc_status, c->d_doccnt, b.stage1(), st, b.total_len, skip)) ||
+        fail(c, "strings launch",
+             sjmi::strings_launch(c->d_copy, b.total_len, c->d_blkpar2, b.d_string_buffer, b.string_capacity, c->d_soff, b.bound() + 64,
+                                  c->d_blk_ord, c->d_ws_strm, b.strings(), st, nullptr, nullptr, sjmi::StringsAlt(), false, skip)) ||
+        fail(c, "doc ordinals",
+             sjmi::strings_doc_ordinals_launch(c->d_copy, c->d_blkpar2, sjmi::StringsAlt(), b.total_len, b.d_doc_offsets, b.n_docs,
+                                               c->d_blk_ord, c->d_soff, b.strings(), c->d_doc_ord, b.d_doc_string_offsets, st, skip)))
+        return SJMI_ERR_HIP;
+    return SJMI_OK;
+}
+
+static int parse_batch_pipeline(sjmi_ctx* c, const BatchCall& b, PipeMode mode) {
+    if (!batch_call_ok(c, b)) return SJMI_ERR_ARG;
     if (fail(c, "hipSetDevice", hipSetDevice(c->device))) return SJMI_ERR_HIP;
     const bool optimistic_only = mode == PIPE_OPTIMISTIC;
-    sjmi_batch_result* r = (sjmi_batch_result*)d_result;
-    hipStream_t st = stream_of(c, stream);
-    const uint64_t bound = index_capacity - 1;
-    const uint64_t soff_cap = bound + 64;
-    static const bool optimistic = !(getenv("SJMI_BATCH_OPTIMISTIC") && atoi(getenv("SJMI_BATCH_OPTIMISTIC")) == 0);
-    static const bool repair_on = !(getenv("SJMI_BATCH_REPAIR") && atoi(getenv("SJMI_BATCH_REPAIR")) == 0);
+    hipStream_t st = stream_of(c, b.stream);
     // (a batch of ONE document has no token-walker path behind tapes laid out in advance -- walk_launch takes the cooperative
     //  walker for it -- so the optimistic entry rejects it like any other batch it cannot take; the exact entry serves it)
-    const bool aligned = optimistic && n_docs && total_len && !((uintptr_t)d_buf & 15) && !((uintptr_t)d_indexes & 15);
-    const bool try_plain = aligned && mode != PIPE_REJECTED && !(optimistic_only && n_docs < 2);
+    const bool aligned = batch_switches().optimistic && b.n_docs && b.total_len && !((uintptr_t)b.d_buf & 15) && !((uintptr_t)b.d_indexes & 15);
+    const bool try_plain = aligned && mode != PIPE_REJECTED && !(optimistic_only && b.n_docs < 2);
     // stage B needs the FAST kernel (its scanner writes the caller's record: a SAFE launch's record is copied out behind the
     // kernel whether it ran or not) and more than one document
-    const bool try_repair = aligned && repair_on && !optimistic_only && n_docs > 1 && !(launch_flags(c) & (sjmi::FLAG_SAFE | sjmi::DBG_NO_LOOKBACK));
+    const bool try_repair = aligned && batch_switches().repair && !optimistic_only && b.n_docs > 1 &&
+                            !(launch_flags(c) & (sjmi::FLAG_SAFE | sjmi::DBG_NO_LOOKBACK));
     // PIPE_REJECTED queues the repair stage and the walkers, nothing else: a batch stage B cannot take either (rare: a scalar running
     // on across a boundary without a separator, a document ending in a backslash) comes back with SJMI_ST_REJECTED once more and is
     // the exact call's -- stage C's ~20 queue entries (100 us of kernels that leave at once) stay off the repaired batch's path
     const bool repair_only = mode == PIPE_REJECTED && try_repair;
-    if (!grow(c, c->d_ws_walk, sjmi::walk_workspace_bytes(bound, n_docs), "hipMalloc(ws_walk)")) return SJMI_ERR_HIP;
-    c->accept_valid = false;
-    sjmi::WalkLaunch w;
-    w.d_buf = (const uint8_t*)d_buf;
-    w.d_doc_offsets = (const unsigned long long*)d_doc_offsets;
-    w.n_docs = n_docs;
-    w.d_idx = (const uint32_t*)d_indexes;
-    w.count = bound;
-    w.d_index_offsets = (const unsigned long long*)d_index_offsets;
-    w.d_doc_status = (const uint32_t*)d_doc_status;
-    w.d_sb = (const uint8_t*)d_string_buffer;
-    w.max_depth = max_depth;
-    w.d_tape = (unsigned long long*)d_tape;
-    w.tape_capacity = tape_capacity;
-    w.d_tape_offsets = (unsigned long long*)d_tape_offsets;
-    w.d_doc_errors = (int32_t*)d_doc_errors;
-    w.d_ws = c->d_ws_walk;
-    w.d_res = (sjmi::WalkResult*)&r->walk;
-    w.dev_count = (const sjmi::Stage1Result*)&r->stage1;
-    w.dev_strings = (const sjmi::UnescapeResult*)&r->strings;
-    if (!try_plain && !try_repair) {
-        if (optimistic_only) {  // (nothing the optimistic pipeline could run on: say so in the record)
-            if (fail(c, "reject", sjmi::batch_reject_launch((sjmi::Stage1Result*)&r->stage1, st))) return SJMI_ERR_HIP;
-            return SJMI_OK;
-        }
-        // the per-document passes only (switched off, misaligned buffers, an empty batch), as the three separate calls would
-        int rc = stage1_batch_isolated_device_impl(c, d_buf, total_len, d_doc_offsets, n_docs, d_indexes, index_capacity, d_index_offsets,
-                                                   d_doc_status, &r->stage1, stream, nullptr);
-        if (rc != SJMI_OK) return rc;
-        rc = strings_batch_impl(c, d_buf, total_len, d_indexes, bound, d_doc_offsets, d_index_offsets, n_docs, false, nullptr, d_string_buffer,
-                                string_capacity, d_doc_string_offsets, &r->strings, st);
-        if (rc != SJMI_OK) return rc;
-        w.d_doc_str_ordinals = c->d_doc_ord;
-        w.d_soff = c->d_soff;
-        return fail(c, "walk launch", sjmi::walk_launch(w, st)) ? SJMI_ERR_HIP : SJMI_OK;
-    }
-    const size_t strm_bytes = (sjmi::strings_workspace_bytes(total_len) + 15) & ~(size_t)15;
-    if (!grow(c, c->d_soff, soff_cap * sizeof(uint32_t), "hipMalloc(soff)") ||
-        !grow(c, c->d_blk_ord, (total_len / 64 + 2) * sizeof(uint32_t), "hipMalloc(blk_ord)") ||
-        !grow(c, c->d_doc_ord, (n_docs + 2) * sizeof(unsigned long long), "hipMalloc(doc_ord)") ||
+    if (!grow(c, c->d_ws_walk, sjmi::walk_workspace_bytes(b.bound(), b.n_docs), "hipMalloc(ws_walk)")) return SJMI_ERR_HIP;
+    c->accept.clear();
+    if (!try_plain && !try_repair) return batch_three_calls(c, b, st, optimistic_only);
+    const size_t strm_bytes = (sjmi::strings_workspace_bytes(b.total_len) + 15) & ~(size_t)15;
+    if (!grow(c, c->d_soff, (b.bound() + 64) * sizeof(uint32_t), "hipMalloc(soff)") ||
+        !grow(c, c->d_blk_ord, (b.total_len / 64 + 2) * sizeof(uint32_t), "hipMalloc(blk_ord)") ||
+        !grow(c, c->d_doc_ord, (b.n_docs + 2) * sizeof(unsigned long long), "hipMalloc(doc_ord)") ||
         !grow(c, c->d_ws_strm, strm_bytes, "hipMalloc(ws_strm)") || !grow(c, c->d_batch_flags, 64, "hipMalloc(batch flags)"))
         return SJMI_ERR_HIP;
     // the pipeline's stage flags: pf[0] != 0 = stage A accepted, pf[1] != 0 = A or B accepted (the tapes are laid out in advance)
     uint32_t* const pf = c->d_batch_flags + 8;
     c->soff_idx = nullptr;
-    sjmi::UnescapeResult* const d_u = sjmi::strings_workspace_result(c->d_ws_strm);
-    const sjmi::WalkPrepared wp = sjmi::walk_prepared(c->d_ws_walk, bound, n_docs);
-    sjmi::DocPrepare pa;
-    pa.idx = (const uint32_t*)d_indexes;
-    pa.doc_offsets = (const unsigned long long*)d_doc_offsets;
-    pa.n_docs = n_docs;
-    pa.total_len = total_len;
-    pa.blk_ord = c->d_blk_ord;
-    pa.soff = c->d_soff;
-    pa.strings = d_u;
-    pa.stage1 = (const sjmi::Stage1Result*)&r->stage1;
-    pa.index_offsets = (unsigned long long*)d_index_offsets;
-    pa.doc_status = (uint32_t*)d_doc_status;
-    pa.doc_ord = c->d_doc_ord;
-    pa.doc_str_offsets = (unsigned long long*)d_doc_string_offsets;
-    pa.lens = wp.lens;
-    pa.chunk_sums = wp.chunk_sums;
-    pa.metas = wp.metas;
-    sjmi::BatchLayout bl = {};
-    bl.stage1 = (const sjmi::Stage1Result*)&r->stage1;
-    bl.stage1_out = (sjmi::Stage1Result*)&r->stage1;
-    bl.strings_ws = d_u;
-    bl.strings_out = (sjmi::UnescapeResult*)&r->strings;
-    bl.walk = (sjmi::WalkResult*)&r->walk;
-    bl.chunk_sums = wp.chunk_sums;
-    bl.n_docs = n_docs;
-    bl.tape_capacity = tape_capacity;
-    bl.tape_offsets = (unsigned long long*)d_tape_offsets;
-    bl.optimistic_only = optimistic_only;
-    bl.pipe_flags = optimistic_only ? nullptr : pf;
     const uint32_t* d_laid_out = nullptr;  // device flag != 0: the tapes are laid out (what the walkers and the packing kernels ask)
+    int rc;
     if (try_plain) {
-        // ---- stage A (1): the plain pass ----
-        int rc0;
+        // ---- stage A: the plain pass over the batch itself, then the rest of the stage ----
         {
             const AutoSafeOff plain_only(c);  // (a tripped liveness bound only rejects the plain pass)
             Stage1Opts o;
             o.side = true;
             o.zero2 = c->d_ws_strm;
             o.zero2_bytes = strm_bytes;
-            rc0 = stage1_device_impl(c, d_buf, total_len, d_indexes, index_capacity, &r->stage1, stream, &o);
+            rc = stage1_device_impl(c, b.d_buf, b.total_len, b.d_indexes, b.index_capacity, b.stage1(), b.stream, &o);
         }
-        if (rc0 != SJMI_OK) return rc0;
-        if (!(c->par_valid && c->par_buf == d_buf && c->par_len == total_len) || !c->ws_dev_last) {
+        if (rc != SJMI_OK) return rc;
+        if (!c->par.covers(b.d_buf, b.total_len) || !c->ws_dev_last) {
             c->err = "batch pipeline: the plain pass left no block parities";
             return SJMI_ERR_HIP;
         }
-        uint32_t* const flags = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(c->ws_dev_last) + sjmi::WS_BATCH_FLAGS_OFFSET);
-        // ---- (2) the string pass over the batch itself (not behind a stage-1 verdict: nothing would use it);
-        //      (3) one pass over the boundaries; (4) the decision and the tape layout ----
-        if (fail(c, "strings launch",
-                 sjmi::strings_launch((const uint8_t*)d_buf, total_len, c->d_blkpar, (uint8_t*)d_string_buffer, string_capacity, c->d_soff,
-                                      soff_cap, c->d_blk_ord, c->d_ws_strm, d_u, st, nullptr, nullptr, sjmi::StringsAlt(), true,
-                                      &r->stage1.status)))
-            return SJMI_ERR_HIP;
-        pa.buf = (const uint8_t*)d_buf;
-        pa.blkidx = c->d_blkidx;
-        pa.blkw = c->d_blkw;
-        pa.blkpar = c->d_blkpar;
-        pa.flags = flags;
-        bl.flags = flags;
-        bl.stage = 0;
-        if (fail(c, "prepare launch", sjmi::batch_prepare_launch(pa, st)) ||
-            fail(c, "layout launch", sjmi::batch_layout_launch(bl, c->d_ws_walk, bound, wp.lens, wp.metas, (int32_t*)d_doc_errors, st)))
-            return SJMI_ERR_HIP;
+        uint32_t* const flags = batch_flags_of(c->ws_dev_last);
+        // (the string pass leaves behind a stage-1 verdict: nothing would use it)
+        rc = batch_plain_stage(c, b, st, 0, b.d_buf, c->d_blkpar, nullptr, flags, nullptr, nullptr, false, optimistic_only,
+                               optimistic_only ? nullptr : pf, nullptr, true, &b.stage1()->status);
+        if (rc != SJMI_OK) return rc;
         d_laid_out = optimistic_only ? flags + 1 : pf + 1;
     } else if (fail(c, "memset(pipe flags)", hipMemsetAsync(pf, 0, 8, st))) {  // (PIPE_REJECTED: stage A is known to fail)
         return SJMI_ERR_HIP;
     }
     if (!optimistic_only) {
-        const int steps = stage1_steps(c, total_len);
-        if (!grow(c, c->d_doccnt, sjmi::batch_isolated_workspace_bytes(n_docs), "hipMalloc(doccnt)") ||
-            !grow(c, c->d_copy, total_len + 2 * SJMI_PADDING + 64, "hipMalloc(copy)") ||
-            !grow(c, c->d_blkpar2, sjmi::strings_parity_words(total_len) * sizeof(unsigned long long), "hipMalloc(blkpar2)") ||
-            !grow(c, c->d_ws_par, sjmi::stage1_workspace_bytes(total_len, steps), "hipMalloc(ws_par)"))
+        const int steps = stage1_steps(c, b.total_len);
+        if (!grow(c, c->d_doccnt, sjmi::batch_isolated_workspace_bytes(b.n_docs), "hipMalloc(doccnt)") ||
+            !grow(c, c->d_copy, b.total_len + 2 * SJMI_PADDING + 64, "hipMalloc(copy)") ||
+            !grow(c, c->d_blkpar2, sjmi::strings_parity_words(b.total_len) * sizeof(unsigned long long), "hipMalloc(blkpar2)") ||
+            !grow(c, c->d_ws_par, sjmi::stage1_workspace_bytes(b.total_len, steps), "hipMalloc(ws_par)"))
             return SJMI_ERR_HIP;
-        const uint32_t* const skip_b = pf;      // stages B and the verdicts: not behind an accepted A
+        const uint32_t* const skip_b = pf;      // stage B and the verdicts: not behind an accepted A
         const uint32_t* const skip_c = pf + 1;  // stage C: not behind an accepted A or B
-        // ---- every document's own stage-1 verdict (B needs nothing else of the per-document passes; C the rest) ----
-        //      with stage B behind it the same pass makes B's sanitized copy on the way: the documents' bytes, a failing one blank
-        if (fail(c, "verdicts launch", sjmi::batch_verdicts_launch((const uint8_t*)d_buf, (const unsigned long long*)d_doc_offsets, n_docs,
-                                                                   (uint32_t*)d_doc_status, c->d_doccnt, st, total_len, skip_b,
-                                                                   try_repair ? c->d_copy : nullptr)))
-            return SJMI_ERR_HIP;
-        c->par_valid = false;  // (whose parities the context holds is decided on the device from here on)
-        const unsigned long long* copy_par = c->d_blkpar2;  // the copy's block parities
+        if ((rc = batch_verdicts(c, b, st, skip_b, try_repair ? c->d_copy.p : nullptr)) != SJMI_OK) return rc;
+        c->par.clear();  // (whose parities the context holds is decided on the device from here on)
         if (try_repair) {
-            // ---- stage B: the plain pipeline over the copy.  Its stage-1 launch has a workspace of its own (a launch that may
-            //      leave at once cannot take part in the context's two alternating halves) and its string pass a zeroed one ----
-            if (!grow(c, c->d_blkidx, sjmi::stage1_block_entries(total_len) * sizeof(uint32_t), "hipMalloc(blkidx)") ||
-                !grow(c, c->d_blkw, sjmi::stage1_block_entries(total_len) * sizeof(uint16_t), "hipMalloc(blkw)"))
+            // ---- stage B: the plain pass over the copy, on a workspace of its own, then the rest of the stage ----
+            if (!grow(c, c->d_blkidx, sjmi::stage1_block_entries(b.total_len) * sizeof(uint32_t), "hipMalloc(blkidx)") ||
+                !grow(c, c->d_blkw, sjmi::stage1_block_entries(b.total_len) * sizeof(uint16_t), "hipMalloc(blkw)"))
                 return SJMI_ERR_HIP;
             sjmi::Stage1Extras ex;
             ex.blkpar = c->d_blkpar2;
             ex.skip = skip_b;
             ex.blkidx = c->d_blkidx;
             ex.blkw = c->d_blkw;
-            ex.result_out = &r->stage1;
-            if (fail(c, "repair: plain pass", sjmi::stage1_launch(c->d_copy, total_len, (uint32_t*)d_indexes, index_capacity, c->d_ws_par, steps, st,
+            ex.result_out = b.stage1();
+            if (fail(c, "repair: plain pass", sjmi::stage1_launch(c->d_copy, b.total_len, b.d_indexes, b.index_capacity, c->d_ws_par, steps, st,
                                                                   nullptr, nullptr, launch_flags(c), ex)))
                 return SJMI_ERR_HIP;
             note_launch(c, st);
-            uint32_t* const flags_b = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(c->d_ws_par.p) + sjmi::WS_BATCH_FLAGS_OFFSET);
-            if (fail(c, "repair: strings launch",
-                     sjmi::strings_launch(c->d_copy, total_len, c->d_blkpar2, (uint8_t*)d_string_buffer, string_capacity, c->d_soff, soff_cap,
-                                          c->d_blk_ord, c->d_ws_strm, d_u, st, nullptr, nullptr, sjmi::StringsAlt(), false, skip_b)))
-                return SJMI_ERR_HIP;
-            sjmi::DocPrepare pb = pa;
-            pb.buf = c->d_copy;
-            pb.boundary_buf = (const uint8_t*)d_buf;
-            pb.blkidx = c->d_blkidx;
-            pb.blkw = c->d_blkw;
-            pb.blkpar = c->d_blkpar2;
-            pb.flags = flags_b;
-            pb.gate = skip_b;
-            pb.status_in = (const uint32_t*)d_doc_status;
-            pb.relaxed = true;
-            sjmi::BatchLayout lb = bl;
-            lb.flags = flags_b;
-            lb.stage = 1;
-            lb.optimistic_only = repair_only;
-            lb.gate = skip_b;
-            lb.status_or = sjmi::batch_status_or(c->d_doccnt, n_docs);
-            if (fail(c, "repair: prepare launch", sjmi::batch_prepare_launch(pb, st)) ||
-                fail(c, "repair: layout launch", sjmi::batch_layout_launch(lb, c->d_ws_walk, bound, wp.lens, wp.metas, (int32_t*)d_doc_errors, st)))
-                return SJMI_ERR_HIP;
+            rc = batch_plain_stage(c, b, st, 1, c->d_copy, c->d_blkpar2, b.d_buf, batch_flags_of(c->d_ws_par), skip_b, b.d_doc_status, true,
+                                   repair_only, pf, sjmi::batch_status_or(c->d_doccnt, b.n_docs), false, skip_b);
+            if (rc != SJMI_OK) return rc;
             d_laid_out = pf + 1;
         }
-        // ---- stage C, every kernel gated on pf[1] == 0: its OWN sanitized copy (the whole buffer, failing documents blank, an odd
-        //      trailing backslash run shortened by one: a batch B does not take may have bytes between its documents and documents
-        //      that end in a backslash) and the copy's block parities from a parity-only launch ----
-        if (!repair_only) {
-            sjmi::Stage1Extras ex;
-            ex.blkpar = c->d_blkpar2;
-            ex.skip = skip_c;
-            if (fail(c, "sanitize", sjmi::strings_sanitize_launch((const uint8_t*)d_buf, total_len, (const unsigned long long*)d_doc_offsets,
-                                                                  nullptr, n_docs, c->d_copy, skip_c, st, (const uint32_t*)d_doc_status)) ||
-                fail(c, "parity launch", parity_launch(c, c->d_copy, total_len, st, ex)))
-                return SJMI_ERR_HIP;
-        }
-        //      ... the per-document index arrays, the string pass over the copy (fills the record k_batch_layout zeroed), ordinals
-        if (!repair_only &&
-            (fail(c, "indexes launch", sjmi::batch_indexes_launch((const uint8_t*)d_buf, (const unsigned long long*)d_doc_offsets, n_docs,
-                                                                 (uint32_t*)d_indexes, index_capacity, (unsigned long long*)d_index_offsets,
-                                                                 (uint32_t*)d_doc_status, c->d_doccnt, (sjmi::Stage1Result*)&r->stage1, st,
-                                                                 total_len, skip_c)) ||
-            fail(c, "strings launch",
-                 sjmi::strings_launch(c->d_copy, total_len, copy_par, (uint8_t*)d_string_buffer, string_capacity, c->d_soff, soff_cap,
-                                      c->d_blk_ord, c->d_ws_strm, (sjmi::UnescapeResult*)&r->strings, st, nullptr, nullptr, sjmi::StringsAlt(),
-                                      false, skip_c)) ||
-            fail(c, "doc ordinals",
-                 sjmi::strings_doc_ordinals_launch(c->d_copy, copy_par, sjmi::StringsAlt(), total_len,
-                                                   (const unsigned long long*)d_doc_offsets, n_docs, c->d_blk_ord, c->d_soff,
-                                                   (const sjmi::UnescapeResult*)&r->strings, c->d_doc_ord,
-                                                   (unsigned long long*)d_doc_string_offsets, st, skip_c))))
-            return SJMI_ERR_HIP;
+        if (!repair_only && (rc = batch_stage_c(c, b, st, skip_c)) != SJMI_OK) return rc;
     }
-    w.d_doc_str_ordinals = c->d_doc_ord;
-    w.d_soff = c->d_soff;
-    w.d_prepared = d_laid_out;  // (try_plain || try_repair: the layout is done)
-    w.layout_done = true;
+    sjmi::WalkLaunch w = batch_walk(c, b);
+    w.d_prepared = d_laid_out;  // (try_plain || try_repair: a stage laid the tapes out, or will say that it did not)
     w.optimistic_only = optimistic_only || repair_only;
     return fail(c, "walk launch", sjmi::walk_launch(w, st)) ? SJMI_ERR_HIP : SJMI_OK;
 }
@@ -1606,9 +1654,9 @@ int sjmi_parse_batch_device(sjmi_ctx* c, const void* d_buf, uint64_t total_len, 
                             void* d_string_buffer, uint64_t string_capacity, void* d_doc_string_offsets, int max_depth,
                             void* d_tape, uint64_t tape_capacity, void* d_tape_offsets, void* d_doc_errors, void* d_result,
                             void* stream) {
-    return parse_batch_pipeline(c, d_buf, total_len, d_doc_offsets, n_docs, d_indexes, index_capacity, d_index_offsets, d_doc_status,
-                                d_string_buffer, string_capacity, d_doc_string_offsets, max_depth, d_tape, tape_capacity, d_tape_offsets,
-                                d_doc_errors, d_result, stream, PIPE_EXACT);
+    const BatchCall b(d_buf, total_len, d_doc_offsets, n_docs, d_indexes, index_capacity, d_index_offsets, d_doc_status, d_string_buffer,
+                      string_capacity, d_doc_string_offsets, max_depth, d_tape, tape_capacity, d_tape_offsets, d_doc_errors, d_result, stream);
+    return parse_batch_pipeline(c, b, PIPE_EXACT);
 }
 
 int sjmi_parse_batch_device_optimistic(sjmi_ctx* c, const void* d_buf, uint64_t total_len, const void* d_doc_offsets, uint64_t n_docs,
@@ -1616,9 +1664,9 @@ int sjmi_parse_batch_device_optimistic(sjmi_ctx* c, const void* d_buf, uint64_t 
                                        void* d_string_buffer, uint64_t string_capacity, void* d_doc_string_offsets, int max_depth,
                                        void* d_tape, uint64_t tape_capacity, void* d_tape_offsets, void* d_doc_errors, void* d_result,
                                        void* stream) {
-    return parse_batch_pipeline(c, d_buf, total_len, d_doc_offsets, n_docs, d_indexes, index_capacity, d_index_offsets, d_doc_status,
-                                d_string_buffer, string_capacity, d_doc_string_offsets, max_depth, d_tape, tape_capacity, d_tape_offsets,
-                                d_doc_errors, d_result, stream, PIPE_OPTIMISTIC);
+    const BatchCall b(d_buf, total_len, d_doc_offsets, n_docs, d_indexes, index_capacity, d_index_offsets, d_doc_status, d_string_buffer,
+                      string_capacity, d_doc_string_offsets, max_depth, d_tape, tape_capacity, d_tape_offsets, d_doc_errors, d_result, stream);
+    return parse_batch_pipeline(c, b, PIPE_OPTIMISTIC);
 }
 
 int sjmi_parse_batch_device_rejected(sjmi_ctx* c, const void* d_buf, uint64_t total_len, const void* d_doc_offsets, uint64_t n_docs,
@@ -1626,9 +1674,9 @@ int sjmi_parse_batch_device_rejected(sjmi_ctx* c, const void* d_buf, uint64_t to
                                      void* d_string_buffer, uint64_t string_capacity, void* d_doc_string_offsets, int max_depth,
                                      void* d_tape, uint64_t tape_capacity, void* d_tape_offsets, void* d_doc_errors, void* d_result,
                                      void* stream) {
-    return parse_batch_pipeline(c, d_buf, total_len, d_doc_offsets, n_docs, d_indexes, index_capacity, d_index_offsets, d_doc_status,
-                                d_string_buffer, string_capacity, d_doc_string_offsets, max_depth, d_tape, tape_capacity, d_tape_offsets,
-                                d_doc_errors, d_result, stream, PIPE_REJECTED);
+    const BatchCall b(d_buf, total_len, d_doc_offsets, n_docs, d_indexes, index_capacity, d_index_offsets, d_doc_status, d_string_buffer,
+                      string_capacity, d_doc_string_offsets, max_depth, d_tape, tape_capacity, d_tape_offsets, d_doc_errors, d_result, stream);
+    return parse_batch_pipeline(c, b, PIPE_REJECTED);
 }
 
 // (the result records of the three stages come back in one place, sjmi::SingleDocPack, written by the walk's last launch)
@@ -1956,7 +2004,7 @@ int sjmi_stream_push(sjmi_stream* s, const uint8_t* chunk, uint64_t len, int is_
         if (s->parity) s->status |= SJMI_ST_UNCLOSED;  // StructuralIndexer.java:297-299
     }
     *status = s->status;
-    c->par_valid = false;
+    c->par.clear();
     c->last_valid = false;
     return SJMI_OK;
 }

@@ -179,25 +179,25 @@ static_assert(sizeof(DocMeta) == 32, "one s_load_dwordx8");
 // = 0, the ordinal / record offset of its first string, its PREDICTED tape length (exact for a well-formed document) and the
 // DocMeta record without `tape`; chunk_sums[j] = predicted words of documents [256 j, 256 j + 256).
 struct DocPrepare {
-    const uint8_t* buf;
-    const uint32_t* idx;
-    const unsigned long long* doc_offsets;
-    uint64_t n_docs, total_len;
-    const uint32_t* blkidx;
-    const uint16_t* blkw;
-    const unsigned long long* blkpar;
-    const uint32_t* blk_ord;
-    const uint32_t* soff;
-    const UnescapeResult* strings;
-    const Stage1Result* stage1;
-    uint32_t* flags;        // [0]: reject bits -- this kernel adds "a separator is missing / the offsets do not cover the buffer"
-    unsigned long long* index_offsets;
-    uint32_t* doc_status;
-    unsigned long long* doc_ord;
-    unsigned long long* doc_str_offsets;
-    uint32_t* lens;
-    unsigned long long* chunk_sums;
-    DocMeta* metas;
+    const uint8_t* buf = nullptr;
+    const uint32_t* idx = nullptr;
+    const unsigned long long* doc_offsets = nullptr;
+    uint64_t n_docs = 0, total_len = 0;
+    const uint32_t* blkidx = nullptr;
+    const uint16_t* blkw = nullptr;
+    const unsigned long long* blkpar = nullptr;
+    const uint32_t* blk_ord = nullptr;
+    const uint32_t* soff = nullptr;
+    const UnescapeResult* strings = nullptr;
+    const Stage1Result* stage1 = nullptr;
+    uint32_t* flags = nullptr;        // [0]: reject bits -- this kernel adds "a separator is missing / the offsets do not cover the buffer"
+    unsigned long long* index_offsets = nullptr;
+    uint32_t* doc_status = nullptr;
+    unsigned long long* doc_ord = nullptr;
+    unsigned long long* doc_str_offsets = nullptr;
+    uint32_t* lens = nullptr;
+    unsigned long long* chunk_sums = nullptr;
+    DocMeta* metas = nullptr;
     // the REPAIR pass (round 6, sjmi_api.hip parse_batch_pipeline stage B): the same kernel over the sanitized copy of a batch
     // whose plain pass was rejected -- the documents that failed stage 1 (status_in[k] != 0, from the verdict pass
     // k_doc_pass<false>) are blank there, so every surviving document begins and ends outside a string whatever separates them
@@ -216,18 +216,18 @@ hipError_t batch_prepare_launch(const DocPrepare& a, hipStream_t stream);
 // accepted: the scan of the predicted tape lengths (chunk bases, tape_offsets[n_docs], walk.tape_words).  optimistic_only: a
 // rejected batch gets SJMI_ST_REJECTED in the caller's stage-1 record (nothing else is queued for it).
 struct BatchLayout {
-    uint32_t* flags;
-    const Stage1Result* stage1;          // the plain pass's record as the kernel left it
-    Stage1Result* stage1_out;            // the caller's (optimistic_only: |= SJMI_ST_REJECTED)
-    const UnescapeResult* strings_ws;    // the string pass's own record
-    UnescapeResult* strings_out;         // the caller's
-    WalkResult* walk;
-    void* slow_header;                   // 64 bytes
-    uint32_t* list;
-    unsigned long long* chunk_sums;
-    uint64_t n_docs, tape_capacity;
-    unsigned long long* tape_offsets;
-    bool optimistic_only;
+    uint32_t* flags = nullptr;
+    const Stage1Result* stage1 = nullptr;          // the plain pass's record as the kernel left it
+    Stage1Result* stage1_out = nullptr;            // the caller's (optimistic_only: |= SJMI_ST_REJECTED)
+    const UnescapeResult* strings_ws = nullptr;    // the string pass's own record
+    UnescapeResult* strings_out = nullptr;         // the caller's
+    WalkResult* walk = nullptr;
+    void* slow_header = nullptr;                   // 64 bytes
+    uint32_t* list = nullptr;
+    unsigned long long* chunk_sums = nullptr;
+    uint64_t n_docs = 0, tape_capacity = 0;
+    unsigned long long* tape_offsets = nullptr;
+    bool optimistic_only = false;
     // round 6: the pipeline's stage flags (sjmi_api.hip): pipe_flags[0] != 0 = the plain pass over the batch itself was accepted
     // (stage A), pipe_flags[1] != 0 = A or the repair pass over the sanitized copy (stage B) was -- the tapes are laid out
     uint32_t* pipe_flags = nullptr;
@@ -265,14 +265,12 @@ struct WalkLaunch {
     bool index_from_zero = false;
     bool results_zeroed = false;
     SingleDocTail tail;
-    // d_prepared (the fused batch pipeline): device flag, != 0 = batch.hip k_doc_prepare ran (the accepted plain pass) and left
-    // every document's DocMeta / predicted tape length in the walk workspace (walk_prepared): the tapes are laid out before the
-    // walk and written at their final addresses -- there a document that fails keeps its (unused) slot: tape_offsets[k + 1] -
-    // tape_offsets[k] is its PREDICTED length, the words are unspecified, doc_errors[k] says so.
+    // d_prepared (the fused batch pipeline; nullptr: the separate calls): batch_layout_launch ran -- the result record and the list
+    // headers are zeroed, nothing of that is queued again -- and left this device flag: != 0 = the tapes ARE laid out, from the
+    // DocMeta / predicted tape lengths batch.hip k_doc_prepare left in the walk workspace (walk_prepared), and are written at their
+    // final addresses -- there a document that fails keeps its (unused) slot: tape_offsets[k + 1] - tape_offsets[k] is its
+    // PREDICTED length, the words are unspecified, doc_errors[k] says so.  optimistic_only: only the kernels of that path are queued.
     const uint32_t* d_prepared = nullptr;
-    // layout_done: batch_layout_launch ran (the tapes ARE laid out when *d_prepared != 0, the result record and list headers are
-    // zeroed): nothing of that is queued again.  optimistic_only: only the kernels of the accepted path are queued.
-    bool layout_done = false;
     bool optimistic_only = false;
 };
 hipError_t walk_launch(const WalkLaunch& w, hipStream_t stream);

@@ -42,8 +42,8 @@ k_tape_chunk_sums(const uint32_t* __restrict__ tape_lens, const int32_t* __restr
 
 __global__ void __launch_bounds__(1024)
 k_tape_chunk_scan(unsigned long long* __restrict__ chunk_sums, uint64_t nchunks, uint64_t n_docs, uint64_t tape_capacity,
-                  unsigned long long* __restrict__ tape_offsets, WalkResult* res, const uint32_t* __restrict__ gate, uint32_t gate_want) {
-    if (gate && (*gate != 0) != (gate_want != 0)) return;
+                  unsigned long long* __restrict__ tape_offsets, WalkResult* res, const uint32_t* __restrict__ gate) {
+    if (gate && *gate) return;
     __shared__ unsigned long long s_wave[16];
     const unsigned long long carry = block_scan_in_place(chunk_sums, nchunks, s_wave);
     if (threadIdx.x == 0) {
@@ -227,7 +227,7 @@ hipError_t batch_layout_launch(const BatchLayout& a0, void* d_ws, uint64_t count
 
 hipError_t walk_launch(const WalkLaunch& w, hipStream_t stream) {
     if (!w.d_soff) return hipErrorInvalidValue;  // (the record table of the string pass: strings.hip)
-    if (w.optimistic_only && !(w.layout_done && w.d_prepared && w.n_docs > 1)) return hipErrorInvalidValue;
+    if (w.optimistic_only && !(w.d_prepared && w.n_docs > 1)) return hipErrorInvalidValue;
     uint8_t* ws = static_cast<uint8_t*>(w.d_ws);
     unsigned long long* scratch = reinterpret_cast<unsigned long long*>(ws);
     // one document whose index range starts at 0 (only sjmi_parse_document knows that: the walker's slot for document 0 is
@@ -236,7 +236,7 @@ hipError_t walk_launch(const WalkLaunch& w, hipStream_t stream) {
     if (direct) scratch = w.d_tape;
     uint32_t* lens = reinterpret_cast<uint32_t*>(ws + walk_lens_offset(w.count, w.n_docs));
     unsigned long long* sums = reinterpret_cast<unsigned long long*>(ws + walk_sums_offset(w.count, w.n_docs));
-    hipError_t e = (w.results_zeroed || w.layout_done) ? hipSuccess : hipMemsetAsync(w.d_res, 0, sizeof(WalkResult), stream);
+    hipError_t e = (w.results_zeroed || w.d_prepared) ? hipSuccess : hipMemsetAsync(w.d_res, 0, sizeof(WalkResult), stream);
     if (e != hipSuccess) return e;
     const uint64_t nchunks = (w.n_docs + PACK_DOCS - 1) / PACK_DOCS;
     static const bool tokens_off = getenv("SJMI_TOKEN_WALK") && atoi(getenv("SJMI_TOKEN_WALK")) == 0;
@@ -245,17 +245,7 @@ hipError_t walk_launch(const WalkLaunch& w, hipStream_t stream) {
         // ---- a batch: the token walker (coop_walk.hip k_tok_stream) with the exact walker behind it for what it declines ----
         const WalkPrepared wp = walk_prepared(w.d_ws, w.count, w.n_docs);
         uint32_t* list = reinterpret_cast<uint32_t*>(ws + walk_list_offset(w.count, w.n_docs));
-        if (w.d_prepared && !w.layout_done) {
-            // the fused pipeline's accepted plain pass (*d_prepared != 0): batch.hip k_doc_prepare left the predicted lengths, so
-            // the tapes are laid out NOW and the walkers store at the final addresses
-            const uint64_t pchunks = (w.n_docs + PREP_DOCS - 1) / PREP_DOCS;
-            hipLaunchKernelGGL(k_tape_chunk_scan, dim3(1), dim3(1024), 0, stream, wp.chunk_sums, pchunks, w.n_docs, w.tape_capacity,
-                               w.d_tape_offsets, w.d_res, w.d_prepared, 1u);
-            hipLaunchKernelGGL(k_tape_offsets, dim3((unsigned)((w.n_docs + 1 + PREP_DOCS - 1) / PREP_DOCS)), dim3(PREP_DOCS), 0, stream,
-                               (const uint32_t*)wp.lens, (const unsigned long long*)wp.chunk_sums, w.n_docs, w.tape_capacity, w.d_tape_offsets,
-                               wp.metas, list, w.d_prepared, w.d_doc_errors);
-        }
-        if (w.d_prepared) packed_skip = w.d_prepared;
+        packed_skip = w.d_prepared;
         if (!w.optimistic_only)
             hipLaunchKernelGGL(k_doc_meta, dim3((unsigned)((w.n_docs + 1 + 255) / 256)), dim3(256), 0, stream, w.d_doc_offsets, w.d_index_offsets,
                            w.d_doc_status, w.d_doc_str_ordinals, w.n_docs, wp.metas, list, packed_skip, w.d_doc_errors);
@@ -274,7 +264,7 @@ hipError_t walk_launch(const WalkLaunch& w, hipStream_t stream) {
         t.max_depth = w.max_depth;
         t.d_tape = w.d_prepared ? w.d_tape : scratch;
         t.d_scratch = w.optimistic_only ? nullptr : scratch;
-        t.header_zeroed = w.layout_done;
+        t.header_zeroed = w.d_prepared != nullptr;
         t.d_sel = w.d_prepared;
         t.d_tape_lens = w.optimistic_only ? nullptr : lens;  // (read by the passes that pack scratch tapes: none of them behind tapes laid out in advance)
         t.d_doc_errors = w.d_doc_errors;
@@ -302,7 +292,7 @@ hipError_t walk_launch(const WalkLaunch& w, hipStream_t stream) {
                            (const uint32_t*)nullptr);
     }
     hipLaunchKernelGGL(k_tape_chunk_scan, dim3(1), dim3(1024), 0, stream, sums, nchunks, w.n_docs, w.tape_capacity, w.d_tape_offsets, w.d_res,
-                       packed_skip, 0u);
+                       packed_skip);
     if (w.n_docs && !direct)
         hipLaunchKernelGGL(k_tape_compact, dim3((unsigned)nchunks), dim3(1024), 0, stream, scratch, lens, w.d_index_offsets, w.n_docs,
                            sums, w.d_tape, w.tape_capacity, w.d_tape_offsets, packed_skip);

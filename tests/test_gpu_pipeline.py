@@ -127,14 +127,14 @@ def test_capacity_shortfall_is_reported_not_overrun(short):
         ctx.close()
 
 
-def _run_shard(ctx, buf, offs, n, exact=False, want_rejected=None):
+def _run_shard(ctx, buf, offs, n, exact=False, want_rejected=None, rejected=False):
     """exact=False: sjmi_parse_batch_device_optimistic, and check() makes the exact call when the record says SJMI_ST_REJECTED;
-    exact=True: sjmi_parse_batch_device (everything queued)."""
+    exact=True: sjmi_parse_batch_device (everything queued); rejected=True: sjmi_parse_batch_device_rejected."""
     import torch
     from simdjson_java_amd import sharding
     shard = sharding.BatchShard(ctx, buf, offs, torch.device("cuda", 0))
     for _ in range(2):
-        shard.step(torch.cuda.current_stream().cuda_stream, exact=exact)
+        shard.step(torch.cuda.current_stream().cuda_stream, exact=exact, rejected=rejected)
         torch.cuda.synchronize()
     if not exact:
         st1 = int(shard.result.cpu().numpy()[1]) & 0xFFFFFFFF
@@ -691,5 +691,122 @@ def test_pipeline_in_safe_mode_with_a_faked_timeout_and_with_misaligned_buffers(
         assert int(shard3.result.cpu().numpy()[1]) & 0x800
         verify(shard3, "misaligned (check() makes the exact call)")
         assert shard3.rejected_steps == 1
+    finally:
+        ctx.close()
+
+
+_GROW_KINDS = {"accepted": (b"\n", True), "repaired": (b"\n", True), "stage C": (b"", False)}
+_grow_cache = {}
+
+
+def _grow_batch(kind, n):
+    """n documents of one kind, packed, with the oracle's verdicts (made once per kind and size).  accepted: containers, one '\\n'
+    behind each; repaired: the same with five documents that fail stage 1 among them; stage C: those without separators and a
+    scalar directly in front of the last document (test_the_repair_stage_takes_what_it_can_and_only_that's documents)."""
+    if (kind, n) not in _grow_cache:
+        sep = _GROW_KINDS[kind][0]
+        docs = [d for d in _small_docs(random.Random(19), 1500) if d[:1] in (b"{", b"[")][:n]
+        assert len(docs) == n
+        if kind != "accepted":
+            for i, b in enumerate([b'["abc', b'def"]', bytes([0x5B, 0x22, 0xC3, 0x22, 0x5D]), b'["a\x01b"]', b'{"k":"v']):
+                docs[1 + i * (n // 6)] = b
+        if kind == "stage C":
+            docs[-2:] = [b"12", b"[3]"]
+        buf = b"".join(d + sep for d in docs)
+        offs = np.concatenate([[0], np.cumsum([len(d) + len(sep) for d in docs])]).astype(np.uint64)
+        _grow_cache[(kind, n)] = docs, buf, offs, [O.parse(d + sep) for d in docs]
+    return _grow_cache[(kind, n)]
+
+
+@pytest.mark.parametrize("kind", list(_GROW_KINDS))
+@pytest.mark.parametrize("entry", ["optimistic", "exact", "rejected"])
+def test_a_small_batch_then_a_larger_one_on_one_context(entry, kind):
+    """8 documents, then 300 (two chunks of k_doc_prepare) on the SAME context: every buffer the call sizes by its batch -- the
+    walk and string workspaces, the record table, the ordinals, the copy and its parities, the side outputs, the stage-1
+    workspaces -- is grown between two calls, under whatever the first one left.  Through each entry point (the optimistic one
+    goes on to the other two through check() when it says SJMI_ST_REJECTED), a batch the plain pass accepts, one the repair
+    stage takes and one only the per-document passes take: every document against the three separate calls and the oracle."""
+    import simdjson_java_amd as S
+    laid_out = _GROW_KINDS[kind][1]
+    ctx = S.Context(0, 1 << 20)
+    try:
+        for n in (8, 300):
+            docs, buf, offs, wants = _grow_batch(kind, n)
+            c, tape, to, err, strings, io, idx = _run_shard(ctx, buf, offs, n, exact=(entry == "exact"), rejected=(entry == "rejected"),
+                                                            want_rejected=(kind != "accepted") if entry == "optimistic" else None)
+            tapes, want_strings, errors = gpu_walk(ctx, docs, packed=(buf, offs))
+            assert np.array_equal(err, errors), (n, err.tolist(), errors.tolist())
+            assert strings == want_strings, n
+            n_bad = 0
+            for k, (d, want) in enumerate(zip(docs, wants)):
+                got = tape[int(to[k]):int(to[k + 1])]
+                assert int(err[k]) == want.error, (n, k, d[:40], int(err[k]), want.error)
+                if want.error:
+                    n_bad += 1
+                    if 1 <= want.error <= 3:  # (failed stage 1: the slot tells which stage took the batch)
+                        assert io[k + 1] == io[k], (n, k)
+                        assert int(to[k + 1] - to[k]) == (2 if laid_out else 0), (n, k, int(to[k + 1] - to[k]))
+                else:
+                    assert np.array_equal(got, tapes[k]), (n, k)
+                    got_idx = idx[int(io[k]):int(io[k + 1])].astype(np.int64) - int(offs[k])
+                    assert np.array_equal(got_idx, O.stage1(d)[0].astype(np.int64)), (n, k)
+                    assert_tape_equal(got, strings, want, (n, k))
+                    assert O.Parsed(got, strings, 0, 0, 0).to_python() == want.to_python(), (n, k)
+            assert c["failed_documents"] == n_bad == (0 if kind == "accepted" else 5), (n, c, n_bad)
+    finally:
+        ctx.close()
+
+
+def test_what_a_pipeline_call_leaves_for_the_separate_walk():
+    """sjmi_walk_batch_device takes the record table of the last batch string pass on the context, by the index array it
+    belongs to.  A pipeline call on aligned buffers runs its own string passes and leaves NO such table: the separate walk over
+    its indexes is refused (SJMI_ERR_ARG, the text names sjmi_unescape_batch_device).  The pipeline's fallback for misaligned
+    buffers is the three separate calls, string pass included: the separate walk over its indexes is accepted and gives the
+    pipeline's tapes again."""
+    import torch
+    import simdjson_java_amd as S
+    from simdjson_java_amd import sharding
+    docs = _small_docs(random.Random(29), 300) + [b"[1 1]"]
+    buf, offs = _pack(docs)
+    n = len(docs)
+    st = torch.cuda.current_stream().cuda_stream
+    ctx = S.Context(0, 1 << 20)
+
+    def walk_again(shard, count):
+        cap = 2 * count + 2 * n + 8
+        out = [torch.zeros(cap, dtype=torch.int64, device="cuda"), torch.zeros(n + 1, dtype=torch.int64, device="cuda"),
+               torch.zeros(n, dtype=torch.int32, device="cuda"), torch.zeros(4, dtype=torch.int64, device="cuda")]
+        ctx.walk_batch_device(shard.buf.data_ptr(), shard.offs.data_ptr(), n, shard.idx.data_ptr(), count, shard.index_offsets.data_ptr(),
+                              shard.doc_status.data_ptr(), shard.sb.data_ptr(), shard.doc_string_offsets.data_ptr(), 0, shard.max_depth,
+                              out[0].data_ptr(), cap, out[1].data_ptr(), out[2].data_ptr(), out[3].data_ptr(), st)
+        torch.cuda.synchronize()
+        return [t.cpu().numpy() for t in out]
+
+    def pipeline(misaligned):
+        shard = sharding.BatchShard(ctx, buf, offs, torch.device("cuda", 0))
+        if misaligned:
+            moved = torch.zeros(shard.n + 256, dtype=torch.uint8, device="cuda")
+            moved[1:1 + shard.n] = shard.buf[:shard.n]
+            shard.buf = moved[1:]
+        assert (shard.buf.data_ptr() % 16 != 0) == misaligned and shard.idx.data_ptr() % 16 == 0
+        shard.step(st, exact=True)
+        torch.cuda.synchronize()
+        c = shard.check()
+        assert c["failed_documents"] == 1 and c["stage1_status"] == 0, c
+        return shard, c
+
+    try:
+        for misaligned in (False, True, False):
+            shard, c = pipeline(misaligned)
+            if not misaligned:
+                with pytest.raises(S.SjmiError) as e:
+                    walk_again(shard, c["structurals"])
+                assert "(rc=-2)" in str(e.value) and "sjmi_unescape_batch_device" in str(e.value), str(e.value)
+                continue
+            tape, to, err, wres = walk_again(shard, c["structurals"])
+            want_to = shard.tape_offsets.cpu().numpy()
+            assert np.array_equal(to, want_to) and int(wres[0]) == int(to[-1]) == c["tape_words"]
+            assert np.array_equal(err, shard.doc_errors.cpu().numpy()[:n]) and int(wres[2]) == 1 and int(err[n - 1]) > 0
+            assert np.array_equal(tape[:int(to[-1])], shard.tape.cpu().numpy()[:int(to[-1])])
     finally:
         ctx.close()
