@@ -89,28 +89,107 @@ def build(force=False, verbose=False):
 
 _lib = None
 
-EXPORTS = ["sjmi_create", "sjmi_destroy", "sjmi_last_error", "sjmi_version", "sjmi_stage1", "sjmi_stage1_device",
-           "sjmi_selftest", "sjmi_set_tile_steps", "sjmi_set_profiling", "sjmi_kernel_time", "sjmi_debug_set_flags", "sjmi_set_tile_mode",
-           "sjmi_unescape", "sjmi_unescape_device",
-           "sjmi_parser_create", "sjmi_parser_destroy", "sjmi_parser_parse", "sjmi_parser_last_message",
-           "sjmi_stage1_batch", "sjmi_stage1_batch_device", "sjmi_parser_parse_batch",
-           "sjmi_stage1_batch_isolated", "sjmi_stage1_batch_isolated_device", "sjmi_host_register", "sjmi_set_input_staging",
-           "sjmi_host_unregister", "sjmi_stage1_unescape", "sjmi_unescape_batch",
-           "sjmi_unescape_batch_device", "sjmi_walk_batch_device", "sjmi_stage1_masks", "sjmi_stage1_masks_device",
-           "sjmi_parser_root", "sjmi_parser_batch_root", "sjmi_value_type", "sjmi_value_as_long", "sjmi_value_as_double",
-           "sjmi_value_as_boolean", "sjmi_value_as_string", "sjmi_value_get", "sjmi_value_size", "sjmi_value_first",
-           "sjmi_value_next", "sjmi_parse_batch_device", "sjmi_parse_batch_device_optimistic", "sjmi_parse_batch_device_rejected", "sjmi_parse_document",
-           "sjmi_parser_set_gpu_walk", "sjmi_set_auto_safe", "sjmi_stage1_shard_device", "sjmi_stage1_shard_device2",
-           "sjmi_stream_open", "sjmi_stream_push", "sjmi_stream_close", "sjmi_split_open", "sjmi_split_scan", "sjmi_split_resolve", "sjmi_split_close",
-           "sjmi_parser_ondemand_init", "sjmi_od_skip_child", "sjmi_od_get_boolean", "sjmi_od_get_long", "sjmi_od_get_integral", "sjmi_od_get_double", "sjmi_od_get_float", "sjmi_od_get_char",
-           "sjmi_od_get_string", "sjmi_od_get_field_name", "sjmi_od_start_array", "sjmi_od_next_array_element",
-           "sjmi_od_start_object", "sjmi_od_next_object_field", "sjmi_od_move_to_field_value", "sjmi_od_assert_no_more_values",
-           "sjmi_od_depth", "sjmi_od_peek",
-           "sjmi_select_plan_compile", "sjmi_select_plan_destroy", "sjmi_select_batch_device",
-           "sjmi_explode_plan_compile", "sjmi_explode_plan_destroy", "sjmi_explode_batch_device",
-           "sjmi_ndjson_offsets_device", "sjmi_ndjson_offsets", "sjmi_ndjson_tile_bytes", "sjmi_string_column_device",
-           "sjmi_filter_plan_compile", "sjmi_filter_plan_destroy", "sjmi_filter_columns_device", "sjmi_arrow_columns_device",
-           "sjmi_time_columns_device", "sjmi_dictionary_column_device"]
+# The C ABI, one line per function of include/sjmi.h, in the header's order: name -> (result, arguments).  lib() declares all of
+# them on the loaded library, so a Python int always travels at the width the header says; tests/test_abi_exports.py holds the
+# table against the header's prototypes.  P: any pointer (handles, buffers, out-parameters, a hipStream_t); PP: where a handle
+# is returned; S: a C string.
+P, PP, I, U32, U64, S = C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_uint32, C.c_uint64, C.c_char_p
+_PARSE_BATCH = (P, P, U64, P, U64, P, U64, P, P, P, U64, P, I, P, U64, P, P, P, P)
+ABI = {
+    "sjmi_create": (I, (PP, I, U64)),
+    "sjmi_destroy": (None, (P,)),
+    "sjmi_last_error": (S, (P,)),
+    "sjmi_version": (S, ()),
+    "sjmi_stage1": (I, (P, P, U64, P, U64, P, P)),
+    "sjmi_stage1_device": (I, (P, P, U64, P, U64, P, P)),
+    "sjmi_stage1_masks": (I, (P, P, U64, P, U64, P)),
+    "sjmi_stage1_masks_device": (I, (P, P, U64, P, U64, P)),
+    "sjmi_stage1_shard_device": (I, (P, P, U64, U64, I, I, P, U64, P, P)),
+    "sjmi_stage1_shard_device2": (I, (P, P, U64, U64, I, I, I, P, U64, P, P)),
+    "sjmi_stream_open": (I, (P, U64, U64, PP)),
+    "sjmi_stream_push": (I, (P, P, U64, I, P, U64, P, P, P)),
+    "sjmi_stream_close": (None, (P,)),
+    "sjmi_split_open": (I, (P, P, U64, U64, I, I, P, U64, PP)),
+    "sjmi_split_scan": (I, (P, P, P, P)),
+    "sjmi_split_resolve": (I, (P, I, P, P, P, P)),
+    "sjmi_split_close": (None, (P,)),
+    "sjmi_unescape_device": (I, (P, P, U64, P, U64, P, U64, P, P)),
+    "sjmi_unescape": (I, (P, P, U64, P, P, P)),
+    "sjmi_stage1_unescape": (I, (P, P, U64, P, U64, P, P, P, U64, P, P, P)),
+    "sjmi_stage1_batch_device": (I, (P, P, U64, P, U64, P, U64, P, P, P)),
+    "sjmi_stage1_batch": (I, (P, P, U64, P, U64, P, U64, P, P, P)),
+    "sjmi_ndjson_offsets_device": (I, (P, P, U64, P, U64, P, P)),
+    "sjmi_ndjson_offsets": (I, (P, P, U64, P, U64, P, P, P)),
+    "sjmi_ndjson_tile_bytes": (U64, ()),
+    "sjmi_stage1_batch_isolated_device": (I, (P, P, U64, P, U64, P, U64, P, P, P, P)),
+    "sjmi_stage1_batch_isolated": (I, (P, P, U64, P, U64, P, U64, P, P, P, P)),
+    "sjmi_unescape_batch": (I, (P, P, U64, P, P, P, P)),
+    "sjmi_unescape_batch_device": (I, (P, P, U64, P, U64, P, P, U64, P, U64, P, P, P)),
+    "sjmi_walk_batch_device": (I, (P, P, P, U64, P, U64, P, P, P, P, U64, I, P, U64, P, P, P, P)),
+    "sjmi_parse_batch_device": (I, _PARSE_BATCH),
+    "sjmi_parse_batch_device_optimistic": (I, _PARSE_BATCH),
+    "sjmi_parse_batch_device_rejected": (I, _PARSE_BATCH),
+    "sjmi_parse_document": (I, (P, P, U64, I, P, U64, P, P, U64, P, P, P)),
+    "sjmi_parser_create": (I, (PP, I, I, I)),
+    "sjmi_parser_destroy": (None, (P,)),
+    "sjmi_parser_parse": (I, (P, P, U64, P, P, P, P, P)),
+    "sjmi_parser_last_message": (S, (P,)),
+    "sjmi_parser_set_gpu_walk": (I, (P, I)),
+    "sjmi_parser_parse_batch": (I, (P, P, U64, P, U64, P, P, P, P, P)),
+    "sjmi_parser_ondemand_init": (I, (P, P, U64, I)),
+    "sjmi_od_skip_child": (I, (P, I)),
+    "sjmi_od_get_boolean": (I, (P, I, I, P, P)),
+    "sjmi_od_get_long": (I, (P, I, I, P, P)),
+    "sjmi_od_get_integral": (I, (P, I, I, I, P, P)),
+    "sjmi_od_get_double": (I, (P, I, I, P, P)),
+    "sjmi_od_get_float": (I, (P, I, I, P, P)),
+    "sjmi_od_get_char": (I, (P, I, I, P, P)),
+    "sjmi_od_get_string": (I, (P, I, P, P, P)),
+    "sjmi_od_get_field_name": (I, (P, P, P)),
+    "sjmi_od_start_array": (I, (P, I, P)),
+    "sjmi_od_next_array_element": (I, (P, P)),
+    "sjmi_od_start_object": (I, (P, I, P)),
+    "sjmi_od_next_object_field": (I, (P, P)),
+    "sjmi_od_move_to_field_value": (I, (P,)),
+    "sjmi_od_assert_no_more_values": (I, (P,)),
+    "sjmi_od_depth": (I, (P,)),
+    "sjmi_od_peek": (I, (P,)),
+    "sjmi_parser_root": (I, (P, P)),
+    "sjmi_parser_batch_root": (I, (P, U64, P)),
+    "sjmi_value_type": (I, (P, P)),
+    "sjmi_value_as_long": (I, (P, P, P)),
+    "sjmi_value_as_double": (I, (P, P, P)),
+    "sjmi_value_as_boolean": (I, (P, P, P)),
+    "sjmi_value_as_string": (I, (P, P, P, U64, P)),
+    "sjmi_value_get": (I, (P, P, P, U64, P)),
+    "sjmi_value_size": (I, (P, P)),
+    "sjmi_value_first": (I, (P, P, P)),
+    "sjmi_value_next": (I, (P, P, P, P)),
+    "sjmi_select_plan_compile": (I, (P, P, U64, PP)),
+    "sjmi_select_plan_destroy": (None, (P,)),
+    "sjmi_select_batch_device": (I, (P, P, P, P, P, P, U64, P, P, P)),
+    "sjmi_explode_plan_compile": (I, (P, U64, P, P, U64, PP)),
+    "sjmi_explode_plan_destroy": (None, (P,)),
+    "sjmi_explode_batch_device": (I, (P, P, P, P, P, P, U64, P, U64, P, P, P)),
+    "sjmi_string_column_device": (I, (P, P, P, U64, P, P, P, P, U64, P, P)),
+    "sjmi_filter_plan_compile": (I, (P, U64, P, U64, PP)),
+    "sjmi_filter_plan_destroy": (None, (P,)),
+    "sjmi_filter_columns_device": (I, (P, P, P, P, U64, U64, U64, P, P, P, U64, P, P, P, P)),
+    "sjmi_arrow_columns_device": (I, (P, P, U64, P, P, U64, U64, U64, P, P, U64, P, U64, P, P)),
+    "sjmi_time_columns_device": (I, (P, P, U64, P, P, U64, U64, U64, P, P, P, U64, P, U64, P, P)),
+    "sjmi_dictionary_column_device": (I, (P, P, P, U64, P, P, P, P, U64, P, P, P, U64, P, P)),
+    "sjmi_host_register": (I, (P, P, U64)),
+    "sjmi_set_input_staging": (I, (P, P, U64)),
+    "sjmi_host_unregister": (I, (P, P)),
+    "sjmi_selftest": (I, (P, P)),
+    "sjmi_set_tile_steps": (I, (P, I)),
+    "sjmi_set_tile_mode": (I, (P, I)),
+    "sjmi_set_auto_safe": (I, (P, I)),
+    "sjmi_set_profiling": (I, (P, I)),
+    "sjmi_debug_set_flags": (I, (P, U32)),
+    "sjmi_kernel_time": (I, (P, P, P)),
+}
+EXPORTS = list(ABI)
 
 
 # Handles that are still open when the interpreter exits are closed HERE, in an atexit hook -- i.e. while the HIP runtime
@@ -147,155 +226,9 @@ def lib():
             pass
         # (SJMI_LIB: an experiment build of the same sources, tools/build_variant.sh -- A/B measurements only)
         L = C.CDLL(os.environ.get("SJMI_LIB") or _LIB)
-        L.sjmi_create.restype = C.c_int
-        L.sjmi_create.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_uint64]
-        L.sjmi_destroy.restype = None
-        L.sjmi_destroy.argtypes = [C.c_void_p]
-        L.sjmi_last_error.restype = C.c_char_p
-        L.sjmi_last_error.argtypes = [C.c_void_p]
-        L.sjmi_version.restype = C.c_char_p
-        L.sjmi_stage1.restype = C.c_int
-        L.sjmi_stage1.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
-        L.sjmi_stage1_device.restype = C.c_int
-        L.sjmi_stage1_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p,
-                                         C.c_void_p]
-        L.sjmi_selftest.restype = C.c_int
-        L.sjmi_selftest.argtypes = [C.c_void_p, C.c_void_p]
-        L.sjmi_set_tile_steps.restype = C.c_int
-        L.sjmi_set_tile_steps.argtypes = [C.c_void_p, C.c_int]
-        L.sjmi_set_profiling.restype = C.c_int
-        L.sjmi_set_profiling.argtypes = [C.c_void_p, C.c_int]
-        L.sjmi_debug_set_flags.restype = C.c_int
-        L.sjmi_debug_set_flags.argtypes = [C.c_void_p, C.c_uint32]
-        L.sjmi_unescape_batch.restype = C.c_int
-        L.sjmi_unescape_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.sjmi_unescape.restype = C.c_int
-        L.sjmi_unescape.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.sjmi_unescape_device.restype = C.c_int
-        L.sjmi_unescape_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
-                                           C.c_void_p, C.c_void_p]
-        L.sjmi_unescape_batch_device.restype = C.c_int
-        L.sjmi_unescape_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
-                                                 C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.sjmi_walk_batch_device.restype = C.c_int
-        L.sjmi_walk_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p,
-                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_uint64,
-                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.sjmi_parser_create.restype = C.c_int
-        L.sjmi_parser_create.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int]
-        L.sjmi_parser_destroy.restype = None
-        L.sjmi_parser_destroy.argtypes = [C.c_void_p]
-        L.sjmi_parser_parse.restype = C.c_int
-        L.sjmi_parser_parse.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                        C.c_void_p]
-        L.sjmi_parser_last_message.restype = C.c_char_p
-        L.sjmi_parser_last_message.argtypes = [C.c_void_p]
-        L.sjmi_stage1_batch.restype = C.c_int
-        L.sjmi_stage1_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
-                                        C.c_void_p, C.c_void_p, C.c_void_p]
-        L.sjmi_stage1_batch_device.restype = C.c_int
-        L.sjmi_stage1_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p,
-                                               C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.sjmi_stage1_batch_isolated.restype = C.c_int
-        L.sjmi_stage1_batch_isolated.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p,
-                                                 C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.sjmi_stage1_batch_isolated_device.restype = C.c_int
-        L.sjmi_stage1_batch_isolated_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p,
-                                                        C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.sjmi_stage1_unescape.restype = C.c_int
-        L.sjmi_stage1_unescape.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
-                                           C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.sjmi_parser_parse_batch.restype = C.c_int
-        L.sjmi_parser_parse_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
-                                              C.c_void_p, C.c_void_p, C.c_void_p]
-        L.sjmi_stage1_shard_device.restype = C.c_int
-        L.sjmi_stage1_shard_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.c_uint64,
-                                               C.c_void_p, C.c_void_p]
-        L.sjmi_stage1_shard_device2.restype = C.c_int
-        L.sjmi_stage1_shard_device2.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_void_p,
-                                                C.c_uint64, C.c_void_p, C.c_void_p]
-        L.sjmi_set_auto_safe.restype = C.c_int
-        L.sjmi_set_auto_safe.argtypes = [C.c_void_p, C.c_int]
-        L.sjmi_set_tile_mode.restype = C.c_int
-        L.sjmi_set_tile_mode.argtypes = [C.c_void_p, C.c_int]
-        L.sjmi_stage1_masks.restype = C.c_int
-        L.sjmi_stage1_masks.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p]
-        L.sjmi_stage1_masks_device.restype = C.c_int
-        L.sjmi_stage1_masks_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p]
-        for name, extra in (("sjmi_parser_root", [C.c_void_p]), ("sjmi_parser_batch_root", [C.c_uint64, C.c_void_p]),
-                            ("sjmi_value_type", [C.c_void_p]), ("sjmi_value_as_long", [C.c_void_p, C.c_void_p]),
-                            ("sjmi_value_as_double", [C.c_void_p, C.c_void_p]), ("sjmi_value_as_boolean", [C.c_void_p, C.c_void_p]),
-                            ("sjmi_value_as_string", [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
-                            ("sjmi_value_get", [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
-                            ("sjmi_value_size", [C.c_void_p]), ("sjmi_value_first", [C.c_void_p, C.c_void_p]),
-                            ("sjmi_value_next", [C.c_void_p, C.c_void_p, C.c_void_p])):
+        for name, (restype, argtypes) in ABI.items():
             f = getattr(L, name)
-            f.restype = C.c_int
-            f.argtypes = [C.c_void_p] + extra
-        L.sjmi_parser_set_gpu_walk.restype = C.c_int
-        L.sjmi_parser_set_gpu_walk.argtypes = [C.c_void_p, C.c_int]
-        P = C.c_void_p
-        for name, args in (("sjmi_parser_ondemand_init", [P, P, C.c_uint64, C.c_int]), ("sjmi_od_skip_child", [P, C.c_int]),
-                           ("sjmi_od_get_boolean", [P, C.c_int, C.c_int, P, P]), ("sjmi_od_get_long", [P, C.c_int, C.c_int, P, P]),
-                           ("sjmi_od_get_double", [P, C.c_int, C.c_int, P, P]), ("sjmi_od_get_float", [P, C.c_int, C.c_int, P, P]), ("sjmi_od_get_char", [P, C.c_int, C.c_int, P, P]), ("sjmi_od_get_integral", [P, C.c_int, C.c_int, C.c_int, P, P]), ("sjmi_od_get_string", [P, C.c_int, P, P, P]),
-                           ("sjmi_od_get_field_name", [P, P, P]), ("sjmi_od_start_array", [P, C.c_int, P]),
-                           ("sjmi_od_next_array_element", [P, P]), ("sjmi_od_start_object", [P, C.c_int, P]),
-                           ("sjmi_od_next_object_field", [P, P]), ("sjmi_od_move_to_field_value", [P]),
-                           ("sjmi_od_assert_no_more_values", [P]), ("sjmi_od_depth", [P]), ("sjmi_od_peek", [P])):
-            getattr(L, name).restype = C.c_int
-            getattr(L, name).argtypes = args
-        L.sjmi_parse_document.restype = C.c_int
-        L.sjmi_parse_document.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
-                                          C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.sjmi_parse_batch_device.restype = C.c_int
-        L.sjmi_parse_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
-                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_int, C.c_void_p,
-                                              C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.sjmi_parse_batch_device_optimistic.restype = C.c_int
-        L.sjmi_parse_batch_device_optimistic.argtypes = L.sjmi_parse_batch_device.argtypes
-        L.sjmi_parse_batch_device_rejected.restype = C.c_int
-        L.sjmi_parse_batch_device_rejected.argtypes = L.sjmi_parse_batch_device.argtypes
-        L.sjmi_kernel_time.restype = C.c_int
-        L.sjmi_kernel_time.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-        L.sjmi_select_plan_compile.restype = C.c_int
-        L.sjmi_select_plan_compile.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p)]
-        L.sjmi_select_plan_destroy.restype = None
-        L.sjmi_select_plan_destroy.argtypes = [C.c_void_p]
-        L.sjmi_explode_plan_compile.restype = C.c_int
-        L.sjmi_explode_plan_compile.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p)]
-        L.sjmi_explode_plan_destroy.restype = None
-        L.sjmi_explode_plan_destroy.argtypes = [C.c_void_p]
-        L.sjmi_explode_batch_device.restype = C.c_int
-        L.sjmi_explode_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
-                                                C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.sjmi_ndjson_offsets_device.restype = C.c_int
-        L.sjmi_ndjson_offsets_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
-        L.sjmi_ndjson_offsets.restype = C.c_int
-        L.sjmi_ndjson_offsets.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.sjmi_ndjson_tile_bytes.restype = C.c_uint64
-        L.sjmi_ndjson_tile_bytes.argtypes = []
-        L.sjmi_string_column_device.restype = C.c_int
-        L.sjmi_string_column_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
-                                                C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
-        L.sjmi_filter_plan_compile.restype = C.c_int
-        L.sjmi_filter_plan_compile.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p)]
-        L.sjmi_filter_plan_destroy.restype = None
-        L.sjmi_filter_plan_destroy.argtypes = [C.c_void_p]
-        L.sjmi_filter_columns_device.restype = C.c_int
-        L.sjmi_filter_columns_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p,
-                                                 C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.sjmi_arrow_columns_device.restype = C.c_int
-        L.sjmi_arrow_columns_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64,
-                                                C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
-        L.sjmi_time_columns_device.restype = C.c_int
-        L.sjmi_time_columns_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64,
-                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
-        L.sjmi_dictionary_column_device.restype = C.c_int
-        L.sjmi_dictionary_column_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                                    C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
-        L.sjmi_select_batch_device.restype = C.c_int
-        L.sjmi_select_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
-                                               C.c_void_p, C.c_void_p, C.c_void_p]
+            f.restype, f.argtypes = restype, list(argtypes)
         _lib = L
     return _lib
 
@@ -1079,12 +1012,6 @@ class Stream:
 
     def __init__(self, ctx, max_chunk_bytes, halo_bytes=0):
         L = lib()
-        L.sjmi_stream_open.restype = C.c_int
-        L.sjmi_stream_open.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(C.c_void_p)]
-        L.sjmi_stream_push.restype = C.c_int
-        L.sjmi_stream_push.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.sjmi_stream_close.restype = None
-        L.sjmi_stream_close.argtypes = [C.c_void_p]
         self._ctx, self._max = ctx, int(max_chunk_bytes)
         h = C.c_void_p()
         ctx._check(L.sjmi_stream_open(ctx._h, self._max, halo_bytes, C.byref(h)), "sjmi_stream_open")
@@ -1109,14 +1036,6 @@ class Split:
 
     def __init__(self, ctx, d_shard, length, halo_bytes, halo_from_start, is_last, d_indexes, index_capacity):
         L = lib()
-        L.sjmi_split_open.restype = C.c_int
-        L.sjmi_split_open.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p)]
-        L.sjmi_split_scan.restype = C.c_int
-        L.sjmi_split_scan.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.sjmi_split_resolve.restype = C.c_int
-        L.sjmi_split_resolve.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.sjmi_split_close.restype = None
-        L.sjmi_split_close.argtypes = [C.c_void_p]
         self._ctx = ctx
         h = C.c_void_p()
         ctx._check(L.sjmi_split_open(ctx._h, d_shard, length, halo_bytes, 1 if halo_from_start else 0, 1 if is_last else 0, d_indexes,

@@ -45,6 +45,55 @@ def global_offsets(gathered):
     return torch.cumsum(g, dim=0) - g
 
 
+# stage-1 status bits of a result record, as include/sjmi.h names them
+SJMI_ST_CAPACITY, SJMI_ST_INTERNAL, SJMI_ST_HALO, SJMI_ST_REJECTED = 0x100, 0x200, 0x400, 0x800
+
+
+def _on_gpu(device):
+    """(the CPU tests' stub engines are synchronous and have no streams)"""
+    return str(device) != "cpu"
+
+
+def _upload(data, device, pad):
+    """bytes or a uint8 tensor -> a uint8 tensor on `device`: the data, then `pad` zero bytes"""
+    import torch
+    if not hasattr(data, "numel"):
+        return torch.frombuffer(bytearray(data) + bytearray(pad), dtype=torch.uint8).to(device)
+    buf = torch.zeros(int(data.numel()) + pad, dtype=torch.uint8, device=device)
+    buf[:int(data.numel())] = data
+    return buf
+
+
+def _ptr(tensor, entries):
+    """the tensor's pointer, or NULL when it has no entries for the call (an empty tensor's own pointer may be anything)"""
+    return tensor.data_ptr() if entries else 0
+
+
+def _column_pair(types, values):
+    """the 1-D (types uint8, values int64) pair of one column -> n_rows"""
+    import torch
+    assert types.dim() == 1 and values.dim() == 1 and types.numel() == values.numel()
+    assert types.dtype == torch.uint8 and values.dtype == torch.int64 and types.is_contiguous() and values.is_contiguous()
+    return int(types.numel())
+
+
+def _column_set(types, values, n_rows):
+    """the 2-D [n_cols, stride] (types uint8, values int64) pair of a set of columns -> n_cols, stride, n_rows (default: the stride)"""
+    import torch
+    assert types.dim() == 2 and values.dim() == 2 and types.shape == values.shape
+    assert types.dtype == torch.uint8 and values.dtype == torch.int64 and types.is_contiguous() and values.is_contiguous()
+    n_cols, stride = int(types.shape[0]), int(types.shape[1])
+    n_rows = stride if n_rows is None else int(n_rows)
+    assert n_cols >= 1 and 0 <= n_rows <= stride
+    return n_cols, stride, n_rows
+
+
+def _check_row_count(row_count, types):
+    import torch
+    if row_count is not None:
+        assert row_count.dtype == torch.int64 and row_count.numel() == 1 and row_count.device == types.device
+
+
 class BatchShard:
     """One rank's contiguous share of a batch of documents, resident on its device, and everything one step of the
     batched path needs: outputs sized once, then `step()` queues sjmi_parse_batch_device (isolated stage 1 -> string
@@ -65,12 +114,7 @@ class BatchShard:
             self.n_docs = offs.size - 1
         else:
             self.n_docs = int(device_offsets.numel()) - 1
-        if hasattr(shard_bytes, "numel"):
-            self.buf = torch.zeros(self.n + 128, dtype=torch.uint8, device=device)
-            self.buf[:self.n] = shard_bytes
-        else:
-            self.buf = torch.zeros(self.n + 128, dtype=torch.uint8, device=device)
-            self.buf[:self.n] = torch.frombuffer(bytearray(shard_bytes), dtype=torch.uint8).to(device)
+        self.buf = _upload(shard_bytes, device, 128)
         self.offs = torch.from_numpy(offs.view(np.int64).copy()).to(device) if device_offsets is None else device_offsets
         # the defaults cover the worst cases (one structural per byte: "[[[[", one tape word per byte: "[1,1,1"); real
         # JSON has one structural per 5-11 bytes, so a caller that knows its data passes tighter ratios (bench.py) -- a
@@ -89,6 +133,13 @@ class BatchShard:
         self.result = torch.zeros(9, dtype=torch.int64, device=device)  # sjmi_batch_result
         self.max_depth = max_depth
         self._ndocs = torch.tensor([self.n_docs], dtype=torch.int64, device=device)
+        # what check() latches for step() (bench.py resets the first two between its sections)
+        self.rejected_steps, self.format_rejected, self.unrepairable = 0, False, False
+        # the last step's stream, and the select / explode queued behind it, for check() to queue again
+        self._last_stream, self._sel_pending, self._exp_pending = 0, None, None
+        self._sel_plan = self._exp_plan = self._exp_capacity = None  # what sel_* / exp_* are allocated for
+        self._side_stream = None  # sharded_step's, made on first use
+        self.ndjson_consumed, self.ndjson_flags = None, 0  # (from_ndjson)
 
     @classmethod
     def from_ndjson(cls, engine, shard_bytes, device, **kwargs):
@@ -100,17 +151,15 @@ class BatchShard:
         at the end of its file appends one '\\n' first.  kwargs as for the constructor."""
         import torch
         n = int(shard_bytes.numel()) if hasattr(shard_bytes, "numel") else len(shard_bytes)
-        raw = shard_bytes.to(device) if hasattr(shard_bytes, "numel") else \
-            torch.frombuffer(bytearray(shard_bytes) + bytearray(64), dtype=torch.uint8).to(device)
-        if hasattr(shard_bytes, "numel"):
-            raw = torch.cat([raw, torch.zeros(64, dtype=torch.uint8, device=device)])  # (SJMI_PADDING readable bytes)
+        raw = _upload(shard_bytes, device, 64)  # (SJMI_PADDING readable bytes)
         result = torch.zeros(3, dtype=torch.int64, device=device)  # sjmi_ndjson_result
         offs = torch.empty(n // 2 + 1, dtype=torch.int64, device=device)  # (a document is at least one byte and its NL)
-        stream = torch.cuda.current_stream(device).cuda_stream if str(device) != "cpu" else 0
-        if not stream and str(device) != "cpu":
-            torch.cuda.synchronize(device)  # (handle 0 names the engine's own stream: the upload has to be done before it starts)
+        stream = torch.cuda.current_stream(device).cuda_stream if _on_gpu(device) else 0
+        engine_stream = _on_gpu(device) and not stream  # (handle 0 names the engine's own stream, which torch's do not order)
+        if engine_stream:
+            torch.cuda.synchronize(device)  # (the upload has to be done before it starts)
         engine.ndjson_offsets_device(raw.data_ptr(), n, offs.data_ptr(), offs.numel(), result.data_ptr(), stream)
-        if not stream and str(device) != "cpu":
+        if engine_stream:
             torch.cuda.synchronize(device)
         r = result.cpu().numpy()
         n_docs, consumed, flags = int(r[0]), int(r[1]), int(r[2]) & 0xFFFFFFFF
@@ -130,21 +179,22 @@ class BatchShard:
         # REJECTED has no valid counts for the gather).  Rejected although every document passed stage 1 = rejected for its FORMAT
         # (no control-character separators): the next batch will be too, so it goes straight to the call for rejected batches;
         # rejected for a document that fails stage 1: the exact call, which tries the plain pass first.
-        rejected = rejected or (not exact and getattr(self, "format_rejected", False) and not getattr(self, "unrepairable", False))
-        exact = exact or getattr(self, "rejected_steps", 0) > 0
+        rejected = rejected or (not exact and self.format_rejected and not self.unrepairable)
+        exact = exact or self.rejected_steps > 0
+        # (an engine from before an entry point existed makes the exact call in its place)
         if rejected and hasattr(self.engine, "parse_batch_device_rejected"):
-            fn = self.engine.parse_batch_device_rejected
+            call = self.engine.parse_batch_device_rejected
+        elif exact or rejected or not hasattr(self.engine, "parse_batch_device_optimistic"):
+            call = self.engine.parse_batch_device
         else:
-            fn = self.engine.parse_batch_device if exact or rejected or not hasattr(self.engine, "parse_batch_device_optimistic") \
-                else self.engine.parse_batch_device_optimistic
+            call = self.engine.parse_batch_device_optimistic
         self._last_stream = stream
         self._sel_pending = None  # (a select queued behind an earlier step does not belong to this one)
         self._exp_pending = None
-        fn(self.buf.data_ptr(), self.n, self.offs.data_ptr(), self.n_docs, self.idx.data_ptr(),
-                                       self.index_capacity, self.index_offsets.data_ptr(), self.doc_status.data_ptr(),
-                                       self.sb.data_ptr(), self.sb_capacity, self.doc_string_offsets.data_ptr(), self.max_depth,
-                                       self.tape.data_ptr(), self.tape_capacity, self.tape_offsets.data_ptr(),
-                                       self.doc_errors.data_ptr(), self.result.data_ptr(), stream)
+        call(self.buf.data_ptr(), self.n, self.offs.data_ptr(), self.n_docs, self.idx.data_ptr(), self.index_capacity,
+             self.index_offsets.data_ptr(), self.doc_status.data_ptr(), self.sb.data_ptr(), self.sb_capacity,
+             self.doc_string_offsets.data_ptr(), self.max_depth, self.tape.data_ptr(), self.tape_capacity,
+             self.tape_offsets.data_ptr(), self.doc_errors.data_ptr(), self.result.data_ptr(), stream)
 
     def select(self, plan, stream=0):
         """Every path of `plan` (a binding.SelectPlan) on every document of the shard: sjmi_select_batch_device, queued on
@@ -156,7 +206,7 @@ class BatchShard:
         call), it queues this select again behind it, and the columns then belong to that run.  A document that failed
         (doc_errors[k] != 0) is MISSING on every path."""
         import torch
-        if getattr(self, "_sel_plan", None) is not plan:
+        if self._sel_plan is not plan:
             self.sel_types = torch.zeros((plan.n_paths, self.n_docs), dtype=torch.uint8, device=self.device)
             self.sel_values = torch.zeros((plan.n_paths, self.n_docs), dtype=torch.int64, device=self.device)
             self._sel_plan = plan
@@ -175,7 +225,7 @@ class BatchShard:
         a step check() has accepted, and check() queues the explode again behind a step it had to run again."""
         import torch
         row_capacity = int(row_capacity)
-        if getattr(self, "_exp_plan", None) is not plan or getattr(self, "_exp_capacity", None) != row_capacity:
+        if self._exp_plan is not plan or self._exp_capacity != row_capacity:
             self.exp_row_offsets = torch.zeros(self.n_docs + 1, dtype=torch.int64, device=self.device)
             self.exp_types = torch.zeros((plan.n_paths, row_capacity), dtype=torch.uint8, device=self.device)
             self.exp_values = torch.zeros((plan.n_paths, row_capacity), dtype=torch.int64, device=self.device)
@@ -184,7 +234,7 @@ class BatchShard:
         cells = plan.n_paths * row_capacity
         self.engine.explode_batch_device(plan, self.tape.data_ptr(), self.tape_offsets.data_ptr(), self.doc_errors.data_ptr(),
                                          self.sb.data_ptr(), self.n_docs, self.exp_row_offsets.data_ptr(), row_capacity,
-                                         self.exp_types.data_ptr() if cells else 0, self.exp_values.data_ptr() if cells else 0, stream)
+                                         _ptr(self.exp_types, cells), _ptr(self.exp_values, cells), stream)
         return self.exp_row_offsets, self.exp_types, self.exp_values
 
     def string_column(self, types, values, byte_capacity=None, stream=0):
@@ -199,26 +249,30 @@ class BatchShard:
         Call it on a step that check() has accepted: unlike select() and explode(), it is not queued again behind a step that
         check() had to run again."""
         import torch
-        assert types.dim() == 1 and values.dim() == 1 and types.numel() == values.numel()
-        assert types.dtype == torch.uint8 and values.dtype == torch.int64 and types.is_contiguous() and values.is_contiguous()
-        n_rows = int(types.numel())
+        n_rows = _column_pair(types, values)
         offsets = torch.empty(n_rows + 1, dtype=torch.int64, device=self.device)
         validity = torch.empty((n_rows + 63) // 64, dtype=torch.int64, device=self.device)
         result = torch.empty(4, dtype=torch.int64, device=self.device)  # sjmi_strcol_result (every call writes all of it)
         call = lambda data, capacity: self.engine.string_column_device(
-            types.data_ptr() if n_rows else 0, values.data_ptr() if n_rows else 0, n_rows, self.sb.data_ptr(), offsets.data_ptr(),
-            validity.data_ptr() if n_rows else 0, data.data_ptr() if capacity else 0, capacity, result.data_ptr(), stream)
+            _ptr(types, n_rows), _ptr(values, n_rows), n_rows, self.sb.data_ptr(), offsets.data_ptr(), _ptr(validity, n_rows),
+            _ptr(data, capacity), capacity, result.data_ptr(), stream)
+        return offsets, validity, self._sized_bytes(call, result, 0, byte_capacity), result
+
+    def _sized_bytes(self, call, record, word, byte_capacity):
+        """The byte buffer of string_column() and dictionary_column(), filled by call(data, capacity).  byte_capacity=None: the
+        sizing call (no buffer, capacity 0), record[word] read back behind a synchronisation, the buffer allocated exactly and
+        the second call made -- none for 0 bytes; with a byte_capacity the one call and nothing synchronises."""
+        import torch
         if byte_capacity is None:
             call(None, 0)
-            if str(self.device) != "cpu":
+            if _on_gpu(self.device):
                 torch.cuda.synchronize(self.device)  # (`stream` need not be the one torch's copy is queued on)
-            byte_capacity = int(result.cpu()[0])
+            byte_capacity = int(record.cpu()[word])
             if not byte_capacity:
-                return offsets, validity, torch.empty(0, dtype=torch.uint8, device=self.device), result
-        byte_capacity = int(byte_capacity)
-        data = torch.empty(byte_capacity, dtype=torch.uint8, device=self.device)
-        call(data, byte_capacity)
-        return offsets, validity, data, result
+                return torch.empty(0, dtype=torch.uint8, device=self.device)
+        data = torch.empty(int(byte_capacity), dtype=torch.uint8, device=self.device)
+        call(data, int(byte_capacity))
+        return data
 
     def filter(self, plan, types, values, n_rows=None, out_capacity=None, stream=0):
         """The rows on which every term of `plan` (a binding.FilterPlan) is true, and the columns compacted to them:
@@ -232,22 +286,16 @@ class BatchShard:
         Call it on a step that check() has accepted: like string_column(), it is not queued again behind a step that check() had
         to run again."""
         import torch
-        assert types.dim() == 2 and values.dim() == 2 and types.shape == values.shape
-        assert types.dtype == torch.uint8 and values.dtype == torch.int64 and types.is_contiguous() and values.is_contiguous()
-        n_cols, stride = int(types.shape[0]), int(types.shape[1])
-        n_rows = stride if n_rows is None else int(n_rows)
-        assert n_cols >= 1 and 0 <= n_rows <= stride
+        n_cols, stride, n_rows = _column_set(types, values, n_rows)
         out_capacity = n_rows if out_capacity is None else int(out_capacity)
         rows = torch.empty(out_capacity, dtype=torch.int64, device=self.device)
         out_types = torch.empty((n_cols, out_capacity), dtype=torch.uint8, device=self.device)
         out_values = torch.empty((n_cols, out_capacity), dtype=torch.int64, device=self.device)
         keep = torch.empty((n_rows + 63) // 64, dtype=torch.int64, device=self.device)
         result = torch.empty(2, dtype=torch.int64, device=self.device)  # sjmi_filter_result (every call writes all of it)
-        # (an empty tensor's pointer may be anything: the call gets NULL for what has no entries)
-        self.engine.filter_columns_device(plan, types.data_ptr() if n_rows else 0, values.data_ptr() if n_rows else 0, n_cols, stride, n_rows,
-                                          self.sb.data_ptr(), keep.data_ptr() if n_rows else 0, rows.data_ptr() if out_capacity else 0,
-                                          out_capacity, out_types.data_ptr() if out_capacity else 0,
-                                          out_values.data_ptr() if out_capacity else 0, result.data_ptr(), stream)
+        self.engine.filter_columns_device(plan, _ptr(types, n_rows), _ptr(values, n_rows), n_cols, stride, n_rows, self.sb.data_ptr(),
+                                          _ptr(keep, n_rows), _ptr(rows, out_capacity), out_capacity, _ptr(out_types, out_capacity),
+                                          _ptr(out_values, out_capacity), result.data_ptr(), stream)
         return rows, out_types, out_values, keep, result
 
     def arrow_columns(self, fields, types, values, n_rows=None, row_count=None, stream=0):
@@ -282,21 +330,14 @@ class BatchShard:
         """arrow_columns() and timestamp_columns(): the checks of the tensor pair, the outputs and the call; `strings` is () or
         (the string buffer's pointer,), record_words the width of a field's record"""
         import torch
-        assert types.dim() == 2 and values.dim() == 2 and types.shape == values.shape
-        assert types.dtype == torch.uint8 and values.dtype == torch.int64 and types.is_contiguous() and values.is_contiguous()
-        n_cols, stride = int(types.shape[0]), int(types.shape[1])
-        n_rows = stride if n_rows is None else int(n_rows)
-        assert n_cols >= 1 and 0 <= n_rows <= stride
-        if row_count is not None:
-            assert row_count.dtype == torch.int64 and row_count.numel() == 1 and row_count.device == types.device
+        n_cols, stride, n_rows = _column_set(types, values, n_rows)
+        _check_row_count(row_count, types)
         n_fields, words = len(fields), (n_rows + 63) // 64
         data = torch.empty((n_fields, n_rows), dtype=torch.int64, device=self.device)
         validity = torch.empty((n_fields, words), dtype=torch.int64, device=self.device)
         results = torch.empty((n_fields, record_words), dtype=torch.int64, device=self.device)  # (every call writes all of it)
-        # (an empty tensor's pointer may be anything: the call gets NULL for what has no entries)
-        call(fields, types.data_ptr() if n_rows else 0, values.data_ptr() if n_rows else 0, n_cols, stride, n_rows,
-             row_count.data_ptr() if row_count is not None else 0, *strings, data.data_ptr() if n_rows else 0, n_rows,
-             validity.data_ptr() if n_rows else 0, words, results.data_ptr(), stream)
+        call(fields, _ptr(types, n_rows), _ptr(values, n_rows), n_cols, stride, n_rows, _ptr(row_count, row_count is not None), *strings,
+             _ptr(data, n_rows), n_rows, _ptr(validity, n_rows), words, results.data_ptr(), stream)
         return data, validity, results
 
     def dictionary_column(self, types, values, dict_capacity, byte_capacity=None, row_count=None, stream=0):
@@ -313,34 +354,20 @@ class BatchShard:
         (SJMI_DICT_BYTES_OVERFLOW) says so.  result[5] & 1 (SJMI_DICT_OVERFLOW): more distinct values than dict_capacity; only
         the counts and the validity mean anything then.  Call it on a step that check() has accepted, like string_column()."""
         import torch
-        assert types.dim() == 1 and values.dim() == 1 and types.numel() == values.numel()
-        assert types.dtype == torch.uint8 and values.dtype == torch.int64 and types.is_contiguous() and values.is_contiguous()
-        if row_count is not None:
-            assert row_count.dtype == torch.int64 and row_count.numel() == 1 and row_count.device == types.device
-        n_rows, dict_capacity = int(types.numel()), int(dict_capacity)
+        n_rows = _column_pair(types, values)
+        _check_row_count(row_count, types)
+        dict_capacity = int(dict_capacity)
         indices = torch.empty(n_rows, dtype=torch.int32, device=self.device)
         validity = torch.empty((n_rows + 63) // 64, dtype=torch.int64, device=self.device)
         dict_rows = torch.empty(dict_capacity, dtype=torch.int64, device=self.device)
         dict_offsets = torch.empty(dict_capacity + 1, dtype=torch.int64, device=self.device)
         result = torch.empty(6, dtype=torch.int64, device=self.device)  # sjmi_dict_result (every call writes all of it)
-        # (an empty tensor's pointer may be anything: the call gets NULL for what has no entries -- but d_indices must not be NULL)
-        one = torch.empty(1, dtype=torch.int32, device=self.device)
+        one = torch.empty(1, dtype=torch.int32, device=self.device)  # (d_indices must not be NULL, not even without rows)
         call = lambda data, capacity: self.engine.dictionary_column_device(
-            types.data_ptr() if n_rows else 0, values.data_ptr() if n_rows else 0, n_rows, row_count.data_ptr() if row_count is not None else 0,
-            self.sb.data_ptr(), indices.data_ptr() if n_rows else one.data_ptr(), validity.data_ptr() if n_rows else 0, dict_capacity,
-            dict_rows.data_ptr() if dict_capacity else 0, dict_offsets.data_ptr(), data.data_ptr() if capacity else 0, capacity,
-            result.data_ptr(), stream)
-        if byte_capacity is None:
-            call(None, 0)
-            if str(self.device) != "cpu":
-                torch.cuda.synchronize(self.device)  # (`stream` need not be the one torch's copy is queued on)
-            byte_capacity = int(result.cpu()[4])
-            if not byte_capacity:
-                return indices, validity, dict_rows, dict_offsets, torch.empty(0, dtype=torch.uint8, device=self.device), result
-        byte_capacity = int(byte_capacity)
-        data = torch.empty(byte_capacity, dtype=torch.uint8, device=self.device)
-        call(data, byte_capacity)
-        return indices, validity, dict_rows, dict_offsets, data, result
+            _ptr(types, n_rows), _ptr(values, n_rows), n_rows, _ptr(row_count, row_count is not None), self.sb.data_ptr(),
+            indices.data_ptr() if n_rows else one.data_ptr(), _ptr(validity, n_rows), dict_capacity, _ptr(dict_rows, dict_capacity),
+            dict_offsets.data_ptr(), _ptr(data, capacity), capacity, result.data_ptr(), stream)
+        return indices, validity, dict_rows, dict_offsets, self._sized_bytes(call, result, 4, byte_capacity), result
 
     def counts_tensor(self):
         """The per-shard row of the count gather, on the device, without a host copy:
@@ -349,34 +376,36 @@ class BatchShard:
         r = self.result
         return torch.cat([self._ndocs, r[0:1], r[2:3], r[6:7] + r[7:8]])
 
+    def _record(self):
+        """sjmi_batch_result on the host -> (the 9 words, stage-1 status, string-pass flags, walk flags)"""
+        r = self.result.cpu().numpy()
+        return r, int(r[1]) & 0xFFFFFFFF, int(r[4]) & 0xFFFFFFFF, int(r[8]) & 0xFFFFFFFF
+
     def check(self):
         """Host-side verdict of the last step (synchronise first): raises if a capacity was exceeded."""
-        r = self.result.cpu().numpy()
-        st1, sflags, wflags = int(r[1]) & 0xFFFFFFFF, int(r[4]) & 0xFFFFFFFF, int(r[8]) & 0xFFFFFFFF
-        if st1 & 0x800:  # SJMI_ST_REJECTED: not a batch for the optimistic pipeline -- the exact call, here, off the hot path
+        r, st1, sflags, wflags = self._record()
+        if st1 & SJMI_ST_REJECTED:  # not a batch for the optimistic pipeline -- the exact call, here, off the hot path
             import torch
-            pending = getattr(self, "_sel_pending", None)
-            exp_pending = getattr(self, "_exp_pending", None)
-            self.rejected_steps = getattr(self, "rejected_steps", 0) + 1
+            pending, exp_pending = self._sel_pending, self._exp_pending
+            self.rejected_steps += 1
             if not (st1 & 0xFF):
                 self.format_rejected = True  # (a clean stage-1 verdict and still rejected: the separators)
             for entry in ({"rejected": True}, {"exact": True}):
                 # the call for rejected batches (repair on the device); a batch it cannot take either -- documents that are not
                 # separated AND let a scalar run on across a boundary -- says REJECTED once more and is the exact call's
-                self.step(getattr(self, "_last_stream", 0), **entry)
+                self.step(self._last_stream, **entry)
                 if pending is not None:  # the select that was queued behind the rejected step read outputs that were not valid
                     self.select(*pending)
                 if exp_pending is not None:  # ... and so did the explode
                     self.explode(*exp_pending)
-                if str(self.device) != "cpu":  # (the CPU tests' stub engines are synchronous)
+                if _on_gpu(self.device):
                     torch.cuda.synchronize(self.device)
-                r = self.result.cpu().numpy()
-                st1, sflags, wflags = int(r[1]) & 0xFFFFFFFF, int(r[4]) & 0xFFFFFFFF, int(r[8]) & 0xFFFFFFFF
-                if not (st1 & 0x800):
+                r, st1, sflags, wflags = self._record()
+                if not (st1 & SJMI_ST_REJECTED):
                     break
                 self.format_rejected = False  # (... and so are the batches behind it: the latch below moves to the exact call)
                 self.unrepairable = True
-        if st1 & 0x300:
+        if st1 & (SJMI_ST_CAPACITY | SJMI_ST_INTERNAL):
             raise RuntimeError("stage 1 of the shard: capacity / internal error (status 0x%x)" % st1)
         if sflags & 1:
             raise RuntimeError("string buffer capacity exceeded")
@@ -397,7 +426,7 @@ def sharded_step(shard, stream=0, always_gather=False):
     import torch
     import torch.distributed as dist
     side = None
-    if not stream and str(shard.device) != "cpu":
+    if not stream and _on_gpu(shard.device):
         # stream handle 0 means "the engine context's own stream" to the C ABI -- and it is also the handle of torch's legacy
         # default stream, so it cannot name that one.  The torch ops that read the result record below must be ordered behind
         # the kernels: the kernels go on a side stream of the shard's, fenced against the caller's current stream on both
@@ -406,7 +435,7 @@ def sharded_step(shard, stream=0, always_gather=False):
         if cur.cuda_stream:
             stream = cur.cuda_stream
         else:
-            side = getattr(shard, "_side_stream", None)
+            side = shard._side_stream
             if side is None:
                 side = shard._side_stream = torch.cuda.Stream(device=shard.device)
             side.wait_stream(cur)
@@ -452,8 +481,7 @@ class DocumentShard:
         total = int(data.numel()) if hasattr(data, "numel") else len(data)
         self.length = total - self.halo
         assert self.halo % 64 == 0 and (self.is_last or self.length % 64 == 0)
-        self.buf = torch.zeros(total + 128, dtype=torch.uint8, device=device)
-        self.buf[:total] = data if hasattr(data, "numel") else torch.frombuffer(bytearray(data), dtype=torch.uint8).to(device)
+        self.buf = _upload(data, device, 128)
         self.capacity = self.length // index_ratio + 66
         self.idx = torch.empty(self.capacity, dtype=torch.int32, device=device)
         self.result = torch.zeros(2, dtype=torch.int64, device=device)  # sjmi_stage1_result
@@ -469,9 +497,9 @@ class DocumentShard:
         """(synchronise first) -> (count, status bits without UNCLOSED, parity after the shard)"""
         r = self.result.cpu().numpy()
         st = int(r[1]) & 0xFFFFFFFF
-        if st & 0x300:
+        if st & (SJMI_ST_CAPACITY | SJMI_ST_INTERNAL):
             raise RuntimeError("stage 1 of the shard: capacity / internal error (status 0x%x)" % st)
-        if st & 0x400:
+        if st & SJMI_ST_HALO:
             raise HaloTooShort("a backslash run fills the %d bytes of halo in front of the shard" % self.halo)
         return int(r[0]), st & 0xFD, (st >> 1) & 1
 

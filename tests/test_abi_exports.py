@@ -20,6 +20,41 @@ def test_library_exports_every_declared_symbol():
     assert set(S.binding.EXPORTS) <= set(names)
 
 
+def _kind(c_type, what):
+    """The ctypes kinds a C parameter or result type of the header may be declared as; a type that is none of these fails the test."""
+    c_type = " ".join(c_type.split())
+    if "*" in c_type:
+        return (ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.c_char_p)
+    kinds = {"int": (ctypes.c_int,), "uint64_t": (ctypes.c_uint64,), "uint32_t": (ctypes.c_uint32,), "void": (None,)}
+    assert c_type in kinds, "%s: no ctypes kind known for %r" % (what, c_type)
+    return kinds[c_type]
+
+
+def test_binding_table_matches_every_prototype():
+    """binding.ABI against include/sjmi.h: every prototype's name, parameter count, kind per parameter and result kind; no name
+    the header lacks.  Needs no built library."""
+    from simdjson_java_amd import binding
+    header = open(os.path.join(ROOT, "include", "sjmi.h")).read()
+    header = re.sub(r"/\*.*?\*/", "", header, flags=re.S)
+    protos = re.findall(r"^((?:const\s+)?\w+[\s*]+)(sjmi_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", header, flags=re.M)
+    names = set(re.findall(r"\b(sjmi_[a-z0-9_]+)\s*\(", header))
+    assert {name for _, name, _ in protos} == names and len(protos) == len(names) >= 92, "a prototype the pattern does not parse"
+    for result, name, params in protos:
+        assert name in binding.ABI, "%s: declared in include/sjmi.h but not in binding.ABI" % name
+        restype, argtypes = binding.ABI[name]
+        params = [] if params.strip() == "void" else [p.strip() for p in params.split(",")]
+        assert len(argtypes) == len(params), "%s: %d parameters in the header, %d in binding.ABI" % (name, len(params), len(argtypes))
+        for k, (param, argtype) in enumerate(zip(params, argtypes)):
+            c_type = re.sub(r"\w+$", "", param)  # (every parameter of the header is named)
+            assert argtype is not None and argtype in _kind(c_type, name), "%s: parameter %d is %r, declared %r" % (name, k, param, argtype)
+        if "*" in result:
+            assert " ".join(result.split()) == "const char*" and restype is ctypes.c_char_p, "%s: result %r, declared %r" % (name, result, restype)
+        else:
+            assert restype in _kind(result, name), "%s: result %r, declared %r" % (name, result, restype)
+    assert set(binding.ABI) == names, "in binding.ABI but not in include/sjmi.h: %s" % sorted(set(binding.ABI) - names)
+    assert isinstance(binding.EXPORTS, list) and binding.EXPORTS == list(binding.ABI)
+
+
 def test_no_cpu_fallback_without_gpu():
     """The product path must fail loudly when no GPU is present (this container has none)."""
     import pytest

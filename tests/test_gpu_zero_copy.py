@@ -2,7 +2,6 @@
 arrays the kernels write indexes / string records / tape straight into the caller's memory.  The bytes must be the ones the
 staged path (pageable arrays: device buffers + download) delivers, for accepted and for rejected documents, through
 registration changes, and for the two-call forms that read the indexes of the previous call back on the device."""
-import ctypes as C
 import random
 
 import numpy as np
@@ -116,8 +115,8 @@ def test_registration_changes_drop_the_cached_views(ctx):
     want = _staged(ctx, doc)
     for state in ("pageable", "registered", "pageable", "registered", "pageable"):
         if state == "registered":
-            assert lib().sjmi_host_register(ctx._h, C.c_void_p(idx.ctypes.data), C.c_uint64(idx.nbytes)) == 0
-            assert lib().sjmi_host_register(ctx._h, C.c_void_p(sb.ctypes.data), C.c_uint64(sb.nbytes)) == 0
+            assert lib().sjmi_host_register(ctx._h, idx.ctypes.data, idx.nbytes) == 0
+            assert lib().sjmi_host_register(ctx._h, sb.ctypes.data, sb.nbytes) == 0
         try:
             for _ in range(2):
                 idx[:] = 0
@@ -125,8 +124,8 @@ def test_registration_changes_drop_the_cached_views(ctx):
                 assert np.array_equal(got[0], want[0]) and bytes(got[2]) == want[2] and got[1] == 0
         finally:
             if state == "registered":
-                assert lib().sjmi_host_unregister(ctx._h, C.c_void_p(idx.ctypes.data)) == 0
-                assert lib().sjmi_host_unregister(ctx._h, C.c_void_p(sb.ctypes.data)) == 0
+                assert lib().sjmi_host_unregister(ctx._h, idx.ctypes.data) == 0
+                assert lib().sjmi_host_unregister(ctx._h, sb.ctypes.data) == 0
 
 
 def test_batch_after_a_zero_copy_call_reads_its_own_indexes(ctx):
@@ -136,12 +135,12 @@ def test_batch_after_a_zero_copy_call_reads_its_own_indexes(ctx):
     from simdjson_java_amd.binding import lib
     single = b'{"first":["call","with","quite","a","few","strings","so","that","the","arrays","differ"]}'
     idx_host = np.empty(len(single) + 2 + 64, dtype=np.uint32)
-    assert lib().sjmi_host_register(ctx._h, C.c_void_p(idx_host.ctypes.data), C.c_uint64(idx_host.nbytes)) == 0
+    assert lib().sjmi_host_register(ctx._h, idx_host.ctypes.data, idx_host.nbytes) == 0
     try:
         got_idx, st = ctx.stage1(single, idx=idx_host)
         assert st == 0 and np.array_equal(got_idx, O.stage1(single)[0])
     finally:
-        assert lib().sjmi_host_unregister(ctx._h, C.c_void_p(idx_host.ctypes.data)) == 0
+        assert lib().sjmi_host_unregister(ctx._h, idx_host.ctypes.data) == 0
     idx_host[:] = 0xFFFFFFFF  # (whatever a stale read would find)
     docs = [b'{"a":"fine"}\n', b'[1,2,3]\n', b'{"k":["x","y","bad \\q escape","z"]}\n', b'"tail"\n']
     buf = b"".join(docs)
@@ -157,8 +156,8 @@ def test_batch_after_a_zero_copy_call_reads_its_own_indexes(ctx):
     assert buf[idx[fei] + 1:idx[fei] + 5] == b"bad " and fec == want_code
     # and the single-document two-call form right behind an unregistration refuses instead of reading through a dead view
     import simdjson_java_amd as S
-    assert lib().sjmi_host_register(ctx._h, C.c_void_p(idx_host.ctypes.data), C.c_uint64(idx_host.nbytes)) == 0
+    assert lib().sjmi_host_register(ctx._h, idx_host.ctypes.data, idx_host.nbytes) == 0
     ctx.stage1(single, idx=idx_host)
-    assert lib().sjmi_host_unregister(ctx._h, C.c_void_p(idx_host.ctypes.data)) == 0
+    assert lib().sjmi_host_unregister(ctx._h, idx_host.ctypes.data) == 0
     with pytest.raises(S.SjmiError):
         ctx.unescape(4096)

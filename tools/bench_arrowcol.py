@@ -17,7 +17,6 @@ bytes read and 8.125 written per live cell (the counting call: 0.125 written) --
 import argparse
 import json
 import os
-import statistics
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -71,23 +70,12 @@ def main():
     a = ap.parse_args()
     import torch
     import simdjson_java_amd as S
-    from simdjson_java_amd import sharding
-    from tools import workloads as W
-    dev = torch.device("cuda", 0)
-    data, offs = W.unique_docs(0, a.docs)
-    ctx = S.Context(0, 1 << 20)
-    shard = sharding.BatchShard(ctx, torch.from_numpy(data), offs, dev, index_ratio=4, string_ratio=1.0, tape_ratio=0.25)
+    from tools import opbench
+    dev, ctx, stream = opbench.device()
+    _, offs, shard, _ = opbench.configs_shard(ctx, dev, stream, a.docs)
     select = S.SelectPlan(POINTERS)
-    # (handle 0 names the context's own stream in the C ABI, so torch's default stream cannot carry the events: a stream of its own)
-    side = torch.cuda.Stream(device=dev)
-    torch.cuda.set_stream(side)
-    stream = side.cuda_stream
-    assert stream != 0
-    shard.step(stream)
     types, values = shard.select(select, stream)
     torch.cuda.synchronize()
-    c = shard.check()
-    assert c["failed_documents"] == 0 and not getattr(shard, "rejected_steps", 0), c
     n, n_cols = a.docs, len(POINTERS)
 
     # ---- the schemas: the numeric columns from the data (those whose commonest type is a number), the mixed one by rotation
@@ -146,21 +134,6 @@ def main():
         print(json.dumps({"traced": list(legs), "calls_each": a.trace_legs, "counts": counts}))
         return
 
-    def timed(fn, steps, warmup):
-        """median / min of `steps` single executions of fn(), each between two HIP events"""
-        for _ in range(warmup):
-            fn()
-        torch.cuda.synchronize()
-        ms = []
-        for _ in range(steps):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            fn()
-            e1.record()
-            e1.synchronize()
-            ms.append(e0.elapsed_time(e1))
-        return {"median_ms": statistics.median(ms), "min_ms": min(ms), "steps": steps}
-
     least = {name: int(live_of[name] * counts[name]["fields"] * (9 + (8.125 if legs[name][4] else 0.125))) for name in legs}
     src = torch.zeros(max(least.values()) // 16 + 1, dtype=torch.int64, device=dev)
     dst = torch.empty_like(src)
@@ -169,26 +142,15 @@ def main():
         timed_legs[name] = lambda name=name: run_leg(name)
         timed_legs[name + "_torch"] = lambda schema=schema, t=t, v=v, name=name: torch_fields(schemas[schema], t, v, live_of[name])
         timed_legs[name + "_copy"] = lambda name=name: dst[:least[name] // 16].copy_(src[:least[name] // 16])
-    # interleaved, so that drift of the box hits every leg alike
-    rounds = 3
-    runs = {k: [] for k in timed_legs}
-    for r in range(rounds):
-        for name, fn in timed_legs.items():
-            runs[name].append(timed(fn, max(3, a.steps // rounds), a.warmup if r == 0 else 1))
     res = {"documents": n, "input_bytes": int(offs[-1]), "paths": POINTERS, "columns": n_cols, "device": torch.cuda.get_device_name(0),
            "commonest_type": [chr(x) for x in commonest], "schemas": {k: [list(f) for f in v] for k, v in schemas.items()}, "filter": [list(x) for x in terms],
            "counts": counts, "least_bytes_moved": least,
            "verified": "every leg: records, validity words and data words equal the framework formulation's; nothing written behind the live rows"}
-    for name, rs in runs.items():
-        res[name] = {"median_ms": statistics.median(x["median_ms"] for x in rs), "min_ms": min(x["min_ms"] for x in rs), "steps": sum(x["steps"] for x in rs)}
+    res.update(opbench.measure(timed_legs, a.steps, a.warmup))
     for name in legs:
         res[name + "_over_torch"] = res[name]["median_ms"] / res[name + "_torch"]["median_ms"]
         res[name + "_over_copy"] = res[name]["median_ms"] / res[name + "_copy"]["median_ms"]
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as f:
-        json.dump(res, f, indent=1)
-        f.write("\n")
-    print(json.dumps(res))
+    opbench.write(a.out, res)
     plan.close()
     select.close()
     ctx.close()

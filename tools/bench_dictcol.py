@@ -14,7 +14,6 @@ The insert kernel's share comes from a run of its own under rocprofv3 --kernel-t
 SJMI_LIB names a variant library for an A/B (tools/build_variant.sh).
   python tools/bench_dictcol.py [--rows N] [--steps K] [--warmup W] [--columns a,b] [--host] [--out PATH]"""
 import argparse
-import json
 import os
 import statistics
 import sys
@@ -72,11 +71,8 @@ def main():
     from tests import select_common as SEL
     from tests.conftest import load_fixture
     from tests.test_gpu_batch import _pack
-    dev = torch.device("cuda", 0)
-    ctx = S.Context(0, 1 << 20)
-    side = torch.cuda.Stream(device=dev)  # (handle 0 names the context's own stream in the C ABI: a stream of its own)
-    torch.cuda.set_stream(side)
-    stream = side.cuda_stream
+    from tools import opbench
+    dev, ctx, stream = opbench.device()
     rng = np.random.default_rng(17)
     wanted = a.columns.split(",")
     cols = []
@@ -126,21 +122,6 @@ def main():
         ctx.string_column_device(col["types"].data_ptr(), col["values"].data_ptr(), col["n"], col["sb"].data_ptr(), col["offsets"].data_ptr(),
                                  col["validity"].data_ptr(), col["str_bytes"].data_ptr(), col["str_bytes"].numel(), col["sresult"].data_ptr(), stream)
 
-    def timed(fn, steps, warmup):
-        """median / min of `steps` single executions of fn(), each between two HIP events"""
-        for _ in range(warmup):
-            fn()
-        torch.cuda.synchronize()
-        ms = []
-        for _ in range(steps):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            fn()
-            e1.record()
-            e1.synchronize()
-            ms.append(e0.elapsed_time(e1))
-        return {"median_ms": statistics.median(ms), "min_ms": min(ms), "steps": steps}
-
     res = {"device": torch.cuda.get_device_name(0), "library": os.environ.get("SJMI_LIB") or "libsjmi.so", "columns": []}
     for col in cols:
         buffers(col)
@@ -161,14 +142,9 @@ def main():
         moved = 13 * col["n"] + r[4]
         src, dst = torch.empty(moved, dtype=torch.uint8, device=dev), torch.empty(moved, dtype=torch.uint8, device=dev)
         legs = {"sizing": lambda: encode(col, False), "full": lambda: encode(col, True), "string_gather": lambda: gather(col), "d2d_copy": lambda: dst.copy_(src)}
-        runs = {k: [] for k in legs}
-        for rnd in range(3):  # interleaved, so that drift of the box hits every leg alike
-            for name, fn in legs.items():
-                runs[name].append(timed(fn, max(3, a.steps // 3), a.warmup if rnd == 0 else 1))
         out = {"name": col["name"], "rows": col["n"], "n_valid": r[1], "n_distinct": r[3], "dict_capacity": col["capacity"], "dict_bytes": r[4],
                "string_bytes": int(col["sresult"][0]), "least_bytes_moved": moved}
-        for name, rs in runs.items():
-            out[name] = {"median_ms": statistics.median(x["median_ms"] for x in rs), "min_ms": min(x["min_ms"] for x in rs), "steps": sum(x["steps"] for x in rs)}
+        out.update(opbench.measure(legs, a.steps, a.warmup))
         full = out["full"]["median_ms"]
         out["full_over_string_gather"] = full / out["string_gather"]["median_ms"]
         out["full_over_d2d_copy"] = full / out["d2d_copy"]["median_ms"]
@@ -192,11 +168,7 @@ def main():
                 out["host_route"] = {"median_ms": statistics.median(ms), "min_ms": min(ms), "steps": 3, "over_full": statistics.median(ms) / full}
         res["columns"].append(out)
         del src, dst
-    os.makedirs(os.path.dirname(a.out), exist_ok=True)
-    with open(a.out, "w") as f:
-        json.dump(res, f, indent=1)
-        f.write("\n")
-    print(json.dumps(res))
+    opbench.write(a.out, res)
     for _, plan in keep:
         plan.close()
     ctx.close()

@@ -17,7 +17,6 @@ workload, interleaved, medians of event-timed single executions:
   d2h             the copy of those bytes into pinned memory -- what a caller without explode has to do.
   python tools/bench_explode.py [--workloads configs,statuses,wide] [--docs N] [--bytes B] [--steps K] [--warmup W] [--out PATH]"""
 import argparse
-import json
 import os
 import statistics
 import sys
@@ -32,47 +31,11 @@ VERIFY_DOCS = 20000
 CHUNK = 10  # statuses per document of the `statuses` workload
 
 
-def timed(torch, fn, steps, warmup):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(steps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        fn()
-        e1.record()
-        e1.synchronize()
-        ms.append(e0.elapsed_time(e1))
-    return ms
-
-
-def measure(torch, legs, steps, warmup, rounds=3):
-    """interleaved, so that drift of the box hits every leg alike -> {leg: {median_ms, min_ms, round_medians_ms, spread, steps}};
-    spread = (largest - smallest round median) / median: what two repeats of the same leg differ by in this run"""
-    runs = {k: [] for k in legs}
-    for r in range(rounds):
-        for name, fn in legs.items():
-            few = name == "d2h"
-            runs[name] += [timed(torch, fn, max(3, steps // (3 if few else 1) // rounds), warmup if r == 0 else 1)]
-    out = {}
-    for name, rs in runs.items():
-        meds = [statistics.median(x) for x in rs]
-        out[name] = {"median_ms": statistics.median(meds), "min_ms": min(min(x) for x in rs), "round_medians_ms": meds, "spread": (max(meds) - min(meds)) / statistics.median(meds),
-                     "steps": sum(len(x) for x in rs)}
-    return out
-
-
 class Batch:
     """a parsed batch on the device, and an explode of it"""
 
-    def __init__(self, torch, S, sharding, ctx, data, offs, stream, **ratios):
-        self.torch, self.ctx, self.stream = torch, ctx, stream
-        self.shard = sharding.BatchShard(ctx, data if isinstance(data, bytes) else torch.from_numpy(data), offs, torch.device("cuda", 0), **ratios)
-        self.shard.step(stream)
-        torch.cuda.synchronize()
-        self.c = self.shard.check()
-        assert self.c["failed_documents"] == 0 and not getattr(self.shard, "rejected_steps", 0), self.c
+    def __init__(self, torch, ctx, stream, shard, c):
+        self.torch, self.ctx, self.shard, self.c, self.stream = torch, ctx, shard, c, stream
         self.sb_bytes, self.tape_bytes = int(self.c["string_bytes"]), 8 * int(self.c["tape_words"])
 
     def explode(self, plan, capacity):
@@ -114,25 +77,19 @@ def main():
     a = ap.parse_args()
     import torch
     import simdjson_java_amd as S
-    from simdjson_java_amd import sharding
     from oracle import oracle as O
     from tests import explode_common as EC
     from tests import select_common as SC
-    from tools import workloads as W
+    from tools import opbench
     O.build()
-    dev = torch.device("cuda", 0)
-    ctx = S.Context(0, 1 << 20)
-    # (handle 0 names the context's own stream in the C ABI, so torch's default stream cannot carry the events: a stream of its own)
-    side = torch.cuda.Stream(device=dev)
-    torch.cuda.set_stream(side)
-    stream = side.cuda_stream
-    assert stream != 0
+    dev, ctx, stream = opbench.device()
+
     out = {"device": torch.cuda.get_device_name(0), "library": os.environ.get("SJMI_LIB") or "libsjmi.so"}
     todo = a.workloads.split(",")
 
     if "configs" in todo:
-        data, offs = W.unique_docs(0, a.docs)
-        b = Batch(torch, S, sharding, ctx, data, offs, stream, index_ratio=4, string_ratio=1.0, tape_ratio=0.25)
+        data, offs, shard, c = opbench.configs_shard(ctx, dev, stream, a.docs)
+        b = Batch(torch, ctx, stream, shard, c)
         plan, sel = S.ExplodePlan(CONFIGS_BASE, CONFIGS_POINTERS), S.SelectPlan(CONFIGS_SELECT)
         ro, _, _ = b.explode(plan, 0)
         torch.cuda.synchronize()
@@ -150,7 +107,7 @@ def main():
         res = {"documents": a.docs, "input_bytes": int(offs[-1]), "base": CONFIGS_BASE, "element_pointers": CONFIGS_POINTERS,
                "verified_documents": nv, "verified_rows": n, "verified_present": int(present), "tape_bytes": b.tape_bytes,
                "string_record_bytes": b.sb_bytes}
-        res.update(measure(torch, b.legs(plan, total, sel), a.steps, a.warmup))
+        res.update(opbench.measure(b.legs(plan, total, sel), a.steps, a.warmup, third={"d2h"}))
         out["configs"] = summarise(res, total)
         plan.close()
         sel.close()
@@ -164,7 +121,7 @@ def main():
         lens = np.tile(np.array([len(c) + 1 for c in chunks], dtype=np.uint64), reps)
         offs = np.concatenate([[0], np.cumsum(lens)]).astype(np.uint64)
         data = np.tile(np.frombuffer(unit, dtype=np.uint8), reps)
-        b = Batch(torch, S, sharding, ctx, data, offs, stream, index_ratio=4, string_ratio=1.0, tape_ratio=0.25)
+        b = Batch(torch, ctx, stream, *opbench.parsed_shard(ctx, dev, stream, data, offs, **opbench.RATIOS))
         plan = S.ExplodePlan("/statuses", ptrs)
         sel = S.SelectPlan(["/statuses/0" + p for p in ptrs])
         parsed = [O.parse(c) for c in chunks]
@@ -185,7 +142,7 @@ def main():
         res = {"documents": len(chunks) * reps, "statuses_per_document": CHUNK, "input_bytes": int(offs[-1]), "base": "/statuses", "element_pointers": ptrs,
                "verified_rows": total, "verified_present_per_copy": int(present), "tape_bytes": b.tape_bytes, "string_record_bytes": b.sb_bytes,
                "tape_words_per_document": b.tape_bytes // 8 // (len(chunks) * reps)}
-        res.update(measure(torch, b.legs(plan, total, sel), a.steps, a.warmup))
+        res.update(opbench.measure(b.legs(plan, total, sel), a.steps, a.warmup, third={"d2h"}))
         out["statuses"] = summarise(res, total)
         plan.close()
         sel.close()
@@ -200,7 +157,7 @@ def main():
         for name, docs in (("small_only", small), ("with_one_wide", small[:50000] + [wide] + small[50000:])):
             blob = b"".join(d + b"\n" for d in docs)
             offs = np.concatenate([[0], np.cumsum([len(d) + 1 for d in docs])]).astype(np.uint64)
-            b = Batch(torch, S, sharding, ctx, blob, offs, stream)
+            b = Batch(torch, ctx, stream, *opbench.parsed_shard(ctx, dev, stream, blob, offs))
             ro, _, _ = b.explode(plan, 0)
             torch.cuda.synchronize()
             total = int(ro[-1].item())
@@ -218,7 +175,7 @@ def main():
                 plain = np.array([c[0] != ord('"') for c in col])
                 assert (vcpu[p][plain] == np.array([c[1] for c in col if c[0] != ord('"')], dtype=np.uint64)).all()
                 assert ((vcpu[p][~plain] >> np.uint64(32)) == np.array([len(c[1]) for c in col if c[0] == ord('"')], dtype=np.uint64)).all()
-            ms = timed(torch, lambda: b.explode(plan, total), a.steps, a.warmup)
+            ms = opbench.timed(lambda: b.explode(plan, total), a.steps, a.warmup)
             res[name] = {"rows": total, "median_ms": statistics.median(ms), "min_ms": min(ms), "steps": len(ms)}
             del b
         extra = res["with_one_wide"]["median_ms"] - res["small_only"]["median_ms"]
@@ -228,11 +185,7 @@ def main():
         out["wide"] = res
         plan.close()
 
-    os.makedirs(os.path.dirname(a.out), exist_ok=True)
-    with open(a.out, "w") as f:
-        json.dump(out, f, indent=1)
-        f.write("\n")
-    print(json.dumps(out))
+    opbench.write(a.out, out)
     ctx.close()
 
 

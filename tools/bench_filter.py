@@ -17,7 +17,6 @@ a rocprofv3 --kernel-trace run of its own, whose dispatches then come in that or
 import argparse
 import json
 import os
-import statistics
 import sys
 
 import numpy as np
@@ -93,23 +92,12 @@ def main():
     a = ap.parse_args()
     import torch
     import simdjson_java_amd as S
-    from simdjson_java_amd import sharding
-    from tools import workloads as W
-    dev = torch.device("cuda", 0)
-    data, offs = W.unique_docs(0, a.docs)
-    ctx = S.Context(0, 1 << 20)
-    shard = sharding.BatchShard(ctx, torch.from_numpy(data), offs, dev, index_ratio=4, string_ratio=1.0, tape_ratio=0.25)
+    from tools import opbench
+    dev, ctx, stream = opbench.device()
+    _, offs, shard, _ = opbench.configs_shard(ctx, dev, stream, a.docs)
     select = S.SelectPlan(POINTERS)
-    # (handle 0 names the context's own stream in the C ABI, so torch's default stream cannot carry the events: a stream of its own)
-    side = torch.cuda.Stream(device=dev)
-    torch.cuda.set_stream(side)
-    stream = side.cuda_stream
-    assert stream != 0
-    shard.step(stream)
     types, values = shard.select(select, stream)
     torch.cuda.synchronize()
-    c = shard.check()
-    assert c["failed_documents"] == 0 and not getattr(shard, "rejected_steps", 0), c
     n, n_cols, sb = a.docs, len(POINTERS), shard.sb
 
     # ---- the plans: constants from the data, so that the kept share is what the leg's name says
@@ -161,21 +149,6 @@ def main():
         print(json.dumps({"traced": ["numeric", "string_eq", "mixed4"], "calls_each": a.trace_legs, "kept_rows": kept}))
         return
 
-    def timed(fn, steps, warmup):
-        """median / min of `steps` single executions of fn(), each between two HIP events"""
-        for _ in range(warmup):
-            fn()
-        torch.cuda.synchronize()
-        ms = []
-        for _ in range(steps):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            fn()
-            e1.record()
-            e1.synchronize()
-            ms.append(e0.elapsed_time(e1))
-        return {"median_ms": statistics.median(ms), "min_ms": min(ms), "steps": steps}
-
     # ---- the string gather of "/z": all rows, and the compacted column of each kept share (buffers of the exact size, sized here)
     def gather_buffers(t, v, rows):
         offsets, validity, data, result = shard.string_column(t, v, stream=stream)
@@ -207,28 +180,17 @@ def main():
         legs[name + "_read_pass"] = lambda name=name: scratch[:least[name] // 8].sum()
     for name in g_kept:
         legs["strcol_" + name] = lambda name=name: filter_then_gather(name)
-    # interleaved, so that drift of the box hits every leg alike
-    rounds = 3
-    runs = {k: [] for k in legs}
-    for r in range(rounds):
-        for name, fn in legs.items():
-            runs[name].append(timed(fn, max(3, a.steps // rounds), a.warmup if r == 0 else 1))
     res = {"documents": n, "input_bytes": int(offs[-1]), "paths": POINTERS, "columns": n_cols, "device": torch.cuda.get_device_name(0),
            "plans": {k: [[c, op, const.decode("latin-1") if isinstance(const, bytes) else const] for c, op, const in v] for k, v in plans.items()},
            "kept_rows": kept, "least_bytes_moved": least, "strcol_bytes": dict({"all_rows": g_all["bytes"]}, **{k: g["bytes"] for k, g in g_kept.items()}),
            "verified": "every plan: n_kept, rows, keep words and all compacted cells equal the framework formulation's"}
-    for name, rs in runs.items():
-        res[name] = {"median_ms": statistics.median(x["median_ms"] for x in rs), "min_ms": min(x["min_ms"] for x in rs), "steps": sum(x["steps"] for x in rs)}
+    res.update(opbench.measure(legs, a.steps, a.warmup))
     for name in ("numeric", "string_eq", "mixed4"):
         res[name + "_over_torch"] = res[name]["median_ms"] / res[name + "_torch"]["median_ms"]
         res[name + "_over_read_pass"] = res[name]["median_ms"] / res[name + "_read_pass"]["median_ms"]
     for name in g_kept:
         res["strcol_" + name + "_over_all_rows"] = res["strcol_" + name]["median_ms"] / res["strcol_all_rows"]["median_ms"]
-    os.makedirs(os.path.dirname(a.out), exist_ok=True)
-    with open(a.out, "w") as f:
-        json.dump(res, f, indent=1)
-        f.write("\n")
-    print(json.dumps(res))
+    opbench.write(a.out, res)
     for p in compiled.values():
         p.close()
     select.close()

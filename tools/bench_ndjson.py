@@ -15,9 +15,7 @@ event-timed single executions:
 import argparse
 import json
 import os
-import statistics
 import sys
-import time
 
 import numpy as np
 
@@ -25,52 +23,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-def timed(torch, fn, steps, warmup):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(steps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        fn()
-        e1.record()
-        e1.synchronize()
-        ms.append(e0.elapsed_time(e1))
-    return ms
-
-
-def wall(torch, fn, steps):
-    ms = []
-    for _ in range(steps):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        fn()
-        torch.cuda.synchronize()
-        ms.append((time.perf_counter() - t0) * 1e3)
-    return ms
-
-
-def measure(torch, legs, steps, warmup, rounds=3):
-    """interleaved, so that drift of the box hits every leg alike -> {leg: {median_ms, min_ms, round_medians_ms, spread, steps}}"""
-    runs = {k: [] for k in legs}
-    for r in range(rounds):
-        for name, fn in legs.items():
-            if name == "host":
-                runs[name] += [wall(torch, fn, 2)]
-            else:
-                runs[name] += [timed(torch, fn, max(3, steps // rounds), warmup if r == 0 else 1)]
-    out = {}
-    for name, rs in runs.items():
-        meds = [statistics.median(x) for x in rs]
-        out[name] = {"median_ms": statistics.median(meds), "min_ms": min(min(x) for x in rs), "round_medians_ms": meds,
-                     "spread": (max(meds) - min(meds)) / statistics.median(meds), "steps": sum(len(x) for x in rs)}
-    return out
-
-
-def run(torch, S, sharding, ctx, stream, data, offs, steps, warmup, **ratios):
+def run(torch, S, sharding, opbench, dev, ctx, stream, data, offs, steps, warmup):
     """data: np.uint8, one document per line; offs: the generator's offsets"""
-    dev = torch.device("cuda", 0)
     n, n_docs = int(data.size), int(offs.size) - 1
     host = torch.from_numpy(data)
     raw = torch.zeros(n + 128, dtype=torch.uint8, device=dev)
@@ -83,12 +37,8 @@ def run(torch, S, sharding, ctx, stream, data, offs, steps, warmup, **ratios):
     r = res.cpu().numpy()
     assert (int(r[0]), int(r[1]), int(r[2])) == (n_docs, n, 1), r
     assert np.array_equal(d_offs.cpu().numpy().view(np.uint64), offs), "the offsets differ from the generator's"
-    shard = sharding.BatchShard(ctx, raw[:n], None, dev, device_offsets=d_offs, **ratios)
-    shard.step(stream)
-    torch.cuda.synchronize()
-    assert not (int(shard.result.cpu().numpy()[1]) & 0x800)
-    c = shard.check()
-    assert c["failed_documents"] == 0 and not getattr(shard, "rejected_steps", 0), c
+    shard = sharding.BatchShard(ctx, raw[:n], None, dev, device_offsets=d_offs, **opbench.RATIOS)
+    opbench.checked_step(shard, stream)  # (nothing rejected: the timed step is the optimistic one)
     words = raw[:n // 8 * 8].view(torch.int64)
     h2d = torch.empty(n_docs + 1, dtype=torch.int64, device=dev)
 
@@ -105,7 +55,7 @@ def run(torch, S, sharding, ctx, stream, data, offs, steps, warmup, **ratios):
             "parse": lambda: shard.step(stream),
             "host": host_offsets}
     out = {"documents": n_docs, "input_bytes": n, "tile_bytes": int(S.lib().sjmi_ndjson_tile_bytes())}
-    out.update(measure(torch, legs, steps, warmup))
+    out.update(opbench.measure(legs, steps, warmup, host={"host"}))
     sp = out["split"]["median_ms"]
     out["split_over_read"] = sp / out["read"]["median_ms"]
     out["split_size_over_read"] = out["split_size"]["median_ms"] / out["read"]["median_ms"]
@@ -128,20 +78,14 @@ def main():
     import simdjson_java_amd as S
     from simdjson_java_amd import sharding
     from tests.conftest import load_fixture
+    from tools import opbench
     from tools import workloads as W
-    dev = torch.device("cuda", 0)
-    ctx = S.Context(0, 1 << 20)
-    # (handle 0 names the context's own stream in the C ABI, so torch's default stream cannot carry the events: a stream of its own)
-    side = torch.cuda.Stream(device=dev)
-    torch.cuda.set_stream(side)
-    stream = side.cuda_stream
-    assert stream != 0
+    dev, ctx, stream = opbench.device()
     out = {"device": torch.cuda.get_device_name(0), "library": os.environ.get("SJMI_LIB") or "libsjmi.so"}
     todo = a.workloads.split(",")
     if "configs" in todo:
         data, offs = W.unique_docs(0, a.docs)
-        out["configs"] = run(torch, S, sharding, ctx, stream, np.asarray(data), np.asarray(offs, dtype=np.uint64), a.steps, a.warmup,
-                             index_ratio=4, string_ratio=1.0, tape_ratio=0.25)
+        out["configs"] = run(torch, S, sharding, opbench, dev, ctx, stream, np.asarray(data), np.asarray(offs, dtype=np.uint64), a.steps, a.warmup)
         del data
     if "twitter" in todo:
         statuses = json.loads(load_fixture("twitter.json"))["statuses"]
@@ -151,13 +95,9 @@ def main():
         lens = np.tile(np.array([len(l) for l in lines], dtype=np.uint64), reps)
         offs = np.concatenate([[0], np.cumsum(lens)]).astype(np.uint64)
         data = np.tile(np.frombuffer(unit, dtype=np.uint8), reps)
-        out["twitter"] = run(torch, S, sharding, ctx, stream, data, offs, a.steps, a.warmup, index_ratio=4, string_ratio=1.0, tape_ratio=0.25)
+        out["twitter"] = run(torch, S, sharding, opbench, dev, ctx, stream, data, offs, a.steps, a.warmup)
         out["twitter"]["statuses"] = len(lines)
-    os.makedirs(os.path.dirname(a.out), exist_ok=True)
-    with open(a.out, "w") as f:
-        json.dump(out, f, indent=1)
-        f.write("\n")
-    print(json.dumps(out))
+    opbench.write(a.out, out)
     ctx.close()
 
 

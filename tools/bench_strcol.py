@@ -11,9 +11,7 @@ columns those that hold strings.  Every such column is first verified against te
   (d) the select step the gather follows.
   python tools/bench_strcol.py [--docs N] [--steps K] [--warmup W] [--out PATH]"""
 import argparse
-import json
 import os
-import statistics
 import sys
 
 import numpy as np
@@ -33,24 +31,13 @@ def main():
     a = ap.parse_args()
     import torch
     import simdjson_java_amd as S
-    from simdjson_java_amd import sharding
     from tests import strcol_common as SC
-    from tools import workloads as W
-    dev = torch.device("cuda", 0)
-    data, offs = W.unique_docs(0, a.docs)
-    ctx = S.Context(0, 1 << 20)
-    shard = sharding.BatchShard(ctx, torch.from_numpy(data), offs, dev, index_ratio=4, string_ratio=1.0, tape_ratio=0.25)
+    from tools import opbench
+    dev, ctx, stream = opbench.device()
+    data, offs, shard, c = opbench.configs_shard(ctx, dev, stream, a.docs)
     plan = S.SelectPlan(POINTERS)
-    # (handle 0 names the context's own stream in the C ABI, so torch's default stream cannot carry the events: a stream of its own)
-    side = torch.cuda.Stream(device=dev)
-    torch.cuda.set_stream(side)
-    stream = side.cuda_stream
-    assert stream != 0
-    shard.step(stream)
     types, values = shard.select(plan, stream)
     torch.cuda.synchronize()
-    c = shard.check()
-    assert c["failed_documents"] == 0 and not getattr(shard, "rejected_steps", 0), c
     sb_host = shard.sb[:int(c["string_bytes"])].cpu().numpy()
 
     # ---- the string-valued columns, sized, and verified before timing
@@ -78,38 +65,15 @@ def main():
                                  col["validity"].data_ptr(), col["out"].data_ptr() if full and col["total_bytes"] else 0,
                                  col["total_bytes"] if full else 0, col["result"].data_ptr(), stream)
 
-    def timed(fn, steps, warmup):
-        """median / min of `steps` single executions of fn(), each between two HIP events"""
-        for _ in range(warmup):
-            fn()
-        torch.cuda.synchronize()
-        ms = []
-        for _ in range(steps):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            fn()
-            e1.record()
-            e1.synchronize()
-            ms.append(e0.elapsed_time(e1))
-        return {"median_ms": statistics.median(ms), "min_ms": min(ms), "steps": steps}
-
     moved = sum(col["total_bytes"] + 17 * n for col in cols)
     src = torch.empty(moved, dtype=torch.uint8, device=dev)
     dst = torch.empty(moved, dtype=torch.uint8, device=dev)
     res = {"documents": n, "input_bytes": int(offs[-1]), "paths": POINTERS, "verified_rows_per_column": min(VERIFY_ROWS, n),
            "string_columns": [{k: col[k] for k in ("pointer", "total_bytes", "n_valid", "n_other")} for col in cols],
            "least_bytes_moved": moved, "device": torch.cuda.get_device_name(0)}
-    # interleaved, so that drift of the box hits every leg alike
     legs = {"sizing": lambda: [gather(col, False) for col in cols], "full": lambda: [gather(col, True) for col in cols],
             "d2d_copy": lambda: dst.copy_(src), "select": lambda: shard.select(plan, stream)}
-    rounds = 3
-    runs = {k: [] for k in legs}
-    for r in range(rounds):
-        for name, fn in legs.items():
-            runs[name].append(timed(fn, max(3, a.steps // rounds), a.warmup if r == 0 else 1))
-    for name, rs in runs.items():
-        res[name] = {"median_ms": statistics.median(x["median_ms"] for x in rs), "min_ms": min(x["min_ms"] for x in rs),
-                     "steps": sum(x["steps"] for x in rs)}
+    res.update(opbench.measure(legs, a.steps, a.warmup))
     full, sizing = res["full"]["median_ms"], res["sizing"]["median_ms"]
     res["copy_kernels_ms"] = full - sizing  # (a difference of two medians, not a measurement of its own)
     res["full_over_d2d_copy"] = full / res["d2d_copy"]["median_ms"]
@@ -117,11 +81,7 @@ def main():
     res["sizing_over_full"] = sizing / full
     res["full_GBps_of_least_bytes"] = moved / (full * 1e-3) / 1e9
     res["one_long_string"] = "not measured"
-    os.makedirs(os.path.dirname(a.out), exist_ok=True)
-    with open(a.out, "w") as f:
-        json.dump(res, f, indent=1)
-        f.write("\n")
-    print(json.dumps(res))
+    opbench.write(a.out, res)
     plan.close()
     ctx.close()
 

@@ -21,7 +21,6 @@ result goes into the file under "fetch_ab".
 import argparse
 import json
 import os
-import statistics
 import subprocess
 import sys
 
@@ -75,27 +74,18 @@ def main():
     a = ap.parse_args()
     import torch
     import simdjson_java_amd as S
-    from simdjson_java_amd import sharding
     from tests import timecol_common as TC
+    from tools import opbench
     if not torch.cuda.is_available():
         raise SystemExit("tools/bench_timecol.py measures on a GPU: none is present")
-    dev = torch.device("cuda", 0)
     n = a.docs
     data, offs, texts = make_documents(n)
-    ctx = S.Context(0, 1 << 20)
-    shard = sharding.BatchShard(ctx, torch.frombuffer(bytearray(data), dtype=torch.uint8), offs, dev, index_ratio=4, string_ratio=1.0, tape_ratio=0.25)
+    dev, ctx, stream = opbench.device()
+    shard, _ = opbench.parsed_shard(ctx, dev, stream, data, offs, **opbench.RATIOS)
     del data
     select = S.SelectPlan(POINTERS)
-    # (handle 0 names the context's own stream in the C ABI, so torch's default stream cannot carry the events: a stream of its own)
-    side = torch.cuda.Stream(device=dev)
-    torch.cuda.set_stream(side)
-    stream = side.cuda_stream
-    assert stream != 0
-    shard.step(stream)
     types, values = shard.select(select, stream)
     torch.cuda.synchronize()
-    c = shard.check()
-    assert c["failed_documents"] == 0 and not getattr(shard, "rejected_steps", 0), c
     n_cols = len(POINTERS)
 
     # ---- what the generator made: per column the cells, their values at MICRO and the counts
@@ -179,21 +169,6 @@ def main():
         print(json.dumps({"traced": list(timed_legs), "calls_each": a.trace_legs, "counts": counts}))
         return
 
-    def timed(fn, steps, warmup):
-        """median / min of `steps` single executions of fn(), each between two HIP events"""
-        for _ in range(warmup):
-            fn()
-        torch.cuda.synchronize()
-        ms = []
-        for _ in range(steps):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            fn()
-            e1.record()
-            e1.synchronize()
-            ms.append(e0.elapsed_time(e1))
-        return {"median_ms": statistics.median(ms), "min_ms": min(ms), "steps": steps}
-
     # the least bytes a leg must move: per live cell 9 read and 8.125 (counting: 0.125) written, and the bytes of its strings
     kept_string_bytes = [sum(len(texts[col][r]) for r in kept_rows.tolist() if texts[col][r] is not None) for col in range(2)]
     least = {}
@@ -204,19 +179,11 @@ def main():
     dst = torch.empty_like(src)
     for name in legs:
         timed_legs[name + "_copy"] = lambda name=name: dst[:least[name] // 16].copy_(src[:least[name] // 16])
-    # interleaved, so that drift of the box hits every leg alike
-    rounds = 3
-    runs = {k: [] for k in timed_legs}
-    for r in range(rounds):
-        for name, fn in timed_legs.items():
-            runs[name].append(timed(fn, max(3, a.steps // rounds), a.warmup if r == 0 else 1))
     res = {"documents": n, "input_bytes": int(offs[-1]), "paths": POINTERS, "columns": n_cols, "device": torch.cuda.get_device_name(0), "unit": "us",
            "strings": strings, "string_bytes": string_bytes, "counts": counts, "least_bytes_moved": least,
            "verified": "every leg: the records equal the Python reference's verdicts on all rows; validity bits and data words equal the "
                        "reference's on a sample of %d rows; nothing written behind the live rows" % a.sample}
-    for name, rs in runs.items():
-        res[name] = {"median_ms": statistics.median(x["median_ms"] for x in rs), "min_ms": min(x["min_ms"] for x in rs), "steps": sum(x["steps"] for x in rs),
-                     "round_medians_ms": [x["median_ms"] for x in rs]}
+    res.update(opbench.measure(timed_legs, a.steps, a.warmup))
     for name in legs:
         res[name + "_over_copy"] = res[name]["median_ms"] / res[name + "_copy"]["median_ms"]
     res["one_field_over_string_gather"] = res["one_field"]["median_ms"] / res["string_gather"]["median_ms"]
@@ -227,11 +194,7 @@ def main():
         if done.returncode != 0:
             raise SystemExit("tools/ubench/timecol_ab failed with %d" % done.returncode)
         res["fetch_ab"] = json.loads(done.stdout.decode().strip().splitlines()[-1])
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as f:
-        json.dump(res, f, indent=1)
-        f.write("\n")
-    print(json.dumps(res))
+    opbench.write(a.out, res)
     plan.close()
     select.close()
     ctx.close()
