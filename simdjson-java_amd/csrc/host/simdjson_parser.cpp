@@ -2,6 +2,7 @@
 // C ABI, then the reference's sequential stage 2 (JsonIterator + TapeBuilder + Tape + number grammar)
 // re-implemented in C++.  Citations: /root/reference/src/main/java/org/simdjson/<file>:<lines>.
 #include "simdjson_parser.h"
+#include "batch_stages.h"
 #include "ondemand.h"
 #include "../sj_number.h"
 #include "../sj_bigdec.h"
@@ -10,7 +11,6 @@
 #include <stdlib.h>
 #include <locale.h>
 #include <algorithm>
-#include <chrono>
 #include <condition_variable>
 #include <functional>
 #include <mutex>
@@ -79,6 +79,20 @@ static JsonParsingException fail(int code, uint64_t pos = 0) {
     return JsonParsingException(code, m, pos);
 }
 
+// SimdJsonParser.stage1's exceptions from the engine's status bits, in the reference's order: Utf8Validator.validate
+// (Utf8Validator.java:165-167) runs first, then StructuralIndexer.index (StructuralIndexer.java:297-302)
+static void throwStage1Failure(uint32_t status) {
+    if (status & SJMI_ST_UTF8) throw fail(E_UTF8);
+    if (status & SJMI_ST_UNCLOSED) throw fail(E_UNCLOSED_STRING);
+    if (status & SJMI_ST_UNESCAPED) throw fail(E_UNESCAPED_CHARS);
+}
+
+// A string record is [be32 length][bytes] (IntegerUtils.toInt, IntegerUtils.java:5-10).  A string the reference's StringParser
+// would have thrown on is marked FF FF FF <SJMI_E_* code> by the kernel instead: a "length" of 0xFFFFFF00 or more, the code its
+// low byte.
+static inline uint32_t recordLength(const uint8_t* r) { return ((uint32_t)r[0] << 24) | ((uint32_t)r[1] << 16) | ((uint32_t)r[2] << 8) | r[3]; }
+static inline bool isFailedStringMarker(uint32_t length) { return length >= 0xFFFFFF00u; }
+
 void Tape::appendDouble(double v) {
     append(0, DOUBLE);
     uint64_t bits;
@@ -100,10 +114,9 @@ size_t Tape::computeNextIndex(size_t i) const {  // Tape.java:86-98
     }
 }
 
-std::string JsonValue::asString() const {  // JsonValue.java:79-89, IntegerUtils.toInt :5-10
+std::string JsonValue::asString() const {  // JsonValue.java:79-89
     const size_t off = (size_t)tape_->getValue(idx_);
-    const uint32_t len = ((uint32_t)sb_[off] << 24) | ((uint32_t)sb_[off + 1] << 16) | ((uint32_t)sb_[off + 2] << 8) | sb_[off + 3];
-    return std::string(reinterpret_cast<const char*>(sb_ + off + 4), len);
+    return std::string(reinterpret_cast<const char*>(sb_ + off + 4), recordLength(sb_ + off));
 }
 
 bool JsonValue::get(const std::string& name, JsonValue* out) const {  // JsonValue.java:91-107 (linear key scan)
@@ -111,7 +124,7 @@ bool JsonValue::get(const std::string& name, JsonValue* out) const {  // JsonVal
     const size_t end = tape_->getMatchingBraceIndex(idx_) - 1;
     while (i < end) {
         const size_t off = (size_t)tape_->getValue(i);
-        const uint32_t len = ((uint32_t)sb_[off] << 24) | ((uint32_t)sb_[off + 1] << 16) | ((uint32_t)sb_[off + 2] << 8) | sb_[off + 3];
+        const uint32_t len = recordLength(sb_ + off);
         const size_t val = tape_->computeNextIndex(i);
         i = tape_->computeNextIndex(val);
         if (len == name.size() && memcmp(sb_ + off + 4, name.data(), len) == 0) {
@@ -192,7 +205,7 @@ SimdJsonParser::SimdJsonParser(int capacity, int maxDepth, int device)
     : capacity_(capacity), maxDepth_(maxDepth), device_(device), stringBuffer_(3 * (size_t)capacity + 256),
       paddedBuffer_((size_t)capacity + PADDING),
       // (+ 2 per sub-batch of parseBatch: sub-batch j's count + sentinel may end at byteStart + byteLen + 2 j + 1)
-      indexes_((size_t)capacity + 2 + 2 * 64),
+      indexes_((size_t)capacity + 2 + 2 * MAX_SUB_BATCHES),
       walker_(paddedBuffer_.data(), indexes_.data(), indexes_.size(), (size_t)capacity + 8, maxDepth) {
     const int rc = sjmi_create(&ctx_, device, (uint64_t)capacity);
     if (rc != SJMI_OK) throw std::runtime_error("SimdJsonParser: no usable MI355X device (sjmi_create rc=" + std::to_string(rc) + "); there is no CPU fallback");
@@ -206,14 +219,14 @@ SimdJsonParser::SimdJsonParser(int capacity, int maxDepth, int device)
     // (the tape: the download of the GPU walker's result, sjmi_parse_document)
     pinned_[3] = sjmi_host_register(ctx_, walker_.tape().raw(), walker_.tape().capacity() * sizeof(uint64_t)) == SJMI_OK ? (void*)walker_.tape().raw() : nullptr;
     unsigned hw = std::thread::hardware_concurrency();
-    batchThreads_ = (int)(hw ? (hw > 64 ? 64 : hw) : 1);  // (tools/batch_e2e.py: 32 -> 64 threads 7.8 -> 6.5 ms per 100k documents, worse beyond)
+    batchThreads_ = (int)(hw ? (hw > 64 ? 64 : hw) : 1);  // (32 -> 64 threads: 7.8 -> 6.5 ms per 100k documents, worse beyond)
     if (const char* e = getenv("SJMI_PARSE_THREADS")) {
         const int v = atoi(e);
         if (v >= 1 && v <= 1024) batchThreads_ = v;
     }
-    if (const char* e = getenv("SJMI_PARSE_PIPELINE")) {  // sub-batches per batch (default: by size, 1..4)
+    if (const char* e = getenv("SJMI_PARSE_PIPELINE")) {  // sub-batches per batch (default: by size, 1..8: subBatchCount)
         const int v = atoi(e);
-        if (v >= 1 && v <= 64) batchPipeline_ = v;
+        if (v >= 1 && v <= (int)MAX_SUB_BATCHES) batchPipeline_ = v;
     }
 }
 
@@ -237,14 +250,13 @@ void SimdJsonParser::stage1(const uint8_t* buffer, size_t len) {
     uint64_t count = 0, total = 0, fei = 0;
     uint32_t status = 0, fec = 0;
     growStringBuffer(len + 4 * (len / 2 + 2) + 64);  // every string takes >= 2 source bytes
-    // stage 1 and the string records stage 2 will need, queued together (two synchronisations instead of four)
+    // stage 1 and the string records stage 2 will need, queued together in ONE engine call (one synchronisation when indexes and
+    // string buffer are page-locked: the kernels write them zero-copy)
     int rc = sjmi_stage1_unescape(ctx_, buffer, len, indexes_.data(), indexes_.size(), &count, &status,
                                   stringBuffer_.data(), stringBuffer_.size(), &total, &fei, &fec);
     if (rc != SJMI_OK) throw std::runtime_error(std::string("sjmi_stage1_unescape: ") + sjmi_last_error(ctx_));
     walker_.bitIndexes().setWriteIdx((size_t)count);
-    if (status & SJMI_ST_UTF8) throw fail(E_UTF8);                 // Utf8Validator.java:165-167 (checked first)
-    if (status & SJMI_ST_UNCLOSED) throw fail(E_UNCLOSED_STRING);  // StructuralIndexer.java:297-299
-    if (status & SJMI_ST_UNESCAPED) throw fail(E_UNESCAPED_CHARS); // :300-302
+    throwStage1Failure(status);
     stringBufferLen_ = (size_t)total;
 }
 
@@ -295,24 +307,19 @@ void SimdJsonParser::onDemandInit(const uint8_t* buffer, size_t len) {
     int rc = sjmi_stage1(ctx_, paddedBuffer_.data(), len, indexes_.data(), indexes_.size(), &count, &status);
     if (rc != SJMI_OK) throw std::runtime_error(std::string("sjmi_stage1: ") + sjmi_last_error(ctx_));
     walker_.bitIndexes().setWriteIdx((size_t)count);
-    if (status & SJMI_ST_UTF8) throw fail(E_UTF8);
-    if (status & SJMI_ST_UNCLOSED) throw fail(E_UNCLOSED_STRING);
-    if (status & SJMI_ST_UNESCAPED) throw fail(E_UNESCAPED_CHARS);
+    throwStage1Failure(status);
     if (!onDemand_) onDemand_.reset(new OnDemandJsonIterator(&walker_.bitIndexes()));
     onDemand_->init(paddedBuffer_.data(), len);
     onDemandReady_ = true;
 }
 
-// Batched parse.  The batch is cut into up to eight sub-batches of whole documents (about 8 MB or more each); two feeder threads, each with its
-// own engine context (= its own stream), take them alternately through the GPU: isolated stage 1 (per-document
-// verdicts and index ranges), the string records, and the string-buffer offset at which each document's records
-// begin.  So the upload of one sub-batch overlaps the kernels and downloads of the other (PCIe is full duplex), and
-// the host stage 2 of a finished sub-batch -- its documents spread over the worker pool by structural count, every
-// thread with a DocWalker building tapes back to back in a slab, then the slabs copied to their place in batchTape() --
-// overlaps the GPU part of the next.
-// Sub-batch j's indexes / string records are placed at fixed bases of the shared arrays (sized for the worst case:
-// one structural per byte, three string-buffer bytes per document byte), so with more than one sub-batch the string
-// buffer has unused gaps between them; tape STRING payloads are offsets into that one buffer.
+// Batched parse.  The batch is cut into up to eight sub-batches of whole documents (about 8 MiB or more each:
+// planSubBatches); two feeder threads, each with its own engine context (= its own stream), take them alternately through
+// the GPU (feedSubBatch).  So the upload of one sub-batch overlaps the kernels and downloads of the other (PCIe is full
+// duplex), and the host stage 2 of a finished sub-batch -- its documents spread over the worker pool by structural count
+// (planWalk), every thread with a DocWalker building tapes back to back in a slab (walkRange), then the slabs copied to their
+// place in batchTape() (placeSubBatch) -- overlaps the GPU part of the next.  batch_stages.h has the plan, the record of one
+// call and the hand-off between this thread and the feeders.
 void SimdJsonParser::parseBatch(const uint8_t* buffer, size_t totalLen, const uint64_t* docOffsets, size_t nDocs) {
     if (totalLen > (size_t)capacity_) throw fail(E_CAPACITY);
     // the offsets come across the public ABI: a non-monotonic pair or an offset past the end must be an argument
@@ -321,54 +328,47 @@ void SimdJsonParser::parseBatch(const uint8_t* buffer, size_t totalLen, const ui
     for (size_t k = 0; k < nDocs; ++k)
         if (docOffsets[k + 1] < docOffsets[k]) throw std::invalid_argument("parseBatch: doc_offsets not monotonic");
     if (nDocs && docOffsets[nDocs] > totalLen) throw std::invalid_argument("parseBatch: doc_offsets[n] > total_len");
-    // SJMI_PARSE_TIMING=1: phase times of every batch on stderr (tools/batch_e2e.py)
-    static const bool timing = getenv("SJMI_PARSE_TIMING") != nullptr;
-    using Clock = std::chrono::steady_clock;
-    const Clock::time_point t0 = Clock::now();
-    auto since = [&] { return std::chrono::duration<double, std::milli>(Clock::now() - t0).count(); };
-    if (!pool_) {
-        pool_.reset(new WorkerPool((size_t)batchThreads_));
-        lanes_.resize((size_t)batchThreads_);
-    }
-    const size_t T = (size_t)batchThreads_;
-
-    // sub-batches: whole documents, about equal bytes
-    size_t J = std::min<size_t>(8, totalLen / (8u << 20) + 1);
-    if (batchPipeline_ > 0) J = (size_t)batchPipeline_;
-    if (J > nDocs) J = nDocs ? nDocs : 1;
-    struct SubBatch {
-        size_t docLo = 0, docHi = 0, byteStart = 0, byteLen = 0, idxBase = 0, sbBase = 0, offBase = 0;
-        uint64_t count = 0, total = 0;
-        std::vector<uint64_t> rel;  // document offsets relative to byteStart
-        std::vector<size_t> cut;    // document ranges of the walk
-        size_t walkers = 0;
-        bool ready = false;
-        bool copied = false;        // its bytes are in paddedBuffer_ (padIfNeeded for the batch, sub-batch by sub-batch)
-        std::exception_ptr error;
-        double tGpu = 0, tWalk = 0;
-    };
-    std::vector<SubBatch> subs(J);
-    for (size_t j = 0; j < J; ++j) {
-        SubBatch& sb = subs[j];
-        sb.docLo = j == 0 ? 0 : subs[j - 1].docHi;
-        if (j + 1 == J) sb.docHi = nDocs;
-        else {
-            const uint64_t want = (uint64_t)totalLen * (j + 1) / J;
-            sb.docHi = (size_t)(std::lower_bound(docOffsets, docOffsets + nDocs, want) - docOffsets);
-            if (sb.docHi < sb.docLo) sb.docHi = sb.docLo;
+    static const bool timing = getenv("SJMI_PARSE_TIMING") != nullptr;  // phase times of every batch on stderr
+    BatchCall call{buffer, totalLen, docOffsets, nDocs, (size_t)batchThreads_,
+                   planSubBatches(docOffsets, nDocs, totalLen, subBatchCount(totalLen, nDocs, batchPipeline_))};
+    const size_t J = call.subs.size();
+    prepareBatch(call);
+    std::exception_ptr failure;
+    {
+        FeederHandOff handOff(J);  // (joins the feeders on every way out of this block)
+        handOff.start(J > 1 ? 2 : 1, [&](size_t feeder, size_t j) { feedSubBatch(call, feeder ? ctx2_ : ctx_, j); });
+        // padIfNeeded for the batch (SimdJsonParser.java:42-48), sub-batch by sub-batch: the GPU part of sub-batch 0 starts as
+        // soon as ITS bytes are in place instead of behind the whole batch's copy (647 MB: 9 ms of a 31 ms call)
+        memset(paddedBuffer_.data() + totalLen, 0, PADDING);
+        for (size_t j = 0; j < J; ++j) {
+            copyInSubBatch(call, j);
+            handOff.markCopied(j);
         }
-        sb.byteStart = nDocs ? (size_t)docOffsets[sb.docLo] : 0;
-        sb.byteLen = nDocs ? (size_t)docOffsets[sb.docHi] - sb.byteStart : 0;
-        sb.idxBase = sb.byteStart + 2 * j;       // count + sentinel <= byteLen + 1
-        sb.sbBase = 3 * sb.byteStart + 8 * j;    // 4 + L <= 2 (L + 2) for every string: total <= 2 byteLen
-        sb.offBase = sb.docLo + j;               // n + 1 offsets per sub-batch
+        call.tCopy = call.since();
+        for (size_t j = 0; j < J; ++j) {
+            handOff.awaitReady(j);  // (after a failure too: the feeders' remaining sub-batches are waited for)
+            if (!failure) failure = call.subs[j].error;
+            if (!failure) failure = walkSubBatch(call, j);
+            if (!failure) placeSubBatch(call, j);  // (while the GPU works on the next sub-batch)
+        }
     }
-    growStringBuffer(3 * totalLen + 8 * J + 64);
-    indexOffsets_.assign(nDocs + J + 1, 0);
-    docStringOffsets_.assign(nDocs + J + 1, 0);
-    docStatus_.assign(nDocs ? nDocs : 1, 0);
-    batchTapeOffsets_.assign(nDocs + 1, 0);
-    batchErrors_.assign(nDocs, 0);
+    if (failure) std::rethrow_exception(failure);
+    stringBufferLen_ = call.subs[J - 1].sbBase + (size_t)call.subs[J - 1].total;
+    if (timing) call.printTiming();
+}
+
+void SimdJsonParser::prepareBatch(const BatchCall& call) {
+    const size_t J = call.subs.size();
+    if (!pool_) {
+        pool_.reset(new WorkerPool(call.threads));
+        lanes_.resize(call.threads);
+    }
+    growStringBuffer(3 * call.totalLen + 8 * J + 64);
+    indexOffsets_.assign(call.nDocs + J + 1, 0);
+    docStringOffsets_.assign(call.nDocs + J + 1, 0);
+    docStatus_.assign(call.nDocs ? call.nDocs : 1, 0);
+    batchTapeOffsets_.assign(call.nDocs + 1, 0);
+    batchErrors_.assign(call.nDocs, 0);
     batchTapeLen_ = 0;
     if (!batchTape_) {
         batchTape_.reset(new uint64_t[1024]);
@@ -378,186 +378,115 @@ void SimdJsonParser::parseBatch(const uint8_t* buffer, size_t totalLen, const ui
         const int rc = sjmi_create(&ctx2_, device_, (uint64_t)capacity_);
         if (rc != SJMI_OK) throw std::runtime_error("SimdJsonParser: second engine context: sjmi_create rc=" + std::to_string(rc));
     }
-    if (pieces_.size() < J * T) pieces_.resize(J * T);
+    if (pieces_.size() < J * call.threads) pieces_.resize(J * call.threads);
+}
 
-    std::mutex m;
-    std::condition_variable readyCv, copiedCv;
-    // the GPU part of sub-batches j = first, first + 2, ... on one context
-    auto feed = [&](sjmi_ctx* ctx, size_t first) {
-        for (size_t j = first; j < J; j += 2) {
-            SubBatch& sb = subs[j];
-            {
-                std::unique_lock<std::mutex> g(m);
-                copiedCv.wait(g, [&] { return sb.copied; });
-            }
+// (on a feeder thread; an engine error is kept in the sub-batch for the caller's thread)
+void SimdJsonParser::feedSubBatch(BatchCall& call, sjmi_ctx* ctx, size_t j) {
+    SubBatch& sb = call.subs[j];
+    try {
+        const size_t n = sb.docs();
+        sb.rel.resize(n + 1);
+        for (size_t i = 0; i <= n; ++i) sb.rel[i] = call.docOffsets[sb.docLo + i] - sb.byteStart;
+        uint32_t status = 0;
+        // isolated mode: a document that fails stage 1 gets its own verdict and contributes no indexes, so
+        // the strings and trees of all other documents are exactly what they would be alone
+        int rc = sjmi_stage1_batch_isolated(ctx, paddedBuffer_.data() + sb.byteStart, sb.byteLen, sb.rel.data(), n,
+                                            indexes_.data() + sb.idxBase, sb.byteLen + 2, indexOffsets_.data() + sb.offBase,
+                                            docStatus_.data() + sb.docLo, &sb.count, &status);
+        if (rc != SJMI_OK) throw std::runtime_error(std::string("sjmi_stage1_batch_isolated: ") + sjmi_last_error(ctx));
+        uint64_t fei = 0;
+        uint32_t fec = 0;
+        rc = sjmi_unescape_batch(ctx, stringBuffer_.data() + sb.sbBase, 3 * sb.byteLen + 8, docStringOffsets_.data() + sb.offBase,
+                                 &sb.total, &fei, &fec);
+        if (rc != SJMI_OK) throw std::runtime_error(std::string("sjmi_unescape_batch: ") + sjmi_last_error(ctx));
+    } catch (...) {
+        sb.error = std::current_exception();
+    }
+    sb.tGpu = call.since();
+}
+
+// (on the pool: one thread copies ~25 GB/s)
+void SimdJsonParser::copyInSubBatch(const BatchCall& call, size_t j) {
+    const SubBatch& sb = call.subs[j];
+    const size_t span = (j + 1 == call.subs.size() ? call.totalLen : sb.byteStart + sb.byteLen) - sb.byteStart;  // (the last one: up to the batch's end)
+    if (!span) return;
+    const size_t parts = std::min<size_t>(call.threads, std::min<size_t>(8, span / (1u << 20) + 1));
+    pool_->run(parts, [&](size_t t) {
+        const size_t lo = sb.byteStart + span * t / parts, hi = sb.byteStart + span * (t + 1) / parts;
+        memcpy(paddedBuffer_.data() + lo, call.buffer + lo, hi - lo);
+    });
+}
+
+std::exception_ptr SimdJsonParser::walkSubBatch(BatchCall& call, size_t j) {
+    SubBatch& sb = call.subs[j];
+    sb.cut = planWalk(indexOffsets_.data() + sb.offBase, sb.docs(), sb.count, call.threads);
+    pool_->run(sb.walkers(), [&](size_t t) { walkRange(call, j, t); });
+    for (size_t t = 0; t < sb.walkers(); ++t)
+        if (lanes_[t].error) return lanes_[t].error;
+    return nullptr;
+}
+
+// (on the pool; what is thrown -- an allocation -- is kept in the thread's lane)
+void SimdJsonParser::walkRange(const BatchCall& call, size_t j, size_t t) {
+    const SubBatch& sb = call.subs[j];
+    const uint64_t* io = indexOffsets_.data() + sb.offBase;
+    const uint64_t* so = docStringOffsets_.data() + sb.offBase;
+    BatchLane& lane = lanes_[t];
+    TapeSlab& slab = pieces_[j * call.threads + t];
+    slab.used = 0;
+    lane.error = nullptr;
+    try {
+        const size_t lo = sb.cut[t], hi = sb.cut[t + 1];
+        // a structural makes at most two tape words (a number); the root adds two
+        const size_t room = 2 * (size_t)(io[hi] - io[lo]) + 8 * (hi - lo) + 8;
+        if (slab.room < room) {
+            slab.words.reset();
+            slab.words.reset(new uint64_t[room + room / 4]);
+            slab.room = room + room / 4;
+        }
+        if (!lane.walker) lane.walker.reset(new DocWalker(nullptr, nullptr, 0, 0, maxDepth_));
+        DocWalker& w = *lane.walker;
+        w.rebind(paddedBuffer_.data() + sb.byteStart, indexes_.data() + sb.idxBase, sb.byteLen + 2);
+        w.setStringBuffer(stringBuffer_.data());
+        for (size_t k = lo; k < hi; ++k) {
+            const size_t doc = sb.docLo + k;
+            w.resetForDocument((size_t)sb.rel[k], sb.sbBase + (size_t)so[k]);
+            w.tape().rebase(slab.words.get() + slab.used, slab.room - slab.used);
+            w.bitIndexes().window((size_t)io[k], (size_t)io[k + 1], (uint32_t)sb.rel[k]);
             try {
-                const size_t n = sb.docHi - sb.docLo;
-                sb.rel.resize(n + 1);
-                for (size_t i = 0; i <= n; ++i) sb.rel[i] = docOffsets[sb.docLo + i] - sb.byteStart;
-                uint32_t status = 0;
-                // isolated mode: a document that fails stage 1 gets its own verdict and contributes no indexes, so
-                // the strings and trees of all other documents are exactly what they would be alone
-                int rc = sjmi_stage1_batch_isolated(ctx, paddedBuffer_.data() + sb.byteStart, sb.byteLen, sb.rel.data(), n,
-                                                    indexes_.data() + sb.idxBase, sb.byteLen + 2,
-                                                    indexOffsets_.data() + sb.offBase, docStatus_.data() + sb.docLo,
-                                                    &sb.count, &status);
-                if (rc != SJMI_OK) throw std::runtime_error(std::string("sjmi_stage1_batch_isolated: ") + sjmi_last_error(ctx));
-                uint64_t fei = 0;
-                uint32_t fec = 0;
-                rc = sjmi_unescape_batch(ctx, stringBuffer_.data() + sb.sbBase, 3 * sb.byteLen + 8,
-                                         docStringOffsets_.data() + sb.offBase, &sb.total, &fei, &fec);
-                if (rc != SJMI_OK) throw std::runtime_error(std::string("sjmi_unescape_batch: ") + sjmi_last_error(ctx));
-            } catch (...) {
-                sb.error = std::current_exception();
+                throwStage1Failure(docStatus_[doc]);
+                w.walkDocument((size_t)sb.rel[k + 1]);
+                slab.used += w.tape().getCurrentIdx();
+            } catch (const JsonParsingException& e) {
+                batchErrors_[doc] = e.code();  // its partial tape is dropped
             }
-            sb.tGpu = since();
-            {
-                std::lock_guard<std::mutex> g(m);
-                sb.ready = true;
-            }
-            readyCv.notify_all();
+            batchTapeOffsets_[doc + 1] = slab.used;  // slab-relative until the slabs are placed
         }
-    };
-    std::thread feeders[2];
-    // The feeders wait for their sub-batches' bytes (copiedCv).  Whatever is thrown between here and the join below -- the
-    // pool, an allocation -- must not leave them waiting with joinable std::thread objects going out of scope (that is
-    // std::terminate): on the way out every sub-batch is marked copied, so the feeders run dry, and they are joined.
-    struct JoinFeeders {
-        std::thread* th;
-        std::vector<SubBatch>& subs;
-        std::mutex& m;
-        std::condition_variable& cv;
-        ~JoinFeeders() {
-            {
-                std::lock_guard<std::mutex> g(m);
-                for (SubBatch& sb : subs) sb.copied = true;
-            }
-            cv.notify_all();
-            for (int i = 0; i < 2; ++i)
-                if (th[i].joinable()) th[i].join();
-        }
-    } joinFeeders{feeders, subs, m, copiedCv};
-    feeders[0] = std::thread(feed, ctx_, (size_t)0);
-    if (J > 1) feeders[1] = std::thread(feed, ctx2_, (size_t)1);
-    // padIfNeeded for the batch (SimdJsonParser.java:42-48), on the pool (one thread copies ~25 GB/s), sub-batch by sub-batch:
-    // the GPU part of sub-batch 0 starts as soon as ITS bytes are in place instead of behind the whole batch's copy (647 MB:
-    // 9 ms of a 31 ms call)
-    memset(paddedBuffer_.data() + totalLen, 0, PADDING);
-    for (size_t j = 0; j < J; ++j) {
-        SubBatch& sb = subs[j];
-        const size_t span = (j + 1 == J ? totalLen : sb.byteStart + sb.byteLen) - sb.byteStart;  // (the last one: up to the batch's end)
-        const size_t parts = std::min<size_t>(T, std::min<size_t>(8, span / (1u << 20) + 1));
-        const std::function<void(size_t)> copyPart = [&](size_t t) {
-            const size_t lo = sb.byteStart + span * t / parts, hi = sb.byteStart + span * (t + 1) / parts;
-            memcpy(paddedBuffer_.data() + lo, buffer + lo, hi - lo);
-        };
-        if (span) pool_->run(parts, copyPart);
-        {
-            std::lock_guard<std::mutex> g(m);
-            sb.copied = true;
-        }
-        copiedCv.notify_all();
+    } catch (...) {
+        lane.error = std::current_exception();
     }
-    const double tCopy = since();
+}
 
-    const uint8_t* strings = stringBuffer_.data();
-    std::exception_ptr failure;
-    for (size_t j = 0; j < J; ++j) {
-        SubBatch& sb = subs[j];
-        {
-            std::unique_lock<std::mutex> g(m);
-            readyCv.wait(g, [&] { return sb.ready; });
-        }
-        if (sb.error && !failure) failure = sb.error;
-        if (failure) continue;  // (still wait for the feeders' remaining sub-batches)
-        // contiguous document ranges of about equal structural count, one per thread
-        const size_t n = sb.docHi - sb.docLo;
-        const uint64_t* io = indexOffsets_.data() + sb.offBase;
-        const uint64_t* so = docStringOffsets_.data() + sb.offBase;
-        size_t W = T;
-        const size_t minPerThread = 4096;  // structurals: below this a thread costs more than it walks
-        if (W > (size_t)sb.count / minPerThread + 1) W = (size_t)sb.count / minPerThread + 1;
-        if (W > n) W = n ? n : 1;
-        sb.walkers = W;
-        sb.cut.assign(W + 1, n);
-        sb.cut[0] = 0;
-        for (size_t t = 1; t < W; ++t) {
-            const uint64_t want = sb.count * t / W;
-            sb.cut[t] = (size_t)(std::lower_bound(io, io + n, want) - io);
-            if (sb.cut[t] < sb.cut[t - 1]) sb.cut[t] = sb.cut[t - 1];
-        }
-        const std::function<void(size_t)> walkRange = [&](size_t t) {
-            BatchLane& lane = lanes_[t];
-            TapeSlab& slab = pieces_[j * T + t];
-            slab.used = 0;
-            lane.error = nullptr;
-            try {
-                const size_t lo = sb.cut[t], hi = sb.cut[t + 1];
-                // a structural makes at most two tape words (a number); the root adds two
-                const size_t room = 2 * (size_t)(io[hi] - io[lo]) + 8 * (hi - lo) + 8;
-                if (slab.room < room) {
-                    slab.words.reset();
-                    slab.words.reset(new uint64_t[room + room / 4]);
-                    slab.room = room + room / 4;
-                }
-                if (!lane.walker) lane.walker.reset(new DocWalker(nullptr, nullptr, 0, 0, maxDepth_));
-                DocWalker& w = *lane.walker;
-                w.rebind(paddedBuffer_.data() + sb.byteStart, indexes_.data() + sb.idxBase, sb.byteLen + 2);
-                w.setStringBuffer(strings);
-                for (size_t k = lo; k < hi; ++k) {
-                    const size_t doc = sb.docLo + k;
-                    w.resetForDocument((size_t)sb.rel[k], sb.sbBase + (size_t)so[k]);
-                    w.tape().rebase(slab.words.get() + slab.used, slab.room - slab.used);
-                    w.bitIndexes().window((size_t)io[k], (size_t)io[k + 1], (uint32_t)sb.rel[k]);
-                    try {
-                        // SimdJsonParser.stage1 order: Utf8Validator.validate (:165-167), then StructuralIndexer.index (:297-302)
-                        if (docStatus_[doc] & SJMI_ST_UTF8) throw fail(E_UTF8);
-                        if (docStatus_[doc] & SJMI_ST_UNCLOSED) throw fail(E_UNCLOSED_STRING);
-                        if (docStatus_[doc] & SJMI_ST_UNESCAPED) throw fail(E_UNESCAPED_CHARS);
-                        w.walkDocument((size_t)sb.rel[k + 1]);
-                        slab.used += w.tape().getCurrentIdx();
-                    } catch (const JsonParsingException& e) {
-                        batchErrors_[doc] = e.code();  // its partial tape is dropped
-                    }
-                    batchTapeOffsets_[doc + 1] = slab.used;  // slab-relative until the slabs are placed
-                }
-            } catch (...) {
-                lane.error = std::current_exception();
-            }
-        };
-        pool_->run(W, walkRange);
-        for (size_t t = 0; t < W && !failure; ++t)
-            if (lanes_[t].error) failure = lanes_[t].error;
-        if (failure) continue;
-        // slabs -> batchTape(), in document order (while the GPU works on the next sub-batch)
-        std::vector<size_t> base(W + 1, batchTapeLen_);
-        for (size_t t = 0; t < W; ++t) base[t + 1] = base[t] + pieces_[j * T + t].used;
-        if (base[W] > batchTapeRoom_) {
-            const size_t room = base[W] + base[W] / 2 + 1024;
-            std::unique_ptr<uint64_t[]> grown(new uint64_t[room]);
-            if (batchTapeLen_) memcpy(grown.get(), batchTape_.get(), batchTapeLen_ * sizeof(uint64_t));
-            batchTape_ = std::move(grown);
-            batchTapeRoom_ = room;
-        }
-        const std::function<void(size_t)> place = [&](size_t t) {
-            const TapeSlab& slab = pieces_[j * T + t];
-            if (slab.used) memcpy(batchTape_.get() + base[t], slab.words.get(), slab.used * sizeof(uint64_t));
-            for (size_t k = sb.cut[t]; k < sb.cut[t + 1]; ++k) batchTapeOffsets_[sb.docLo + k + 1] += base[t];
-        };
-        pool_->run(W, place);
-        batchTapeLen_ = base[W];
-        sb.tWalk = since();
+void SimdJsonParser::placeSubBatch(BatchCall& call, size_t j) {
+    SubBatch& sb = call.subs[j];
+    const size_t W = sb.walkers();
+    const TapeSlab* slabs = pieces_.data() + j * call.threads;
+    std::vector<size_t> base(W + 1, batchTapeLen_);
+    for (size_t t = 0; t < W; ++t) base[t + 1] = base[t] + slabs[t].used;
+    if (base[W] > batchTapeRoom_) {
+        const size_t room = base[W] + base[W] / 2 + 1024;
+        std::unique_ptr<uint64_t[]> grown(new uint64_t[room]);
+        if (batchTapeLen_) memcpy(grown.get(), batchTape_.get(), batchTapeLen_ * sizeof(uint64_t));
+        batchTape_ = std::move(grown);
+        batchTapeRoom_ = room;
     }
-    for (std::thread& th : feeders)
-        if (th.joinable()) th.join();
-    if (failure) std::rethrow_exception(failure);
-    stringBufferLen_ = subs[J - 1].sbBase + (size_t)subs[J - 1].total;
-
-    if (timing) {
-        fprintf(stderr, "parseBatch %zu docs %zu B, %zu threads, %zu sub-batches: copy+pad done at %.2f ms;", nDocs, totalLen, T, J, tCopy);
-        for (size_t j = 0; j < J; ++j) fprintf(stderr, " [%zu] gpu %.2f walked+placed %.2f;", j, subs[j].tGpu, subs[j].tWalk);
-        fprintf(stderr, " done at %.2f ms\n", since());
-    }
+    pool_->run(W, [&](size_t t) {
+        if (slabs[t].used) memcpy(batchTape_.get() + base[t], slabs[t].words.get(), slabs[t].used * sizeof(uint64_t));
+        for (size_t k = sb.cut[t]; k < sb.cut[t + 1]; ++k) batchTapeOffsets_[sb.docLo + k + 1] += base[t];
+    });
+    batchTapeLen_ = base[W];
+    sb.tWalk = call.since();
 }
 
 // TapeBuilder.visitString (TapeBuilder.java:174-177): the record [be32 len][bytes] was produced on the GPU at
@@ -566,10 +495,8 @@ void DocWalker::visitString(uint32_t idx, size_t indexPos) {
     (void)idx;
     (void)indexPos;
     tape_.append(stringBufferIdx_, Tape::STRING);
-    const uint8_t* r = stringBuffer_.data() + stringBufferIdx_;
-    const uint32_t n = ((uint32_t)r[0] << 24) | ((uint32_t)r[1] << 16) | ((uint32_t)r[2] << 8) | r[3];
-    // a string the reference's StringParser would have thrown on is marked FF FF FF <SJMI_E_* code> by the kernel
-    if (n >= 0xFFFFFF00u) throw fail((int)(n & 0xFFu));
+    const uint32_t n = recordLength(stringBuffer_.data() + stringBufferIdx_);
+    if (isFailedStringMarker(n)) throw fail((int)(n & 0xFFu));
     stringBufferIdx_ += 4 + (size_t)n;
 }
 

@@ -195,6 +195,7 @@ private:
 };
 
 class WorkerPool;  // simdjson_parser.cpp: the host threads of parseBatch
+struct BatchCall;  // batch_stages.h: one parseBatch call
 class OnDemandJsonIterator;  // ondemand.h
 
 // SimdJsonParser.java:3-59
@@ -247,19 +248,33 @@ private:
     void growStringBuffer(size_t need);
 
     sjmi_ctx* ctx_ = nullptr;
-    sjmi_ctx* ctx2_ = nullptr;  // parseBatch: the second stream of the sub-batch pipeline (created on first use)
     int capacity_, maxDepth_, device_;
     std::vector<uint8_t> stringBuffer_, paddedBuffer_;
     std::vector<uint32_t> indexes_;  // BitIndexes storage (filled by the engine)
     DocWalker walker_;
     size_t stringBufferLen_ = 0;
+    int gpuWalk_ = -1;
+    void* pinned_[4] = {nullptr, nullptr, nullptr, nullptr};  // page-locked parser buffers (sjmi_host_register)
+    bool stagedInput_ = false;  // paddedBuffer_ is the engine's input staging (sjmi_set_input_staging)
+    std::unique_ptr<OnDemandJsonIterator> onDemand_;
+    bool onDemandReady_ = false;
+
+    // ---- parseBatch: its stages (each over the record of one call, batch_stages.h) and what it keeps between batches ----
+    void prepareBatch(const BatchCall& call);                     // the pool, the second context, room for the results
+    void feedSubBatch(BatchCall& call, sjmi_ctx* ctx, size_t j);  // the GPU part: isolated stage 1, then the string records
+    void copyInSubBatch(const BatchCall& call, size_t j);         // padIfNeeded for its bytes, on the pool
+    std::exception_ptr walkSubBatch(BatchCall& call, size_t j);   // the host stage 2 of its documents, on the pool
+    void walkRange(const BatchCall& call, size_t j, size_t t);    // ... of range t, into that range's slab
+    void placeSubBatch(BatchCall& call, size_t j);                // its slabs -> batchTape(), in document order
+    sjmi_ctx* ctx2_ = nullptr;  // the second stream of the sub-batch pipeline (created by the first batch that needs it)
+    int batchThreads_ = 1;      // host threads walking the documents of a batch (SJMI_PARSE_THREADS overrides)
+    int batchPipeline_ = 0;     // sub-batches per batch, 0 = by size (SJMI_PARSE_PIPELINE overrides)
     std::unique_ptr<uint64_t[]> batchTape_;  // (not a vector: grown without zero-filling, kept between batches)
     size_t batchTapeLen_ = 0, batchTapeRoom_ = 0;
     std::vector<uint64_t> batchTapeOffsets_, indexOffsets_, docStringOffsets_;
-    int gpuWalk_ = -1;
-    int batchThreads_ = 1;  // host threads walking the documents of a batch (SJMI_PARSE_THREADS overrides)
-    int batchPipeline_ = 0;  // sub-batches per batch, 0 = by size (SJMI_PARSE_PIPELINE overrides)
-    // kept between batches: a walker per batch thread, and per (sub-batch, thread) the slab its tapes are built in
+    std::vector<uint32_t> docStatus_;
+    std::vector<int32_t> batchErrors_;
+    // a walker per batch thread, and per (sub-batch, thread) the slab its tapes are built in
     struct BatchLane {
         std::unique_ptr<DocWalker> walker;
         std::exception_ptr error;
@@ -271,12 +286,6 @@ private:
     std::vector<BatchLane> lanes_;
     std::vector<TapeSlab> pieces_;
     std::unique_ptr<WorkerPool> pool_;  // created by the first parseBatch
-    std::vector<uint32_t> docStatus_;
-    void* pinned_[4] = {nullptr, nullptr, nullptr, nullptr};  // page-locked parser buffers (sjmi_host_register)
-    bool stagedInput_ = false;  // paddedBuffer_ is the engine's input staging (sjmi_set_input_staging)
-    std::vector<int32_t> batchErrors_;
-    std::unique_ptr<OnDemandJsonIterator> onDemand_;
-    bool onDemandReady_ = false;
 };
 
 }  // namespace org_simdjson

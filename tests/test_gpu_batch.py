@@ -275,3 +275,71 @@ def test_parse_batch_odd_shapes(monkeypatch):
                         assert O.Parsed(tapes[k], strings, 0, 0, 0).to_python() == want.to_python(), (pipeline, k)
         finally:
             p.close()
+
+
+_SEQUENCE = None
+
+
+def _shape_sequence():
+    """-> [(documents, packed bytes, offsets, the oracle's parse of every document)]: built once, shared by both runs."""
+    global _SEQUENCE
+    if _SEQUENCE is None:
+        rng = random.Random(83)
+        tiny = [b"[1]", b'{"a":"b\\n"}', b"tru"]
+        # a walk of several ranges: fat documents, and failing ones of every kind (grammar, strings, stage 1, empty) among them
+        parts = _small_docs(rng, 1400)
+        heavy = [b'{"id":%d,"a":%s,"b":%s}' % (k, parts[2 * k], parts[2 * k + 1]) for k in range(700)]
+        bad = [b"[1 1]", b'{"a" 1}', b"[1,2", b'["\\q"]', b'["\\uD800"]', b"[-]", b'["abc', b'{"k": "v', bytes([0x5B, 0x22, 0xC3, 0x22, 0x5D]),
+               b'["a\x01b"]', b"", b'"']
+        for i in range(60):
+            heavy.insert(rng.randrange(len(heavy)), bad[i % len(bad)])
+        heavy.append(b'["abc')
+        fixture = _small_docs(rng, 12) + [load_fixture("twitter.json").rstrip()] + _small_docs(rng, 12) + [b"[1,"]
+        _SEQUENCE = []
+        for docs in (tiny, heavy, [], fixture, tiny):
+            buf, offs = _pack(docs)
+            _SEQUENCE.append((docs, buf, offs, [O.parse(d + b"\n") for d in docs]))
+    return _SEQUENCE
+
+
+@pytest.mark.parametrize("pipeline", [None, "3"])
+def test_parse_batch_shapes_in_sequence_on_one_parser(monkeypatch, pipeline):
+    """One parser, batches of changing shape: three tiny documents, a batch whose walk is cut into several ranges (>= 3 x 4096
+    structurals in one sub-batch, failing documents in it), an empty batch, one large fixture among small documents, the first
+    batch again.  What a parser keeps between batches -- pool, lanes, slabs, the batch tape, the second context (with three
+    sub-batches: first needed by the second batch) -- is reused at another size and another sub-batch count: every document
+    equals the oracle's, and the last batch equals the first word for word."""
+    import simdjson_java_amd as S
+    sequence = _shape_sequence()
+    if pipeline is None:
+        monkeypatch.delenv("SJMI_PARSE_PIPELINE", raising=False)
+    else:
+        monkeypatch.setenv("SJMI_PARSE_PIPELINE", pipeline)
+    monkeypatch.setenv("SJMI_PARSE_THREADS", "4")
+    # the heavy batch as the parser cuts it: sub-batches of about equal bytes, whole documents
+    docs, buf, offs, want = sequence[1]
+    J = 1 if pipeline is None else int(pipeline)
+    assert len(buf) < 8 << 20  # (by size: one sub-batch)
+    cuts = [0] + [int(np.searchsorted(offs[:-1], len(buf) * (j + 1) // J, "left")) for j in range(J - 1)] + [len(docs)]
+    structurals = [sum(w.n_structurals for w in want[lo:hi] if not w.stage1_status) for lo, hi in zip(cuts, cuts[1:])]
+    assert max(structurals) >= 3 * 4096, structurals
+    assert sum(1 for w in want if w.error) >= 60 and sum(1 for w in want if w.stage1_status) >= 20
+    p = S.SimdJsonParser(capacity=max(len(b) for _, b, _, _ in sequence) + 64)
+    try:
+        results = []
+        for n, (docs, buf, offs, want) in enumerate(sequence):
+            tapes, strings, errors = p.parse_batch(buf, offs)
+            assert len(tapes) == len(docs)
+            for k, w in enumerate(want):
+                assert int(errors[k]) == w.error, (pipeline, n, k, docs[k][:40], int(errors[k]), w.error)
+                if not w.error:
+                    assert_tape_equal(tapes[k], strings, w, (pipeline, n, k))
+                    assert O.Parsed(tapes[k], strings, 0, 0, 0).to_python() == w.to_python(), (pipeline, n, k)
+            results.append(([None if t is None else np.array(t, copy=True) for t in tapes], bytes(strings), np.array(errors, copy=True)))
+        first, last = results[0], results[-1]
+        assert np.array_equal(first[2], last[2]) and len(first[1]) == len(last[1])
+        if pipeline is None:  # (one sub-batch: no gaps between the sub-batches' records, whose bytes are nobody's)
+            assert first[1] == last[1]
+        assert all((a is None and b is None) or np.array_equal(a, b) for a, b in zip(first[0], last[0]))
+    finally:
+        p.close()

@@ -19,7 +19,8 @@ SIM_DIR = os.path.join(ROOT, "tests", "host_sim")
 def walk():
     so = os.path.join(SIM_DIR, "libwalksim.so")
     deps = [os.path.join(SIM_DIR, "walk_sim.cpp"), os.path.join(ROOT, "simdjson-java_amd", "csrc", "host", "simdjson_parser.cpp"),
-            os.path.join(ROOT, "simdjson-java_amd", "csrc", "host", "simdjson_parser.h"), os.path.join(ROOT, "include", "sjmi.h")]
+            os.path.join(ROOT, "simdjson-java_amd", "csrc", "host", "simdjson_parser.h"),
+            os.path.join(ROOT, "simdjson-java_amd", "csrc", "host", "batch_stages.h"), os.path.join(ROOT, "include", "sjmi.h")]
     if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(d) for d in deps):
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-pthread", "-o", so, deps[0]])
     lib = C.CDLL(so)
