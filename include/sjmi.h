@@ -559,6 +559,25 @@ typedef struct sjmi_explode_plan sjmi_explode_plan;
 int sjmi_explode_plan_compile(const uint8_t* base_pointer, uint64_t base_len, const uint8_t* pointers, const uint64_t* pointer_offsets,
                               uint64_t n_paths, sjmi_explode_plan** out);
 void sjmi_explode_plan_destroy(sjmi_explode_plan* plan);
+/* A MEMBERS plan: JsonValue.objectIterator (JsonValue.java:170-194) over ONE object per document -- Arrow's map<utf8, struct>
+ * shape, for objects whose keys differ from document to document.  The same plan type, destroyed by
+ * sjmi_explode_plan_destroy, with the rules, limits and SJMI_ERR_ARG cases of sjmi_explode_plan_compile, except that n_paths is
+ * at most SJMI_EXPLODE_MEMBERS_MAX_PATHS: the key takes the 64th cell of a row.
+ * With such a plan sjmi_explode_batch_device gives document k rows iff its base value is an OBJECT ('{'): the members of the
+ * iterator chain -- from idx + 1, the key one word at pos, the value at pos + 1, the next member at Tape.computeNextIndex of the
+ * value, up to getMatchingBraceIndex - 1; never the 24-bit scope count --, the walk made to move forward and to stay inside the
+ * document whatever the words hold.  A base that is an array, a scalar, a string or MISSING gives 0 rows, and so does a failed
+ * document.  The members of nested objects are not rows.  Row row_offsets[k] + j is member j in tape order; DUPLICATE KEYS ARE
+ * SEPARATE ROWS, as the iterator yields them (unlike get()'s first-match rule), and the empty key "" is a key of length 0.
+ * The call writes n_paths + 1 columns strided by row_capacity: columns 0 .. n_paths - 1 are the element pointers evaluated with
+ * the member's VALUE as the root (the encoding unchanged, container cells carry tape indexes inside the document), column
+ * n_paths is the KEY: type '"', value (length << 32) | (record offset + 4) -- exactly a string cell, which
+ * sjmi_string_column_device, sjmi_dictionary_column_device and STRING filter terms take unchanged.  Everything else (the
+ * offsets always complete, the sizing call, the capacity rule, the plan slot, the scratch, the stream rules, the known limit) is
+ * as stated below.  An array plan behaves on every input as it did before members plans existed. */
+#define SJMI_EXPLODE_MEMBERS_MAX_PATHS (SJMI_SELECT_MAX_PATHS - 1u)
+int sjmi_explode_members_plan_compile(const uint8_t* base_pointer, uint64_t base_len, const uint8_t* pointers,
+                                      const uint64_t* pointer_offsets, uint64_t n_paths, sjmi_explode_plan** out);
 /* Inputs as sjmi_select_batch_device.  d_row_offsets (uint64[n_docs + 1]) is the exclusive prefix sum of the documents' row
  * counts and is ALWAYS complete: d_row_offsets[n_docs] is the total number of rows, whatever row_capacity is.  Columns are
  * strided by row_capacity: d_types[p * row_capacity + r] (uint8), d_values[p * row_capacity + r] (uint64).  Rows r >=
@@ -896,6 +915,48 @@ typedef struct sjmi_dict_result {
 int sjmi_dictionary_column_device(sjmi_ctx* ctx, const void* d_types, const void* d_values, uint64_t n_rows, const void* d_row_count,
                                   const void* d_string_buffer, void* d_indices, void* d_validity, uint64_t dict_capacity, void* d_dict_rows,
                                   void* d_dict_offsets, void* d_dict_bytes, uint64_t dict_byte_capacity, void* d_result, void* stream);
+
+/* ---- the key census: rows per dictionary entry and value type, counted on the device ----------------------------------------
+ * "Which keys are in here, and what types do they hold?"  A members explode gives a key column and a column of value types,
+ * sjmi_dictionary_column_device turns the keys into indices, and this call counts the rows per (index, type class): a group-by
+ * of counts, nothing else -- no sums, minima or maxima (csrc/census.hip, csrc/sj_census.h).
+ *
+ * INPUTS.  d_indices: int32[n_rows], 4-byte aligned -- the indices of sjmi_dictionary_column_device.  d_validity: its LSB-first
+ * bitmap (8-byte aligned words); NULL: every live row counts.  d_types: ONE uint8 column with the same rows, loaded as bytes at
+ * any alignment -- normally the "" element pointer of a members explode, but any types column is legal.  LIVE ROWS as in
+ * sjmi_arrow_columns_device: d_row_count == NULL: live = n_rows; else live = min(n_rows, *d_row_count), a uint64 in DEVICE
+ * memory (8-byte aligned) that the kernels read.  Rows at or above `live` are not read.
+ * CLASSES.  0 'l', 1 'd', 2 '"', 3 't' or 'f', 4 'n', 5 '[', 6 '{', 7 every other type byte (MISSING included).
+ * MEANING.  A live row r whose validity bit is set and whose index lies in [0, n_keys) adds 1 to d_counts[indices[r] *
+ * SJMI_CENSUS_CLASSES + class(types[r])]; d_counts is uint64[n_keys * SJMI_CENSUS_CLASSES], 8-byte aligned.  A valid live row
+ * whose index lies outside [0, n_keys) -- the unspecified indices under SJMI_DICT_OVERFLOW: negatives, INT32_MIN, INT32_MAX -- is
+ * counted in n_out_of_range and touches nothing else.  The record: n_rows = live, n_counted = the rows that were added,
+ * n_out_of_range, flags = 0; always complete.  Exactly d_counts[0, n_keys * 8) is written, every word, zeros included; nothing
+ * before or behind it is touched.  The outputs are exact integer sums: a function of the input alone.
+ * THE EMPTY CASES.  n_rows == 0, live == 0 and n_keys == 0 are legal: the counts are zeroed, the record is zero but for n_rows
+ * and, with n_keys == 0, n_out_of_range; no kernel is launched with an empty grid.
+ * ARGUMENTS.  SJMI_ERR_ARG: NULL d_result; NULL d_indices or d_types with n_rows > 0; NULL d_counts with n_keys > 0; n_keys >
+ * SJMI_DICT_MAX_ENTRIES; d_indices not 4-byte aligned; d_validity, d_row_count, d_counts or d_result not 8-byte aligned;
+ * n_rows >= 2^40.
+ * STREAM AND STATE.  Asynchronous on `stream` (NULL = the context's), no host synchronisation, no memset node: a kernel that
+ * clears the counts and the record, then ONE kernel over the rows, which the stream orders.  The context keeps NO state for
+ * this call -- no scratch, nothing to grow, nothing that two calls could share: census calls on one context need no ordering
+ * among themselves beyond what their buffers ask.
+ * KERNELS.  n_keys <= SJMI_CENSUS_LDS_KEYS: a workgroup takes chunks of 1024 rows in a grid stride, counts into 32-bit bins in
+ * LDS with LDS atomics (it takes fewer than 2^32 rows, so a bin cannot overflow) and adds its NON-ZERO bins to d_counts once,
+ * with agent-scope relaxed 64-bit atomic adds.  Larger n_keys: such adds go straight to d_counts, the rows of a wave that fall
+ * into the same bin merged into one add first.  The record's counts are summed the same way.  Nothing spins or waits for another workgroup; the counts are read across the kernel boundary
+ * only.
+ * KNOWN LIMIT.  Above SJMI_CENSUS_LDS_KEYS equal bins are merged inside a wave only: a column whose rows all fall into one bin
+ * still sends one add per 64 rows to one address, and is slower there than below the threshold (4.16). */
+#define SJMI_CENSUS_CLASSES 8u
+#define SJMI_CENSUS_LDS_KEYS 1024u         /* 8192 32-bit bins = 32 KiB of LDS per workgroup */
+typedef struct sjmi_census_result {
+    uint64_t n_rows, n_counted, n_out_of_range;
+    uint32_t flags, reserved;
+} sjmi_census_result;
+int sjmi_key_census_device(sjmi_ctx* ctx, const void* d_indices, const void* d_validity, const void* d_types, uint64_t n_rows,
+                           const void* d_row_count, uint64_t n_keys, void* d_counts, void* d_result, void* stream);
 
 /* Optional: page-lock caller-owned host memory that is passed to the host-buffer entry points again and again
  * (SimdJsonParser's padded input, index array and string buffer): H2D / D2H copies of pinned memory skip the

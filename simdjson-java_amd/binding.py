@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_HERE)
 _CSRC = os.path.join(_HERE, "csrc")
 _LIB = os.path.join(_HERE, "libsjmi.so")
-SOURCES = ["stage1.hip", "strings.hip", "batch.hip", "walk.hip", "coop_walk.hip", "masks.hip", "select.hip", "explode.hip", "ndjson.hip", "strcol.hip", "filter.hip", "arrowcol.hip", "timecol.hip", "dictcol.hip", "sjmi_api.hip", "host/simdjson_parser.cpp"]
+SOURCES = ["stage1.hip", "strings.hip", "batch.hip", "walk.hip", "coop_walk.hip", "masks.hip", "select.hip", "explode.hip", "ndjson.hip", "strcol.hip", "filter.hip", "arrowcol.hip", "timecol.hip", "dictcol.hip", "census.hip", "sjmi_api.hip", "host/simdjson_parser.cpp"]
 
 ST_UTF8, ST_UNCLOSED, ST_UNESCAPED, ST_CAPACITY, ST_INTERNAL = 1, 2, 4, 0x100, 0x200
 PADDING = 64
@@ -170,6 +170,7 @@ ABI = {
     "sjmi_select_batch_device": (I, (P, P, P, P, P, P, U64, P, P, P)),
     "sjmi_explode_plan_compile": (I, (P, U64, P, P, U64, PP)),
     "sjmi_explode_plan_destroy": (None, (P,)),
+    "sjmi_explode_members_plan_compile": (I, (P, U64, P, P, U64, PP)),
     "sjmi_explode_batch_device": (I, (P, P, P, P, P, P, U64, P, U64, P, P, P)),
     "sjmi_string_column_device": (I, (P, P, P, U64, P, P, P, P, U64, P, P)),
     "sjmi_filter_plan_compile": (I, (P, U64, P, U64, PP)),
@@ -178,6 +179,7 @@ ABI = {
     "sjmi_arrow_columns_device": (I, (P, P, U64, P, P, U64, U64, U64, P, P, U64, P, U64, P, P)),
     "sjmi_time_columns_device": (I, (P, P, U64, P, P, U64, U64, U64, P, P, P, U64, P, U64, P, P)),
     "sjmi_dictionary_column_device": (I, (P, P, P, U64, P, P, P, P, U64, P, P, P, U64, P, P)),
+    "sjmi_key_census_device": (I, (P, P, P, P, U64, P, U64, P, P, P)),
     "sjmi_host_register": (I, (P, P, U64)),
     "sjmi_set_input_staging": (I, (P, P, U64)),
     "sjmi_host_unregister": (I, (P, P)),
@@ -491,9 +493,10 @@ class Context:
 
     def explode_batch_device(self, plan, d_tape, d_tape_offsets, d_doc_errors, d_sb, n_docs, d_row_offsets, row_capacity, d_types,
                              d_values, stream=0):
-        """sjmi_explode_batch_device: the base array of `plan` (an ExplodePlan) of every document of a parsed batch as rows;
-        d_row_offsets (uint64, n_docs + 1 entries) is always complete, d_types (uint8) / d_values (uint64) are path-major
-        columns strided by row_capacity (both None / 0 with row_capacity 0: the offsets only).  Asynchronous on `stream`."""
+        """sjmi_explode_batch_device: the base array of `plan` (an ExplodePlan; a members plan: the base object) of every document
+        of a parsed batch as rows; d_row_offsets (uint64, n_docs + 1 entries) is always complete, d_types (uint8) / d_values
+        (uint64) are plan.n_columns column-major columns strided by row_capacity (both None / 0 with row_capacity 0: the offsets
+        only).  Asynchronous on `stream`."""
         self._check(lib().sjmi_explode_batch_device(self._h, plan._h, d_tape, d_tape_offsets, d_doc_errors, d_sb, n_docs, d_row_offsets,
                                                     row_capacity, d_types or None, d_values or None, stream), "sjmi_explode_batch_device")
 
@@ -566,6 +569,15 @@ class Context:
                                                         d_indices or None, d_validity or None, dict_capacity, d_dict_rows or None,
                                                         d_dict_offsets or None, d_dict_bytes or None, dict_byte_capacity, d_result or None,
                                                         stream), "sjmi_dictionary_column_device")
+
+    def key_census_device(self, d_indices, d_validity, d_types, n_rows, d_row_count, n_keys, d_counts, d_result, stream=0):
+        """sjmi_key_census_device: the rows per dictionary entry and value type.  d_indices (int32 [n_rows]) / d_validity (uint64
+        words, LSB first; None / 0: every live row counts) as sjmi_dictionary_column_device wrote them, d_types (uint8 [n_rows]) a
+        types column with the same rows; d_row_count (None / 0: every row) = a device uint64 that holds the live rows; d_counts
+        (uint64 [n_keys * 8]: entry-major, class-minor), d_result = device sjmi_census_result (4 x int64: live rows, n_counted,
+        n_out_of_range, flags in the low half of the fourth).  Asynchronous on `stream`."""
+        self._check(lib().sjmi_key_census_device(self._h, d_indices or None, d_validity or None, d_types or None, n_rows, d_row_count or None,
+                                                 n_keys, d_counts or None, d_result or None, stream), "sjmi_key_census_device")
 
     def ndjson_offsets(self, data):
         """sjmi_ndjson_offsets (host form) -> (doc_offsets np.uint64 [n_docs + 1], consumed, flags): the documents are the
@@ -662,12 +674,15 @@ class SelectPlan:
 
 class ExplodePlan:
     """sjmi_explode_plan: a base pointer and a set of element pointers (RFC 6901, str or bytes) compiled once, on the host (no
-    device needed), for Context.explode_batch_device / BatchShard.explode.  Raises ValueError for a malformed pointer or an
-    exceeded limit (include/sjmi.h: SJMI_SELECT_MAX_*)."""
+    device needed), for Context.explode_batch_device / BatchShard.explode.  members=True: a MEMBERS plan -- the base is an
+    object, a row is a member, and the member's key is one more column behind the element pointers' (n_columns = n_paths + 1).
+    Raises ValueError for a malformed pointer or an exceeded limit (include/sjmi.h: SJMI_SELECT_MAX_*,
+    SJMI_EXPLODE_MEMBERS_MAX_PATHS)."""
 
     MISSING = 0
 
-    def __init__(self, base, pointers):
+    def __init__(self, base, pointers, members=False):
+        self.members = bool(members)
         self.base = base.encode("utf-8") if isinstance(base, str) else bytes(base)
         self.pointers = [p.encode("utf-8") if isinstance(p, str) else bytes(p) for p in pointers]
         self.n_paths = len(self.pointers)
@@ -676,11 +691,16 @@ class ExplodePlan:
         offs = np.zeros(self.n_paths + 1, dtype=np.uint64)
         offs[1:] = np.cumsum([len(p) for p in self.pointers], dtype=np.uint64)
         self._h = C.c_void_p()
-        rc = lib().sjmi_explode_plan_compile(base_blob.ctypes.data, len(self.base), blob.ctypes.data, offs.ctypes.data, self.n_paths,
-                                             C.byref(self._h))
+        entry = "sjmi_explode_members_plan_compile" if self.members else "sjmi_explode_plan_compile"
+        rc = getattr(lib(), entry)(base_blob.ctypes.data, len(self.base), blob.ctypes.data, offs.ctypes.data, self.n_paths, C.byref(self._h))
         if rc != 0:
             self._h = C.c_void_p()
-            raise ValueError("sjmi_explode_plan_compile failed (rc=%d): a malformed JSON Pointer or a plan limit exceeded" % rc)
+            raise ValueError("%s failed (rc=%d): a malformed JSON Pointer or a plan limit exceeded" % (entry, rc))
+
+    @property
+    def n_columns(self):
+        """the columns an explode with this plan writes: the element pointers', and a members plan's key column behind them"""
+        return self.n_paths + (1 if self.members else 0)
 
     def close(self):
         if self._h:

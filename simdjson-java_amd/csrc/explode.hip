@@ -1,6 +1,7 @@
 // explode.hip -- one array per document of a parsed batch becomes a run of rows (include/sjmi.h, sjmi_explode_*):
 // the array is the value of a BASE pointer, and every path of an element plan is evaluated on every element, into one typed
-// column per path.  The walk is sj_select.h (sel_explode_count / sel_explode_rows, shared with the host simulation,
+// column per path.  A MEMBERS plan takes an OBJECT there: a row is a member, the element plan is evaluated on its
+// value, and its key is one more column behind the paths'.  The two kernels that walk are instantiated per mode.  The walk is sj_select.h (sel_explode_count / sel_explode_rows, shared with the host simulation,
 // tests/host_sim/explode_sim.cpp), the 16-lane form of its group primitives is Lanes16 of sj_group.h; this file is the plan object
 // and the kernels:
 //   k_explode_count       rows and the base array's tape index of every document
@@ -18,8 +19,11 @@
 struct sjmi_explode_plan {
     std::vector<sj_u64> image;  // [the base pointer as a plan of one path][the element plan]
     size_t base_words;
+    bool members;  // rows are the members of an object: the key is a column behind the element plan's
     uint64_t serial;  // never reused: how a context knows that the plan it holds on the device is this one
 };
+
+static_assert(SJMI_EXPLODE_MEMBERS_MAX_PATHS + 1 == SEL_MAX_PATHS, "a members plan's key takes the last cell of a row");
 
 namespace sjmi {
 
@@ -30,10 +34,11 @@ constexpr uint32_t EXP_BLOCK_DOCS = EXP_BLOCK / SEL_GROUP;
 constexpr uint32_t EXP_MAX_GRID = 16384;  // a workgroup loads the plan once and takes documents in a grid stride
 constexpr uint32_t EXP_SCAN_DOCS = 1024;  // documents per workgroup of the scan's passes
 // the rows a group buffers before it stores them: EXP_ROWS at most, and as many as EXP_CELLS cells hold for the plan's paths
-// (12 paths: 8 rows = 64-byte runs in a value column; 64 paths: one row)
+// and, under a members plan, the key (12 columns: 8 rows = 64-byte runs in a value column; 64 columns: one row)
 constexpr uint32_t EXP_ROWS = 8;
 constexpr uint32_t EXP_CELLS = 96;
 
+template <bool MEMBERS>
 __global__ __launch_bounds__(EXP_BLOCK) void k_explode_count(const sj_u64* __restrict__ plan_image, uint32_t image_words,
                                                               const sj_u64* __restrict__ tape,
                                                               const unsigned long long* __restrict__ tape_offsets,
@@ -54,7 +59,7 @@ __global__ __launch_bounds__(EXP_BLOCK) void k_explode_count(const sj_u64* __res
         uint32_t n = 0, base = 0;
         if (doc_errors[doc] == 0) {  // (a failed document's tape slot is never read: its contents are unspecified)
             const SelDoc d = sel_stage(g, tape + tape_offsets[doc], doc_words(tape_offsets, doc), sb, s);
-            n = sel_explode_count(g, plan, d, s, &base);
+            n = sel_explode_count<MEMBERS>(g, plan, d, s, &base);
         }
         if (g.lane == 0) {
             counts[doc] = n;
@@ -98,6 +103,7 @@ struct RowBuf {
     uint8_t types[EXP_CELLS];
 };
 
+template <bool MEMBERS>
 __global__ __launch_bounds__(EXP_BLOCK) void k_explode_rows(const sj_u64* __restrict__ plan_image, uint32_t image_words,
                                                              const sj_u64* __restrict__ tape,
                                                              const unsigned long long* __restrict__ tape_offsets,
@@ -109,7 +115,7 @@ __global__ __launch_bounds__(EXP_BLOCK) void k_explode_rows(const sj_u64* __rest
     __shared__ SelScratch scratch[EXP_BLOCK_DOCS];
     __shared__ RowBuf bufs[EXP_BLOCK_DOCS];
     const SelHeader* plan = stage_plan<EXP_BLOCK>(lds_plan, plan_image, image_words);
-    const uint32_t n_paths = plan->n_paths;
+    const uint32_t n_paths = plan->n_paths + (MEMBERS ? 1u : 0u);  // the columns: the key's cell lies behind the paths'
     Lanes16 g = group_lanes();
     SelScratch& s = scratch[threadIdx.x / SEL_GROUP];
     RowBuf& b = bufs[threadIdx.x / SEL_GROUP];
@@ -121,7 +127,7 @@ __global__ __launch_bounds__(EXP_BLOCK) void k_explode_rows(const sj_u64* __rest
         // the elements whose rows lie below the capacity: the others are neither walked nor stored
         const uint32_t limit = row_capacity - first < n ? (uint32_t)(row_capacity - first) : n;
         const SelDoc d = sel_stage(g, tape + tape_offsets[doc], doc_words(tape_offsets, doc), sb, s);
-        sel_explode_rows(g, plan, d, s, base, limit, [&](uint32_t j) {
+        sel_explode_rows<MEMBERS>(g, plan, d, s, base, limit, [&](uint32_t j) {
             const uint32_t q = j % rows;
             for (uint32_t p = g.lane; p < n_paths; p += SEL_GROUP) {
                 b.types[p * rows + q] = s.types[p];
@@ -147,11 +153,13 @@ __global__ __launch_bounds__(EXP_BLOCK) void k_explode_rows(const sj_u64* __rest
 
 }  // namespace
 
-const void* explode_plan_image(const sjmi_explode_plan* plan, size_t* bytes, size_t* base_bytes, uint64_t* serial, uint32_t* n_paths) {
+const void* explode_plan_image(const sjmi_explode_plan* plan, size_t* bytes, size_t* base_bytes, uint64_t* serial, uint32_t* n_cols,
+                               bool* members) {
     *bytes = plan->image.size() * sizeof(sj_u64);
     *base_bytes = plan->base_words * sizeof(sj_u64);
     *serial = plan->serial;
-    *n_paths = ((const SelHeader*)(plan->image.data() + plan->base_words))->n_paths;
+    *members = plan->members;
+    *n_cols = ((const SelHeader*)(plan->image.data() + plan->base_words))->n_paths + (plan->members ? 1u : 0u);
     return plan->image.data();
 }
 
@@ -160,7 +168,7 @@ size_t explode_workspace_bytes(uint64_t n_docs) {
     return 2 * ((n_docs * sizeof(uint32_t) + 63) / 64 * 64) + ((n_docs + EXP_SCAN_DOCS - 1) / EXP_SCAN_DOCS + 2) * sizeof(unsigned long long);
 }
 
-hipError_t explode_launch(const void* d_plan, size_t plan_bytes, size_t base_bytes, uint32_t n_paths, const void* d_tape,
+hipError_t explode_launch(const void* d_plan, size_t plan_bytes, size_t base_bytes, uint32_t n_cols, bool members, const void* d_tape,
                           const void* d_tape_offsets, const void* d_doc_errors, const void* d_string_buffer, uint64_t n_docs, void* d_ws,
                           void* d_row_offsets, uint64_t row_capacity, void* d_types, void* d_values, hipStream_t stream) {
     uint8_t* ws = static_cast<uint8_t*>(d_ws);
@@ -173,7 +181,8 @@ hipError_t explode_launch(const void* d_plan, size_t plan_bytes, size_t base_byt
     const sj_u64* base_plan = (const sj_u64*)d_plan;
     const sj_u64* elem_plan = base_plan + base_bytes / 8;
     if (n_docs) {
-        hipLaunchKernelGGL(k_explode_count, dim3(grid), dim3(EXP_BLOCK), base_bytes, stream, base_plan, (uint32_t)(base_bytes / 8),
+        hipLaunchKernelGGL(members ? k_explode_count<true> : k_explode_count<false>, dim3(grid), dim3(EXP_BLOCK), base_bytes, stream, base_plan,
+                           (uint32_t)(base_bytes / 8),
                            (const sj_u64*)d_tape, (const unsigned long long*)d_tape_offsets, (const int32_t*)d_doc_errors,
                            (const uint8_t*)d_string_buffer, n_docs, counts, bases);
         hipLaunchKernelGGL(k_explode_chunk_sums, dim3((unsigned)nchunks), dim3(1024), 0, stream, (const uint32_t*)counts, n_docs, sums);
@@ -182,11 +191,12 @@ hipError_t explode_launch(const void* d_plan, size_t plan_bytes, size_t base_byt
     if (n_docs)
         hipLaunchKernelGGL(k_explode_offsets, dim3((unsigned)nchunks), dim3(1024), 0, stream, (const uint32_t*)counts, n_docs,
                            (const unsigned long long*)sums, (unsigned long long*)d_row_offsets);
-    if (n_docs && n_paths && row_capacity) {
-        uint32_t rows = EXP_CELLS / n_paths;
+    if (n_docs && n_cols && row_capacity) {
+        uint32_t rows = EXP_CELLS / n_cols;
         rows = rows < 1 ? 1 : rows > EXP_ROWS ? EXP_ROWS : rows;
         const size_t elem_bytes = plan_bytes - base_bytes;
-        hipLaunchKernelGGL(k_explode_rows, dim3(grid), dim3(EXP_BLOCK), elem_bytes, stream, elem_plan, (uint32_t)(elem_bytes / 8),
+        hipLaunchKernelGGL(members ? k_explode_rows<true> : k_explode_rows<false>, dim3(grid), dim3(EXP_BLOCK), elem_bytes, stream, elem_plan,
+                           (uint32_t)(elem_bytes / 8),
                            (const sj_u64*)d_tape, (const unsigned long long*)d_tape_offsets, (const uint8_t*)d_string_buffer, n_docs,
                            (const uint32_t*)counts, (const uint32_t*)bases, (const unsigned long long*)d_row_offsets, row_capacity, rows,
                            (uint8_t*)d_types, (sj_u64*)d_values);
@@ -196,13 +206,13 @@ hipError_t explode_launch(const void* d_plan, size_t plan_bytes, size_t base_byt
 
 }  // namespace sjmi
 
-extern "C" {
-
-int sjmi_explode_plan_compile(const uint8_t* base_pointer, uint64_t base_len, const uint8_t* pointers, const uint64_t* pointer_offsets,
-                              uint64_t n_paths, sjmi_explode_plan** out) {
+// both kinds of plan: the rules are one, a members plan leaves the last cell to the key
+static int explode_compile(bool members, const uint8_t* base_pointer, uint64_t base_len, const uint8_t* pointers, const uint64_t* pointer_offsets,
+                           uint64_t n_paths, sjmi_explode_plan** out) {
     static std::atomic<uint64_t> next_serial{1};
     if (!out) return SJMI_ERR_ARG;
     *out = nullptr;
+    if (members && n_paths > SJMI_EXPLODE_MEMBERS_MAX_PATHS) return SJMI_ERR_ARG;
     if (base_len && !base_pointer) return SJMI_ERR_ARG;
     if (n_paths && (!pointer_offsets || (!pointers && pointer_offsets[n_paths] != pointer_offsets[0]))) return SJMI_ERR_ARG;
     sjmi_explode_plan* plan = new (std::nothrow) sjmi_explode_plan();
@@ -215,9 +225,22 @@ int sjmi_explode_plan_compile(const uint8_t* base_pointer, uint64_t base_len, co
     }
     plan->base_words = plan->image.size();
     plan->image.insert(plan->image.end(), elems.begin(), elems.end());
+    plan->members = members;
     plan->serial = next_serial.fetch_add(1);
     *out = plan;
     return SJMI_OK;
+}
+
+extern "C" {
+
+int sjmi_explode_plan_compile(const uint8_t* base_pointer, uint64_t base_len, const uint8_t* pointers, const uint64_t* pointer_offsets,
+                              uint64_t n_paths, sjmi_explode_plan** out) {
+    return explode_compile(false, base_pointer, base_len, pointers, pointer_offsets, n_paths, out);
+}
+
+int sjmi_explode_members_plan_compile(const uint8_t* base_pointer, uint64_t base_len, const uint8_t* pointers, const uint64_t* pointer_offsets,
+                                      uint64_t n_paths, sjmi_explode_plan** out) {
+    return explode_compile(true, base_pointer, base_len, pointers, pointer_offsets, n_paths, out);
 }
 
 void sjmi_explode_plan_destroy(sjmi_explode_plan* plan) { delete plan; }

@@ -301,41 +301,55 @@ SJ_HD void sel_document(G& g, const SelHeader* plan, const sj_u64* tape, uint32_
     sel_walk(g, plan, d, s, 1);
 }
 
-// ---- explode (csrc/explode.hip): one array per document becomes rows, an element plan is walked on every
-// element.  The array is the value of a BASE pointer, compiled as a plan of one path.
-// The staged document's base array: its elements by the iterator chain (JsonValue.arrayIterator :143-168 -- from idx + 1, by
-// Tape.computeNextIndex, to getMatchingBraceIndex - 1), never by the 24-bit scope count, which saturates.
-// -> the number of elements; *base = the array's tape index, 0 when the base is MISSING or no array (then no elements).
+// ---- explode (csrc/explode.hip): one container per document becomes rows, an element plan is walked on
+// every row's value.  The container is the value of a BASE pointer, compiled as a plan of one path.  MEMBERS = false: the base is
+// an ARRAY and a row is an element; MEMBERS = true: the base is an OBJECT and a row is a member -- its value is the root of the
+// element plan, its key one more cell behind the plan's paths.  The mode is a template parameter: the array form pays for no
+// run-time branch.
+// The staged document's base container: its rows by the iterator chain (JsonValue.arrayIterator :143-168 -- from idx + 1, by
+// Tape.computeNextIndex, to getMatchingBraceIndex - 1; JsonValue.objectIterator :170-194 -- the same chain, the key one word at
+// pos, the value at pos + 1, the next member behind the value), never by the 24-bit scope count, which saturates.
+// -> the number of rows; *base = the container's tape index, 0 when the base is MISSING or not of the mode's kind (then no rows).
 // s.types[0] / s.values[0] must be zero on entry.
-template <class G>
+template <bool MEMBERS = false, class G>
 SJ_HD uint32_t sel_explode_count(G& g, const SelHeader* base_plan, const SelDoc& d, SelScratch& s, uint32_t* base) {
     *base = 0;
     if (d.n < 2) return 0;
     sel_walk(g, base_plan, d, s, 1);
-    if (s.types[0] != '[') return 0;
+    if (s.types[0] != (MEMBERS ? '{' : '[')) return 0;
     const uint32_t v = (uint32_t)s.values[0];
     *base = v;
     const uint32_t end = sel_container_end(d, sel_word(d, s, v), v);
     uint32_t n = 0;
-    for (uint32_t pos = v + 1; pos < end; pos = sel_next(d, s, pos, end)) ++n;
+    if (MEMBERS) {  // (a key without a value in front of the closing word is no member: sel_match_round's rule)
+        for (uint32_t pos = v + 1; pos + 1 < end; pos = sel_next(d, s, pos + 1, end)) ++n;
+    } else {
+        for (uint32_t pos = v + 1; pos < end; pos = sel_next(d, s, pos, end)) ++n;
+    }
     return n;
 }
 
-// Every path of the element plan on the first `limit` elements of the array at tape index `base` of the staged document (the
-// elements whose rows fit the caller's columns: the others are not walked): for element j, row(j) is called with the element's
-// results in s.types / s.values (sel_emit's form: sel_finish is the caller's, when it stores the row).  row() runs in every
-// lane of the group and may use the group's primitives.
-template <class G, class Row>
+// Every path of the element plan on the first `limit` rows of the container at tape index `base` of the staged document (the
+// rows that fit the caller's columns: the others are not walked): for row j, row(j) is called with the results in s.types /
+// s.values (sel_emit's form: sel_finish is the caller's, when it stores the row).  MEMBERS: the member's key is cell
+// plan->n_paths (< SEL_MAX_PATHS there), a string cell in sel_emit's form like the others.  row() runs in every lane of the group
+// and may use the group's primitives.
+template <bool MEMBERS = false, class G, class Row>
 SJ_HD void sel_explode_rows(G& g, const SelHeader* plan, const SelDoc& d, SelScratch& s, uint32_t base, uint32_t limit, Row row) {
     const uint32_t end = sel_container_end(d, sel_word(d, s, base), base);
     uint32_t j = 0;
-    for (uint32_t pos = base + 1; pos < end && j < limit; pos = sel_next(d, s, pos, end), ++j) {
+    for (uint32_t pos = base + 1; pos + (MEMBERS ? 1u : 0u) < end && j < limit; pos = sel_next(d, s, pos + (MEMBERS ? 1u : 0u), end), ++j) {
+        const uint32_t v = pos + (MEMBERS ? 1u : 0u);  // the row's value
         for (uint32_t p = g.stride_first(); p < plan->n_paths; p += g.stride()) {  // MISSING until the walk says otherwise
             s.types[p] = 0;
             s.values[p] = 0;
         }
         g.fence();
-        sel_walk(g, plan, d, s, pos);
+        sel_walk(g, plan, d, s, v);
+        if (MEMBERS && g.stride_first() == 0) {  // the key: one word at pos, its record's offset
+            s.types[plan->n_paths] = '"';
+            s.values[plan->n_paths] = sel_word(d, s, pos) & 0x00FFFFFFFFFFFFFFull;
+        }
         g.fence();
         row(j);
     }

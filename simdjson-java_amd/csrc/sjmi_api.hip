@@ -975,8 +975,9 @@ int sjmi_explode_batch_device(sjmi_ctx* c, const sjmi_explode_plan* plan, const 
     if (!c || !plan || !d_row_offsets) return SJMI_ERR_ARG;
     size_t bytes, base_bytes;
     uint64_t serial;
-    uint32_t n_paths;
-    const void* image = sjmi::explode_plan_image(plan, &bytes, &base_bytes, &serial, &n_paths);
+    uint32_t n_paths;  // the columns of a row: a members plan's key among them
+    bool members;
+    const void* image = sjmi::explode_plan_image(plan, &bytes, &base_bytes, &serial, &n_paths, &members);
     if (n_docs && (!d_tape || !d_tape_offsets || !d_doc_errors || !d_string_buffer)) return SJMI_ERR_ARG;
     if (row_capacity && n_paths && (!d_types || !d_values)) return SJMI_ERR_ARG;
     if (n_paths && row_capacity > ~0ull / 8 / n_paths) return SJMI_ERR_ARG;
@@ -985,7 +986,7 @@ int sjmi_explode_batch_device(sjmi_ctx* c, const sjmi_explode_plan* plan, const 
     if (!upload_plan(c, c->explode_plan, image, bytes, serial, "explode plan") ||
         !grow_scratch(c, c->d_ws_explode, sjmi::explode_workspace_bytes(n_docs), "hipMalloc(ws_explode)"))
         return SJMI_ERR_HIP;
-    return fail(c, "explode launch", sjmi::explode_launch(c->explode_plan.d, bytes, base_bytes, n_paths, d_tape, d_tape_offsets, d_doc_errors,
+    return fail(c, "explode launch", sjmi::explode_launch(c->explode_plan.d, bytes, base_bytes, n_paths, members, d_tape, d_tape_offsets, d_doc_errors,
                                                           d_string_buffer, n_docs, c->d_ws_explode, d_row_offsets, row_capacity, d_types,
                                                           d_values, st))
                ? SJMI_ERR_HIP
@@ -1093,6 +1094,20 @@ int sjmi_dictionary_column_device(sjmi_ctx* c, const void* d_types, const void* 
     return fail(c, "dictionary column launch",
                 sjmi::dictcol_launch(d_types, d_values, n_rows, d_row_count, d_string_buffer, d_indices, d_validity, dict_capacity, d_dict_rows,
                                      d_dict_offsets, d_dict_bytes, dict_byte_capacity, d_result, c->d_ws_dict, st))
+               ? SJMI_ERR_HIP
+               : SJMI_OK;
+}
+
+int sjmi_key_census_device(sjmi_ctx* c, const void* d_indices, const void* d_validity, const void* d_types, uint64_t n_rows,
+                           const void* d_row_count, uint64_t n_keys, void* d_counts, void* d_result, void* stream) {
+    if (!c || !d_result || (n_rows && (!d_indices || !d_types)) || (n_keys && !d_counts)) return SJMI_ERR_ARG;
+    if (n_keys > SJMI_DICT_MAX_ENTRIES || n_rows >= (1ull << 40)) return SJMI_ERR_ARG;  // (one workgroup per 1024 rows at most)
+    if (((uintptr_t)d_indices & 3) || ((uintptr_t)d_validity & 7) || ((uintptr_t)d_row_count & 7) || ((uintptr_t)d_counts & 7) ||
+        ((uintptr_t)d_result & 7))
+        return SJMI_ERR_ARG;
+    if (fail(c, "hipSetDevice", hipSetDevice(c->device))) return SJMI_ERR_HIP;
+    hipStream_t st = stream_of(c, stream);  // (the call keeps no state in the context: no scratch to grow)
+    return fail(c, "key census launch", sjmi::census_launch(d_indices, d_validity, d_types, n_rows, d_row_count, n_keys, d_counts, d_result, st))
                ? SJMI_ERR_HIP
                : SJMI_OK;
 }

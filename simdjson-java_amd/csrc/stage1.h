@@ -377,13 +377,14 @@ hipError_t select_launch(const void* d_plan, size_t plan_bytes, const void* d_ta
 
 // ---- explode (explode.hip) ----
 // a compiled plan as the kernels read it: [the base pointer as a plan of one path: base_bytes][the element plan], the plan's
-// serial number and the paths of the element plan
-const void* explode_plan_image(const sjmi_explode_plan* plan, size_t* bytes, size_t* base_bytes, uint64_t* serial, uint32_t* n_paths);
+// serial number, the columns of a row (the paths of the element plan, and a members plan's key) and whether it is a members plan
+const void* explode_plan_image(const sjmi_explode_plan* plan, size_t* bytes, size_t* base_bytes, uint64_t* serial, uint32_t* n_cols,
+                               bool* members);
 // per-document scratch of one call: row counts, base tape indexes, the scan's chunk sums
 size_t explode_workspace_bytes(uint64_t n_docs);
-// k_explode_count, the scan into d_row_offsets[n_docs + 1], and (row_capacity != 0, n_paths != 0) k_explode_rows into the columns
-// types[p * row_capacity + r] / values[p * row_capacity + r]
-hipError_t explode_launch(const void* d_plan, size_t plan_bytes, size_t base_bytes, uint32_t n_paths, const void* d_tape,
+// k_explode_count, the scan into d_row_offsets[n_docs + 1], and (row_capacity != 0, n_cols != 0) k_explode_rows into the columns
+// types[p * row_capacity + r] / values[p * row_capacity + r]; `members` picks the kernels' instantiation
+hipError_t explode_launch(const void* d_plan, size_t plan_bytes, size_t base_bytes, uint32_t n_cols, bool members, const void* d_tape,
                           const void* d_tape_offsets, const void* d_doc_errors, const void* d_string_buffer, uint64_t n_docs, void* d_ws,
                           void* d_row_offsets, uint64_t row_capacity, void* d_types, void* d_values, hipStream_t stream);
 
@@ -450,5 +451,11 @@ size_t dictcol_workspace_bytes(uint64_t n_rows, uint64_t dict_capacity);
 hipError_t dictcol_launch(const void* d_types, const void* d_values, uint64_t n_rows, const void* d_row_count, const void* d_string_buffer,
                           void* d_indices, void* d_validity, uint64_t dict_capacity, void* d_dict_rows, void* d_dict_offsets, void* d_dict_bytes,
                           uint64_t dict_byte_capacity, void* d_result, void* d_ws, hipStream_t stream);
+
+// ---- the key census: rows per dictionary entry and value type (census.hip) ----
+// k_census_clear (the counts, the sjmi_census_result at d_result) and, with n_rows != 0, k_census_lds (n_keys <=
+// SJMI_CENSUS_LDS_KEYS) or k_census_global; no scratch.  d_validity and d_row_count may be NULL; d_row_count is read by the kernels
+hipError_t census_launch(const void* d_indices, const void* d_validity, const void* d_types, uint64_t n_rows, const void* d_row_count,
+                         uint64_t n_keys, void* d_counts, void* d_result, hipStream_t stream);
 
 }  // namespace sjmi

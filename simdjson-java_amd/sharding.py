@@ -219,7 +219,9 @@ class BatchShard:
         """The base array of `plan` (a binding.ExplodePlan) of every document of the shard as rows, every element pointer on
         every element: sjmi_explode_batch_device, queued on `stream` behind the step() that was queued there -- no host
         synchronisation.  -> (exp_row_offsets [n_docs + 1] int64, exp_types [n_paths, row_capacity] uint8, exp_values
-        [n_paths, row_capacity] int64), allocated once per (plan, row_capacity) and overwritten by every call.  The offsets
+        [n_paths, row_capacity] int64), allocated once per (plan, row_capacity) and overwritten by every call.  A MEMBERS plan
+        (ExplodePlan(..., members=True)) takes the base OBJECT's members as rows and has plan.n_columns = n_paths + 1 columns:
+        the element pointers on the member's value, and the member's key -- a string cell -- in the last one.  The offsets
         are always complete (exp_row_offsets[n_docs] = the total number of rows); rows at or behind row_capacity are not
         written.  row_capacity 0: the offsets only (the columns are empty).  As for select(), the outputs are valid only for
         a step check() has accepted, and check() queues the explode again behind a step it had to run again."""
@@ -227,11 +229,12 @@ class BatchShard:
         row_capacity = int(row_capacity)
         if self._exp_plan is not plan or self._exp_capacity != row_capacity:
             self.exp_row_offsets = torch.zeros(self.n_docs + 1, dtype=torch.int64, device=self.device)
-            self.exp_types = torch.zeros((plan.n_paths, row_capacity), dtype=torch.uint8, device=self.device)
-            self.exp_values = torch.zeros((plan.n_paths, row_capacity), dtype=torch.int64, device=self.device)
+            n_columns = getattr(plan, "n_columns", plan.n_paths)
+            self.exp_types = torch.zeros((n_columns, row_capacity), dtype=torch.uint8, device=self.device)
+            self.exp_values = torch.zeros((n_columns, row_capacity), dtype=torch.int64, device=self.device)
             self._exp_plan, self._exp_capacity = plan, row_capacity
         self._exp_pending = (plan, row_capacity, stream)
-        cells = plan.n_paths * row_capacity
+        cells = int(self.exp_types.numel())
         self.engine.explode_batch_device(plan, self.tape.data_ptr(), self.tape_offsets.data_ptr(), self.doc_errors.data_ptr(),
                                          self.sb.data_ptr(), self.n_docs, self.exp_row_offsets.data_ptr(), row_capacity,
                                          _ptr(self.exp_types, cells), _ptr(self.exp_values, cells), stream)
@@ -368,6 +371,63 @@ class BatchShard:
             indices.data_ptr() if n_rows else one.data_ptr(), _ptr(validity, n_rows), dict_capacity, _ptr(dict_rows, dict_capacity),
             dict_offsets.data_ptr(), _ptr(data, capacity), capacity, result.data_ptr(), stream)
         return indices, validity, dict_rows, dict_offsets, self._sized_bytes(call, result, 4, byte_capacity), result
+
+    def key_census(self, indices, validity, types, n_keys, row_count=None, stream=0):
+        """The rows per dictionary entry and value type: sjmi_key_census_device on the (indices [n_rows] int32, validity words) of
+        dictionary_column() -- validity None: every live row counts -- and a 1-D types uint8 tensor with the same rows, normally
+        the "" element pointer's row of a members explode.  n_keys is the number of dictionary entries (at most 2^20); row_count
+        as for dictionary_column().  -> (counts [n_keys, 8] int64: per entry the rows whose type is 'l', 'd', '"', 't' or 'f',
+        'n', '[', '{', anything else; result [4] int64 = live rows, n_counted, n_out_of_range, flags), new tensors every call,
+        every word of them written.  A valid row whose index is outside [0, n_keys) -- the indices of an overflowed dictionary
+        -- is counted in result[2] only.  Nothing synchronises.  Call it on a step that check() has accepted: like
+        dictionary_column(), it is not queued again behind a step that check() had to run again."""
+        import torch
+        n_rows, n_keys = int(indices.numel()), int(n_keys)
+        assert indices.dim() == 1 and indices.dtype == torch.int32 and indices.is_contiguous()
+        assert types.dim() == 1 and types.dtype == torch.uint8 and types.is_contiguous() and int(types.numel()) == n_rows
+        assert validity is None or (validity.dtype == torch.int64 and validity.is_contiguous() and int(validity.numel()) >= (n_rows + 63) // 64)
+        _check_row_count(row_count, types)
+        counts = torch.empty((n_keys, 8), dtype=torch.int64, device=self.device)
+        result = torch.empty(4, dtype=torch.int64, device=self.device)  # sjmi_census_result (every call writes all of it)
+        self.engine.key_census_device(_ptr(indices, n_rows), _ptr(validity, validity is not None and n_rows), _ptr(types, n_rows), n_rows,
+                                      _ptr(row_count, row_count is not None), n_keys, _ptr(counts, n_keys), result.data_ptr(), stream)
+        return counts, result
+
+    def discover_keys(self, base_pointer="", dict_capacity=4096, stream=0):
+        """"Which keys are in here, and what types do they hold?" for the object at base_pointer of every document: a members
+        explode with the one element pointer "" (a sizing call, then the full one), dictionary_column() on its key column and
+        key_census() on its type column, both with the explode's last row offset as the device row count.  A convenience with
+        host readbacks (the row total, the dictionary's byte size, the results), on a step that check() has accepted; the C
+        calls stay asynchronous.  -> ([(key bytes, [8 counts by class])] in the order of first occurrence, the row offsets
+        [n_docs + 1] (numpy), the sjmi_dict_result [6] and the sjmi_census_result [4] (numpy int64)).  Raises RuntimeError
+        naming dict_capacity when there are more distinct keys than it (SJMI_DICT_OVERFLOW)."""
+        import torch
+        from .binding import ExplodePlan
+        sync = lambda: torch.cuda.synchronize(self.device) if _on_gpu(self.device) else None
+        plan = ExplodePlan(base_pointer, [""], members=True)
+        try:
+            offs = self.explode(plan, 0, stream)[0]
+            sync()
+            total = int(offs[self.n_docs].cpu())
+            offs, types, values = self.explode(plan, total, stream)
+            row_count = offs[self.n_docs:]
+            indices, validity, _, dict_offsets, dict_bytes, dres = self.dictionary_column(types[1], values[1], dict_capacity, row_count=row_count,
+                                                                                           stream=stream)
+            sync()
+            d = dres.cpu().numpy()
+            if int(d[5]) & 1:
+                raise RuntimeError("discover_keys(%r): more distinct keys than dict_capacity = %d (SJMI_DICT_OVERFLOW)" % (base_pointer, dict_capacity))
+            n_keys = int(d[3])
+            counts, cres = self.key_census(indices, validity, types[0], n_keys, row_count=row_count, stream=stream)
+            sync()
+            ends, raw = dict_offsets[:n_keys + 1].cpu().numpy(), bytes(dict_bytes.cpu().numpy())
+            table = counts.cpu().numpy()
+            keys = [(raw[int(ends[j]):int(ends[j + 1])], [int(x) for x in table[j]]) for j in range(n_keys)]
+            return keys, offs.cpu().numpy(), d, cres.cpu().numpy()
+        finally:
+            self._exp_pending = None  # (the plan does not outlive this call: check() has nothing to queue again)
+            self._exp_plan = None
+            plan.close()
 
     def counts_tensor(self):
         """The per-shard row of the count gather, on the device, without a host copy:
