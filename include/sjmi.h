@@ -919,7 +919,8 @@ int sjmi_dictionary_column_device(sjmi_ctx* ctx, const void* d_types, const void
 /* ---- the key census: rows per dictionary entry and value type, counted on the device ----------------------------------------
  * "Which keys are in here, and what types do they hold?"  A members explode gives a key column and a column of value types,
  * sjmi_dictionary_column_device turns the keys into indices, and this call counts the rows per (index, type class): a group-by
- * of counts, nothing else -- no sums, minima or maxima (csrc/census.hip, csrc/sj_census.h).
+ * of counts, nothing else -- no sums, minima or maxima (csrc/census.hip, csrc/sj_census.h).  Those are
+ * sjmi_group_stats_device's, below.
  *
  * INPUTS.  d_indices: int32[n_rows], 4-byte aligned -- the indices of sjmi_dictionary_column_device.  d_validity: its LSB-first
  * bitmap (8-byte aligned words); NULL: every live row counts.  d_types: ONE uint8 column with the same rows, loaded as bytes at
@@ -957,6 +958,62 @@ typedef struct sjmi_census_result {
 } sjmi_census_result;
 int sjmi_key_census_device(sjmi_ctx* ctx, const void* d_indices, const void* d_validity, const void* d_types, uint64_t n_rows,
                            const void* d_row_count, uint64_t n_keys, void* d_counts, void* d_result, void* stream);
+
+/* ---- group statistics per dictionary key: count, sum, minimum and maximum, on the device ----------------------------------
+ * "Total and largest /payload/size per /type": sjmi_dictionary_column_device turns the key column into indices, and this call
+ * aggregates ONE (type, value) column with the same rows per index (csrc/groupstats.hip, csrc/sj_groupstats.h).
+ *
+ * INPUTS.  d_indices, d_validity, n_rows, d_row_count, n_keys exactly as sjmi_key_census_device takes them: int32 indices (4-byte
+ * aligned), the LSB-first bitmap or NULL for "every live row", live = min(n_rows, *d_row_count) read on the device.  d_types (uint8,
+ * any alignment) and d_values (uint64, 8-byte aligned) are ONE (type, value) column with the same rows: a row of sel_* or exp_*, or
+ * of a filter's compacted pair.  A row's value word is loaded only behind the type test, and only for 'l' and 'd': what lies
+ * behind any other type byte is never read.  Rows at or above `live` are not read.
+ * MEANING.  A valid live row with 0 <= index < n_keys belongs to that key, and its cell counts as long ('l'), as double ('d') or
+ * as other (every other type byte, MISSING included).  A valid row with any other index is counted in n_out_of_range and touches
+ * nothing else (its type and value are not read).  A 'd' cell of a key that is a NaN is counted in the record's n_nan and nowhere
+ * else -- not in n_other, not in n_grouped; such cells are outside the parser's output.  Longs and doubles are never mixed: a
+ * caller who wants one total adds the two sums and owns that rounding.
+ * OUTPUT.  d_stats: uint64[n_keys * SJMI_GROUP_STATS_WORDS], key-major, 8-byte aligned; per key the words
+ *     0 n_long  1 n_double  2 n_other  3 sum_long_lo  4 sum_long_hi  5 sum_double  6 min_long  7 max_long  8 min_double  9 max_double
+ * sum_long_hi:sum_long_lo is the 128-bit two's-complement sum of the key's 'l' cells: exact, no wrap, no overflow flag.  min_long /
+ * max_long are int64; a key without an 'l' cell has INT64_MAX / INT64_MIN.  sum_double, min_double and max_double are the bits of
+ * doubles.  min_double / max_double are exact under IEEE totalOrder restricted to non-NaN values, so -0.0 < +0.0; a key without a
+ * 'd' cell has +inf / -inf.  sum_double is the sum of the key's 'd' cells IN AN UNSPECIFIED ORDER: IT IS THE ONE OUTPUT WORD THAT
+ * MAY DIFFER BETWEEN TWO RUNS ON THE SAME INPUT (in its last bits: |sum_double - the exact sum| <= gamma(n_double - 1) * sum|x|,
+ * gamma(k) = k u / (1 - k u), u = 2^-53, for every order).  Infinite cells follow IEEE addition (+inf and -inf in one key: NaN);
+ * the sign of a zero sum is unspecified.  Every other word, and the record, is a function of the input alone.  The call writes
+ * exactly d_stats[0, n_keys * 10), every word, and nothing before or behind them.
+ * The record, sjmi_group_result, 40 bytes, always complete: n_rows = live, n_grouped = the rows that belong to a key (the sum of
+ * all n_long, n_double and n_other), n_out_of_range, n_nan, flags = 0.
+ * WHY n_rows < 2^32.  The 128-bit sum is accumulated as two 64-bit words: the unsigned sum of the cells' low 32 bits, each below
+ * 2^32, so below 2^32 * 2^32 = 2^64 for fewer than 2^32 rows; and the signed sum of their high 32 bits (v >> 32), each in [-2^31,
+ * 2^31), so of magnitude at most 2^31 * (2^32 - 1) < 2^63.  Neither can overflow, and sum = hi * 2^32 + lo exactly.  The same
+ * bound keeps a workgroup's 32-bit bin counts from overflowing.
+ * THE EMPTY CASES.  n_rows == 0, live == 0 and n_keys == 0 are legal: every key has zero counts and sums and the empty minima and
+ * maxima; no kernel is launched with an empty grid.
+ * ARGUMENTS.  SJMI_ERR_ARG: NULL d_result; NULL d_indices, d_types or d_values with n_rows > 0; NULL d_stats with n_keys > 0;
+ * n_keys > SJMI_DICT_MAX_ENTRIES; d_indices not 4-byte aligned; d_validity, d_values, d_row_count, d_stats or d_result not 8-byte
+ * aligned; n_rows >= 2^32.
+ * STREAM AND STATE.  Asynchronous on `stream` (NULL = the context's), no host synchronisation, no memset node: a kernel that
+ * writes every word's accumulation identity and the record, ONE kernel over the rows, and a kernel per key that finishes the
+ * words, which the stream orders.  The context keeps NO state for this call -- no scratch, nothing to grow: calls on one context
+ * need no ordering among themselves beyond what their buffers ask.  All buffers are device memory.
+ * KERNELS.  n_keys <= SJMI_GROUP_LDS_KEYS: a workgroup takes chunks of 1024 rows in a grid stride into bins of its own in LDS
+ * (three 32-bit counts and seven 64-bit words per key, 68 bytes) with LDS atomics, and sends the words of the keys it touched to
+ * d_stats once, with agent-scope relaxed atomics (64-bit add, double add, signed / unsigned minimum and maximum; the doubles'
+ * minima and maxima as unsigned integers on an order-preserving key of the bits).  Larger n_keys: such atomics go straight to
+ * d_stats, the rows of a wave that have the same key combined into one cell first.  Nothing spins or waits for another workgroup;
+ * d_stats is read across the kernel boundary only.
+ * KNOWN LIMIT.  Above SJMI_GROUP_LDS_KEYS equal keys are combined inside a wave only, as in the census.  Out of scope: several
+ * value columns per call, mean / variance (the caller divides), a compensated or reproducible double sum. */
+#define SJMI_GROUP_STATS_WORDS 10u
+#define SJMI_GROUP_LDS_KEYS 512u           /* 68 bytes of bins per key = 34 KiB of LDS per workgroup */
+typedef struct sjmi_group_result {
+    uint64_t n_rows, n_grouped, n_out_of_range, n_nan;
+    uint32_t flags, reserved;
+} sjmi_group_result;
+int sjmi_group_stats_device(sjmi_ctx* ctx, const void* d_indices, const void* d_validity, const void* d_types, const void* d_values,
+                            uint64_t n_rows, const void* d_row_count, uint64_t n_keys, void* d_stats, void* d_result, void* stream);
 
 /* Optional: page-lock caller-owned host memory that is passed to the host-buffer entry points again and again
  * (SimdJsonParser's padded input, index array and string buffer): H2D / D2H copies of pinned memory skip the

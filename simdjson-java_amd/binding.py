@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_HERE)
 _CSRC = os.path.join(_HERE, "csrc")
 _LIB = os.path.join(_HERE, "libsjmi.so")
-SOURCES = ["stage1.hip", "strings.hip", "batch.hip", "walk.hip", "coop_walk.hip", "masks.hip", "select.hip", "explode.hip", "ndjson.hip", "strcol.hip", "filter.hip", "arrowcol.hip", "timecol.hip", "dictcol.hip", "census.hip", "sjmi_api.hip", "host/simdjson_parser.cpp"]
+SOURCES = ["stage1.hip", "strings.hip", "batch.hip", "walk.hip", "coop_walk.hip", "masks.hip", "select.hip", "explode.hip", "ndjson.hip", "strcol.hip", "filter.hip", "arrowcol.hip", "timecol.hip", "dictcol.hip", "census.hip", "groupstats.hip", "sjmi_api.hip", "host/simdjson_parser.cpp"]
 
 ST_UTF8, ST_UNCLOSED, ST_UNESCAPED, ST_CAPACITY, ST_INTERNAL = 1, 2, 4, 0x100, 0x200
 PADDING = 64
@@ -180,6 +180,7 @@ ABI = {
     "sjmi_time_columns_device": (I, (P, P, U64, P, P, U64, U64, U64, P, P, P, U64, P, U64, P, P)),
     "sjmi_dictionary_column_device": (I, (P, P, P, U64, P, P, P, P, U64, P, P, P, U64, P, P)),
     "sjmi_key_census_device": (I, (P, P, P, P, U64, P, U64, P, P, P)),
+    "sjmi_group_stats_device": (I, (P, P, P, P, P, U64, P, U64, P, P, P)),
     "sjmi_host_register": (I, (P, P, U64)),
     "sjmi_set_input_staging": (I, (P, P, U64)),
     "sjmi_host_unregister": (I, (P, P)),
@@ -578,6 +579,16 @@ class Context:
         n_out_of_range, flags in the low half of the fourth).  Asynchronous on `stream`."""
         self._check(lib().sjmi_key_census_device(self._h, d_indices or None, d_validity or None, d_types or None, n_rows, d_row_count or None,
                                                  n_keys, d_counts or None, d_result or None, stream), "sjmi_key_census_device")
+
+    def group_stats_device(self, d_indices, d_validity, d_types, d_values, n_rows, d_row_count, n_keys, d_stats, d_result, stream=0):
+        """sjmi_group_stats_device: count, sum, minimum and maximum of ONE (type, value) column per dictionary entry.  d_indices /
+        d_validity / d_row_count / n_keys as key_census_device takes them; d_types (uint8 [n_rows]) and d_values (uint64
+        [n_rows]) one column with the same rows; d_stats (uint64 [n_keys * 10], key-major: n_long, n_double, n_other, sum_long_lo,
+        sum_long_hi, sum_double, min_long, max_long, min_double, max_double), d_result = device sjmi_group_result (5 x int64:
+        live rows, n_grouped, n_out_of_range, n_nan, flags in the low half of the fifth).  n_rows < 2^32.  Asynchronous on
+        `stream`."""
+        self._check(lib().sjmi_group_stats_device(self._h, d_indices or None, d_validity or None, d_types or None, d_values or None, n_rows,
+                                                  d_row_count or None, n_keys, d_stats or None, d_result or None, stream), "sjmi_group_stats_device")
 
     def ndjson_offsets(self, data):
         """sjmi_ndjson_offsets (host form) -> (doc_offsets np.uint64 [n_docs + 1], consumed, flags): the documents are the

@@ -1,7 +1,7 @@
 // sj_census.h -- the key census: how many rows every dictionary entry has of every value type (include/sjmi.h,
 // sjmi_key_census_device).  A count by (index, type class) over two finished columns with the same rows: the
 // int32 indices (and the validity bitmap) of sjmi_dictionary_column_device, and ONE column of type bytes -- normally the ""
-// element pointer of a members explode.  Sums, minima and maxima are not here.
+// element pointer of a members explode.  Sums, minima and maxima are not here: sj_groupstats.h (sjmi_group_stats_device) has them.
 //
 // The rows that count are [0, live), live = min(n_rows, *row_count) read HERE, on the device, where a row count is given.  A live
 // row r whose validity bit is set (every row without a bitmap) and whose index lies in [0, n_keys) adds 1 to counts[index *

@@ -1112,6 +1112,21 @@ int sjmi_key_census_device(sjmi_ctx* c, const void* d_indices, const void* d_val
                : SJMI_OK;
 }
 
+int sjmi_group_stats_device(sjmi_ctx* c, const void* d_indices, const void* d_validity, const void* d_types, const void* d_values,
+                            uint64_t n_rows, const void* d_row_count, uint64_t n_keys, void* d_stats, void* d_result, void* stream) {
+    if (!c || !d_result || (n_rows && (!d_indices || !d_types || !d_values)) || (n_keys && !d_stats)) return SJMI_ERR_ARG;
+    if (n_keys > SJMI_DICT_MAX_ENTRIES || n_rows >= (1ull << 32)) return SJMI_ERR_ARG;  // (the two halves of a 128-bit sum cannot overflow)
+    if (((uintptr_t)d_indices & 3) || ((uintptr_t)d_validity & 7) || ((uintptr_t)d_values & 7) || ((uintptr_t)d_row_count & 7) ||
+        ((uintptr_t)d_stats & 7) || ((uintptr_t)d_result & 7))
+        return SJMI_ERR_ARG;
+    if (fail(c, "hipSetDevice", hipSetDevice(c->device))) return SJMI_ERR_HIP;
+    hipStream_t st = stream_of(c, stream);  // (the call keeps no state in the context: no scratch to grow)
+    return fail(c, "group stats launch",
+                sjmi::groupstats_launch(d_indices, d_validity, d_types, d_values, n_rows, d_row_count, n_keys, d_stats, d_result, st))
+               ? SJMI_ERR_HIP
+               : SJMI_OK;
+}
+
 int sjmi_ndjson_offsets(sjmi_ctx* c, const uint8_t* buf, uint64_t len, uint64_t* doc_offsets, uint64_t offset_capacity,
                         uint64_t* n_docs, uint64_t* consumed, uint32_t* flags) {
     if (!c || (!buf && len) || (!doc_offsets && offset_capacity) || !n_docs || !consumed || !flags) return SJMI_ERR_ARG;

@@ -458,4 +458,11 @@ hipError_t dictcol_launch(const void* d_types, const void* d_values, uint64_t n_
 hipError_t census_launch(const void* d_indices, const void* d_validity, const void* d_types, uint64_t n_rows, const void* d_row_count,
                          uint64_t n_keys, void* d_counts, void* d_result, hipStream_t stream);
 
+// ---- group statistics per dictionary key: count, sum, min, max (groupstats.hip) ----
+// k_group_clear (the stats, the sjmi_group_result at d_result), with n_rows != 0 k_group_lds (n_keys <= SJMI_GROUP_LDS_KEYS) or
+// k_group_global, and with n_keys != 0 k_group_finish; no scratch.  d_validity and d_row_count may be NULL; d_row_count is read by
+// the kernels
+hipError_t groupstats_launch(const void* d_indices, const void* d_validity, const void* d_types, const void* d_values, uint64_t n_rows,
+                             const void* d_row_count, uint64_t n_keys, void* d_stats, void* d_result, hipStream_t stream);
+
 }  // namespace sjmi

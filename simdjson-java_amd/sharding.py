@@ -94,6 +94,28 @@ def _check_row_count(row_count, types):
         assert row_count.dtype == torch.int64 and row_count.numel() == 1 and row_count.device == types.device
 
 
+GROUP_STATS_WORDS = 10  # SJMI_GROUP_STATS_WORDS
+
+
+def decode_group_stats(stats):
+    """The stats of BatchShard.group_stats() on the host (a numpy array of shape [n_keys, 10], int64 or uint64) -> one dict per
+    key with Python values: n_long, n_double, n_other, sum_long (an int built from the 128 bits), sum_double, min_long, max_long,
+    min_double, max_double.  The minima and maxima of a class without a row are None."""
+    words = np.ascontiguousarray(stats).view(np.uint64).reshape(-1, GROUP_STATS_WORDS)
+    signed, floats = words.view(np.int64), words.view(np.float64)
+    out = []
+    for k in range(words.shape[0]):
+        n_long, n_double = int(words[k, 0]), int(words[k, 1])
+        out.append({
+            "n_long": n_long, "n_double": n_double, "n_other": int(words[k, 2]),
+            "sum_long": (int(signed[k, 4]) << 64) + int(words[k, 3]),
+            "sum_double": float(floats[k, 5]),
+            "min_long": int(signed[k, 6]) if n_long else None, "max_long": int(signed[k, 7]) if n_long else None,
+            "min_double": float(floats[k, 8]) if n_double else None, "max_double": float(floats[k, 9]) if n_double else None,
+        })
+    return out
+
+
 class BatchShard:
     """One rank's contiguous share of a batch of documents, resident on its device, and everything one step of the
     batched path needs: outputs sized once, then `step()` queues sjmi_parse_batch_device (isolated stage 1 -> string
@@ -392,6 +414,51 @@ class BatchShard:
         self.engine.key_census_device(_ptr(indices, n_rows), _ptr(validity, validity is not None and n_rows), _ptr(types, n_rows), n_rows,
                                       _ptr(row_count, row_count is not None), n_keys, _ptr(counts, n_keys), result.data_ptr(), stream)
         return counts, result
+
+    def group_stats(self, indices, validity, types, values, n_keys, row_count=None, stream=0):
+        """Count, sum, minimum and maximum of ONE column per dictionary entry: sjmi_group_stats_device on the (indices [n_rows]
+        int32, validity words) of dictionary_column() -- validity None: every live row counts -- and a 1-D (types uint8, values
+        int64) pair with the same rows: a row of sel_* / exp_*, or of filter()'s compacted pair.  n_keys is the number of
+        dictionary entries (at most 2^20), n_rows below 2^32; row_count as for dictionary_column().  -> (stats [n_keys, 10] int64:
+        per entry n_long, n_double, n_other, sum_long_lo, sum_long_hi, the bits of sum_double, min_long, max_long, the bits of
+        min_double and max_double -- decode_group_stats() reads them on the host --; result [5] int64 = live rows, n_grouped,
+        n_out_of_range, n_nan, flags), new tensors every call, every word of them written.  The long words are exact and the same
+        in every run; sum_double is summed in an unspecified order.  Nothing synchronises.  Call it on a step that check() has
+        accepted: like key_census(), it is not queued again behind a step that check() had to run again."""
+        import torch
+        n_rows, n_keys = int(indices.numel()), int(n_keys)
+        assert indices.dim() == 1 and indices.dtype == torch.int32 and indices.is_contiguous()
+        assert _column_pair(types, values) == n_rows
+        assert validity is None or (validity.dtype == torch.int64 and validity.is_contiguous() and int(validity.numel()) >= (n_rows + 63) // 64)
+        _check_row_count(row_count, types)
+        stats = torch.empty((n_keys, GROUP_STATS_WORDS), dtype=torch.int64, device=self.device)
+        result = torch.empty(5, dtype=torch.int64, device=self.device)  # sjmi_group_result (every call writes all of it)
+        self.engine.group_stats_device(_ptr(indices, n_rows), _ptr(validity, validity is not None and n_rows), _ptr(types, n_rows),
+                                       _ptr(values, n_rows), n_rows, _ptr(row_count, row_count is not None), n_keys, _ptr(stats, n_keys),
+                                       result.data_ptr(), stream)
+        return stats, result
+
+    def group_by_string(self, key_types, key_values, val_types, val_values, dict_capacity, row_count=None, stream=0):
+        """"Total and largest <value> per <key>": dictionary_column() on the 1-D key column (its string cells point into self.sb),
+        then group_stats() on the 1-D value column with the same rows.  A convenience with host readbacks (the dictionary's
+        size and bytes, the results), in the manner of discover_keys(), on a step that check() has accepted; the C calls stay
+        asynchronous.  -> ([(key bytes, decode_group_stats()'s dict)] in the order of first occurrence, the sjmi_dict_result [6]
+        and the sjmi_group_result [5] (numpy int64)).  Rows whose key cell is no string belong to no key.  Raises RuntimeError
+        naming dict_capacity when there are more distinct keys than it (SJMI_DICT_OVERFLOW)."""
+        import torch
+        sync = lambda: torch.cuda.synchronize(self.device) if _on_gpu(self.device) else None
+        indices, validity, _, dict_offsets, dict_bytes, dres = self.dictionary_column(key_types, key_values, dict_capacity, row_count=row_count,
+                                                                                       stream=stream)
+        sync()
+        d = dres.cpu().numpy()
+        if int(d[5]) & 1:
+            raise RuntimeError("group_by_string(): more distinct keys than dict_capacity = %d (SJMI_DICT_OVERFLOW)" % dict_capacity)
+        n_keys = int(d[3])
+        stats, gres = self.group_stats(indices, validity, val_types, val_values, n_keys, row_count=row_count, stream=stream)
+        sync()
+        ends, raw = dict_offsets[:n_keys + 1].cpu().numpy(), bytes(dict_bytes.cpu().numpy())
+        decoded = decode_group_stats(stats.cpu().numpy())
+        return [(raw[int(ends[j]):int(ends[j + 1])], decoded[j]) for j in range(n_keys)], d, gres.cpu().numpy()
 
     def discover_keys(self, base_pointer="", dict_capacity=4096, stream=0):
         """"Which keys are in here, and what types do they hold?" for the object at base_pointer of every document: a members
