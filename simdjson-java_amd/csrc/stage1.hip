@@ -369,7 +369,8 @@ struct Stage1Chain {
 // T = 0.15 ms + 7 ns * tiles -- the bubbles over the ~1000 resident workgroups.  Here both are overlapped:
 //
 //   iteration k of a wave:   C(k)    classify granule k (its first step was loaded during E(k-2)), publish its
-//                                    AGGREGATE; before the last step, request the PREFIX in front of granule k-1
+//                                    AGGREGATE; in the last step, request the ticket of granule k+1 and the PREFIX in
+//                                    front of granule k-1, both waited for at their first use behind the publication
 //                            E(k-1)  expand granule k-1's masks (parked in LDS) and store its indexes
 //                            park granule k's masks / offsets in the wave's LDS slice (20 bytes per block)
 //
@@ -540,11 +541,34 @@ stage1_body(const uint8_t* __restrict__ buf, sj_u64 len, uint32_t* __restrict__ 
 
     for (;;) {
         const bool have = cur < ngran;  // wave-uniform
-        uint32_t tk = 0;  // FAST mode: the ticket of the next iteration, requested before the last step below
+        // FAST mode: the ticket of the next iteration (lane 0) and the prefix in front of `prev`, as requested in the last step
+        // below.  Both stay per-lane values in VGPRs until their first use -- `nxt`, the top of the expansion -- so the waits
+        // for them stand there and not at the requests.
+        uint32_t tk = 0;
+        sj_u64 pfv = 0;
         sj_u64 pot[S], m[S];
         uint32_t meta[S];
         uint32_t wpar = 0, W0 = 0, WP = 0;
-        sj_u64 pf = 0;  // FAST mode: the prefix in front of `prev`, requested before the last step below
+        // To the compiler a value loaded from a wave-uniform address is uniform: it moves it to SGPRs at the load (the prefix) or
+        // lets one lane do the atomic for the wave and reads its result back at once (the ticket), and either way waits for
+        // the round trip where it is requested.  A lane offset it cannot see through (always 0) keeps both in VGPRs.
+        auto request_ticket = [&] {
+            if (lane == 0 && retire != 0) {
+                uint32_t z = 0;
+                asm volatile("" : "+v"(z));
+                tk = __hip_atomic_fetch_add(my_ticket + z, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+        };
+        // (Branch-free, and the ticket's branch stands behind the wait for the step's halo: behind a conditional request the
+        //  compiler no longer knows how many are in flight, and the next wait for an older load drains the queue.)
+        auto request_prefix = [&] {
+            uint32_t z = 0;
+            asm volatile("" : "+v"(z));
+            pfv = granule_load(&pfx[prev != NO_TILE && prev != 0 ? prev - 1 : 0u] + z);  // (no granule in front: read and ignored)
+        };
+        auto next_granule = [&] {
+            return retire != 0 ? ((uint32_t)__builtin_amdgcn_readfirstlane((int)tk) + ticket_base) * NC + cls : NO_TILE;
+        };
 
         // =================== C: classify granule `cur`, publish its aggregate ===================
         if (have) {
@@ -568,14 +592,17 @@ stage1_body(const uint8_t* __restrict__ buf, sj_u64 len, uint32_t* __restrict__ 
                 const sj_u64 halo = d.halo;
                 uint32_t plo[8], phi[8];  // the block's eight bit planes, bytes 0..31 / 32..63 (sj_block32.h)
                 sj_transpose32(w, plo, phi);
-                asm volatile("" ::: "memory");
+                asm volatile("" ::"v"(halo) : "memory");  // (the halo arrived with the block: its wait belongs here, in front of the requests)
                 if (s + 1 < S) load_step(d, buf, blk0 + (uint32_t)(s + 1) * 64u + (uint32_t)lane, nblocks, left_halo);
                 if (s == S - 1 && !safe) {
-                    // requested one step ahead of their use: late enough that granules are started in ticket order
-                    // (a ticket held through a whole slow iteration delays every granule behind it), early enough to
-                    // hide the round trips
-                    if (lane == 0 && retire != 0) tk = __hip_atomic_fetch_add(my_ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    if (prev != NO_TILE && prev != 0) pf = granule_load(&pfx[prev - 1]);
+                    // Requested in the last step: late enough that granules are started in ticket order (a ticket held through
+                    // a whole slow iteration delays every granule behind it), and the last step's algebra, the scans and the
+                    // aggregate's publication lie between the requests and the first use of either value, which is where the
+                    // waits stand: both round trips are hidden.  (Measured and dropped, profiles/r25/README.md: the ticket a
+                    // step earlier, so that the next granule's first step can be requested here as well and a wave always
+                    // has a document load in flight -- the earlier ticket changes nothing, the earlier load costs 0.5 %.)
+                    request_ticket();
+                    request_prefix();
                 }
                 asm volatile("" ::: "memory");
                 pot[s] = 0;
@@ -671,13 +698,7 @@ stage1_body(const uint8_t* __restrict__ buf, sj_u64 len, uint32_t* __restrict__ 
             __builtin_amdgcn_s_setprio(0);
         }
         uint32_t nxt = NO_TILE;
-        if (have) {
-            if (safe) {
-                nxt = take_ticket(my_ticket);
-            } else {
-                nxt = retire != 0 ? ((uint32_t)__builtin_amdgcn_readfirstlane((int)tk) + ticket_base) * NC + cls : NO_TILE;
-            }
-        }
+        if (have) nxt = safe ? take_ticket(my_ticket) : next_granule();  // (FAST: the wait for the ticket stands here)
         // first step of the next granule: in flight during the expansion below (clamped, so harmless without one)
         load_step(d, buf, nxt * (64u * S) + (uint32_t)lane, nblocks, left_halo);  // (NO_TILE wraps: any block will do)
 
@@ -691,6 +712,8 @@ stage1_body(const uint8_t* __restrict__ buf, sj_u64 len, uint32_t* __restrict__ 
                 if constexpr (safe) {
                     tile_lookback<LB_K>(agg, prev, lane, &pe, &cnt_in, res);
                 } else {
+                    sj_u64 pf = (sj_u64)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)pfv) |
+                                ((sj_u64)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(pfv >> 32)) << 32);
                     wait_prefix(&pfx[prev - 1], pf, [&] {
                         if (lane == 0) __hip_atomic_fetch_or(&res->status, SJMI_ST_INTERNAL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                     });
