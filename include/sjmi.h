@@ -1015,6 +1015,70 @@ typedef struct sjmi_group_result {
 int sjmi_group_stats_device(sjmi_ctx* ctx, const void* d_indices, const void* d_validity, const void* d_types, const void* d_values,
                             uint64_t n_rows, const void* d_row_count, uint64_t n_keys, void* d_stats, void* d_result, void* stream);
 
+/* ---- the top k rows of a column: ORDER BY a value, LIMIT k, on the device -------------------------------------------------
+ * "The 100 statuses with the most retweets", "the 50 latest events by created_at": the k rows with the largest (or smallest)
+ * value of ONE key column, in rank order, with the cells of any number of carried columns (csrc/toprows.hip, csrc/sj_toprows.h;
+ * DESIGN.md 4.18).
+ *
+ * INPUTS.  The key column: d_key_values, uint64[n_rows], 8-byte aligned; d_key_types (uint8, any alignment) and d_key_validity
+ * (LSB-first 64-bit words, 8-byte aligned), each of which may be NULL.  With types it is ONE (type, value) column: a row of sel_* or
+ * exp_*, or of a filter's compacted pair.  Without types and with validity it is a finished Arrow array: a row of
+ * sjmi_arrow_columns_device or sjmi_time_columns_device.  With both, both must pass; with neither, every live row is a number.
+ * The live rows are min(n_rows, *d_row_count), read on the device, exactly as sjmi_key_census_device takes them; rows at or above
+ * them are not read.  A row is read in the order validity word, type byte, value word, each only behind the test in front of it:
+ * the value word behind a type byte that makes no candidate is never read.
+ * MEANING.  Every live row is exactly one of: a CANDIDATE; NULL (its validity bit is clear, or its type byte is MISSING or 'n');
+ * OTHER (any other type byte that is no number of the kind); a NaN.  SJMI_TOP_LONG: with types only 'l' cells are candidates and
+ * 'd' cells are OTHER; without types every valid row is an int64.  SJMI_TOP_DOUBLE: 'd' cells are candidates, 'l' cells are
+ * converted as sjmi_arrow_columns_device converts them for a FLOAT64 field (round to nearest even; those that rounded are counted in
+ * n_inexact); without types every valid row is the bits of a double.  A NaN is counted in n_nan and nowhere else.  Doubles are
+ * ordered by IEEE totalOrder on the non-NaN values, -0.0 < +0.0, as sjmi_group_stats_device orders them.  flags:
+ * SJMI_TOP_SMALLEST takes the k smallest and ranks them smallest first.
+ * OUTPUT.  n_out = min(k, n_candidates).  d_rows, uint64[k]: d_rows[j], j < n_out, are the row indices in RANK order: by value,
+ * largest first (smallest first under the flag), equal values by ASCENDING ROW INDEX -- and which of the rows that tie at the cut
+ * are taken follows the same rule: the lowest row indices.  d_out_types[col * k + j] / d_out_values[col * k + j] are the cell of
+ * row d_rows[j] in carried column col (d_types / d_values, n_cols columns col_stride cells apart; n_cols may be 0): the layout of
+ * a filter's compacted pair with capacity k.  Entries at or behind n_out are not written, and nothing before or behind the
+ * buffers is touched.  The record, sjmi_top_result, nine uint64 words, always complete: n_rows = live, n_candidates, n_null,
+ * n_other, n_nan, n_inexact, n_out, kth_bits = the value word of the last returned row as the chosen kind (an int64, or the bits
+ * of a double; 0 when n_out == 0), flags = 0.  n_candidates + n_null + n_other + n_nan == n_rows.  THE WHOLE OUTPUT IS A FUNCTION
+ * OF THE INPUT ALONE.
+ * THE EMPTY CASES.  k == 0, n_rows == 0, live == 0 and a column without candidates are legal: n_out = 0 and nothing but the record
+ * is written; no kernel is launched with an empty grid.
+ * ARGUMENTS.  SJMI_ERR_ARG: NULL d_result; an unknown kind; a flag other than SJMI_TOP_SMALLEST; k > SJMI_TOP_MAX_K;
+ * n_rows >= 2^32; NULL d_key_values with n_rows > 0; NULL d_rows with k > 0; with n_cols > 0: col_stride < n_rows, or with k > 0 a
+ * NULL d_types, d_values, d_out_types or d_out_values; d_key_validity, d_key_values, d_row_count, d_values, d_rows, d_out_values
+ * or d_result not 8-byte aligned.
+ * STREAM AND STATE.  Asynchronous on `stream` (NULL = the context's), no host synchronisation, no memset node.  The context owns a
+ * scratch slot of its own for this call (48 KiB, a word per 1024 rows, 12 bytes per unit of k); when it has to grow, the device
+ * is drained first.  Calls on one context that share it must be ordered by the caller, as for sjmi_filter_columns_device.  All
+ * buffers are device memory.
+ * KERNELS.  An exact radix select on a 64-bit order-preserving unsigned key (a long with its sign bit flipped, a double's
+ * totalOrder key; complemented under SJMI_TOP_SMALLEST): a pass over the rows for the counts and the candidates' minimum and
+ * maximum key -- the bits above the highest bit in which they differ are common to all candidates and are skipped --, then per
+ * 11-bit digit below them (0 to 6 of them) a histogram pass (2048 32-bit LDS bins per workgroup, the non-zero ones added to the
+ * pass's histogram with agent-scope relaxed atomics) and one workgroup that picks the digit's bin; then the filter's three-pass
+ * scheme (counts per 1024 rows, their scan by one workgroup, the emit) takes the rows above the threshold and the first rows, in
+ * row order, equal to it; one workgroup sorts the n_out (key, row) pairs in LDS with a bitonic network under (key descending, row
+ * ascending) -- a strict total order -- and gathers the carried cells.  Nothing spins or waits for another workgroup; the scratch
+ * is read across kernel boundaries only.
+ * KNOWN LIMITS.  k <= SJMI_TOP_MAX_K: the final sort is one workgroup's.  n_rows < 2^32: a row index travels as 32 bits inside
+ * the kernels, and a histogram bin is 32 bits.  Every digit pass reads the key column again.  Out of scope: a full sort, an order
+ * across longs and doubles as real numbers, string keys, several sort columns, top k per group. */
+#define SJMI_TOP_LONG 1u
+#define SJMI_TOP_DOUBLE 2u
+#define SJMI_TOP_SMALLEST 1u               /* flags: the k smallest, smallest first */
+#define SJMI_TOP_MAX_K 2048u
+#define SJMI_TOP_RESULT_WORDS 9u
+typedef struct sjmi_top_result {
+    uint64_t n_rows, n_candidates, n_null, n_other, n_nan, n_inexact, n_out, kth_bits;
+    uint32_t flags, reserved;
+} sjmi_top_result;
+int sjmi_top_rows_device(sjmi_ctx* ctx, const void* d_key_types, const void* d_key_validity, const void* d_key_values, uint64_t n_rows,
+                         const void* d_row_count, uint32_t kind, uint32_t flags, uint64_t k, const void* d_types, const void* d_values,
+                         uint64_t n_cols, uint64_t col_stride, void* d_rows, void* d_out_types, void* d_out_values, void* d_result,
+                         void* stream);
+
 /* Optional: page-lock caller-owned host memory that is passed to the host-buffer entry points again and again
  * (SimdJsonParser's padded input, index array and string buffer): H2D / D2H copies of pinned memory skip the
  * driver's staging copy (3-4x faster for the ~1 MB transfers of a single-document parse).  Purely a performance

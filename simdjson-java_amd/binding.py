@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_HERE)
 _CSRC = os.path.join(_HERE, "csrc")
 _LIB = os.path.join(_HERE, "libsjmi.so")
-SOURCES = ["stage1.hip", "strings.hip", "batch.hip", "walk.hip", "coop_walk.hip", "masks.hip", "select.hip", "explode.hip", "ndjson.hip", "strcol.hip", "filter.hip", "arrowcol.hip", "timecol.hip", "dictcol.hip", "census.hip", "groupstats.hip", "sjmi_api.hip", "host/simdjson_parser.cpp"]
+SOURCES = ["stage1.hip", "strings.hip", "batch.hip", "walk.hip", "coop_walk.hip", "masks.hip", "select.hip", "explode.hip", "ndjson.hip", "strcol.hip", "filter.hip", "arrowcol.hip", "timecol.hip", "dictcol.hip", "census.hip", "groupstats.hip", "toprows.hip", "sjmi_api.hip", "host/simdjson_parser.cpp"]
 
 ST_UTF8, ST_UNCLOSED, ST_UNESCAPED, ST_CAPACITY, ST_INTERNAL = 1, 2, 4, 0x100, 0x200
 PADDING = 64
@@ -181,6 +181,7 @@ ABI = {
     "sjmi_dictionary_column_device": (I, (P, P, P, U64, P, P, P, P, U64, P, P, P, U64, P, P)),
     "sjmi_key_census_device": (I, (P, P, P, P, U64, P, U64, P, P, P)),
     "sjmi_group_stats_device": (I, (P, P, P, P, P, U64, P, U64, P, P, P)),
+    "sjmi_top_rows_device": (I, (P, P, P, P, U64, P, U32, U32, U64, P, P, U64, U64, P, P, P, P, P)),
     "sjmi_host_register": (I, (P, P, U64)),
     "sjmi_set_input_staging": (I, (P, P, U64)),
     "sjmi_host_unregister": (I, (P, P)),
@@ -589,6 +590,21 @@ class Context:
         `stream`."""
         self._check(lib().sjmi_group_stats_device(self._h, d_indices or None, d_validity or None, d_types or None, d_values or None, n_rows,
                                                   d_row_count or None, n_keys, d_stats or None, d_result or None, stream), "sjmi_group_stats_device")
+
+    def top_rows_device(self, d_key_types, d_key_validity, d_key_values, n_rows, d_row_count, kind, flags, k, d_types, d_values, n_cols,
+                        col_stride, d_rows, d_out_types, d_out_values, d_result, stream=0):
+        """sjmi_top_rows_device: the k rows with the largest (flags = TOP_SMALLEST: smallest) value of ONE key column, in rank
+        order, ties by ascending row.  d_key_types (uint8 [n_rows]; None / 0: every valid row is a number), d_key_validity (uint64
+        words, LSB first; None / 0: every live row is valid), d_key_values (uint64 [n_rows]); d_row_count (None / 0: every row) =
+        a device uint64 that holds the live rows; kind = TOP_LONG or TOP_DOUBLE; k <= TOP_MAX_K; d_types / d_values = n_cols
+        carried columns col_stride cells apart (None / 0 with n_cols 0); d_rows (uint64 [k]), d_out_types (uint8 [n_cols * k]),
+        d_out_values (uint64 [n_cols * k]), d_result = device sjmi_top_result (9 x int64: live rows, n_candidates, n_null,
+        n_other, n_nan, n_inexact, n_out, kth_bits, flags in the low half of the ninth).  n_rows < 2^32.  Asynchronous on
+        `stream`."""
+        self._check(lib().sjmi_top_rows_device(self._h, d_key_types or None, d_key_validity or None, d_key_values or None, n_rows,
+                                               d_row_count or None, kind, flags, k, d_types or None, d_values or None, n_cols, col_stride,
+                                               d_rows or None, d_out_types or None, d_out_values or None, d_result or None, stream),
+                    "sjmi_top_rows_device")
 
     def ndjson_offsets(self, data):
         """sjmi_ndjson_offsets (host form) -> (doc_offsets np.uint64 [n_docs + 1], consumed, flags): the documents are the

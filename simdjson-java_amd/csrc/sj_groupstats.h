@@ -52,6 +52,7 @@
 #include <stdint.h>
 
 #include "sj_fieldcol.h"
+#include "sj_okey.h"
 
 constexpr uint32_t GS_CHUNK_ROWS = 1024;  // rows of a chunk = threads of its workgroup
 constexpr uint32_t GS_WORDS = 10;         // SJMI_GROUP_STATS_WORDS
@@ -67,7 +68,6 @@ static_assert(GS_LDS_KEYS * GS_BIN_BYTES == 34 * 1024 && GS_LDS_KEYS * GS_BIN_BY
 
 typedef long long sj_i64;
 constexpr sj_i64 GS_I64_MAX = 0x7FFFFFFFFFFFFFFFll, GS_I64_MIN = -GS_I64_MAX - 1;
-constexpr sj_u64 GS_INF_BITS = 0x7FF0000000000000ull, GS_SIGN = 0x8000000000000000ull;
 
 enum GsWord : uint32_t { GS_N_LONG, GS_N_DOUBLE, GS_N_OTHER, GS_SUM_LO, GS_SUM_HI, GS_SUM_DOUBLE, GS_MIN_LONG, GS_MAX_LONG, GS_MIN_DOUBLE, GS_MAX_DOUBLE };
 
@@ -89,10 +89,7 @@ struct GsColumn {
 SJ_HD sj_u64 gs_live(const GsColumn& c) { return fc_live(c.n_rows, c.row_count); }
 SJ_HD sj_u64 gs_chunks(sj_u64 rows, uint32_t chunk_rows) { return fc_chunks(rows, chunk_rows); }
 
-// the order-preserving key of a double's bits and back: negative doubles have all bits flipped, the others the sign bit
-SJ_HD sj_u64 gs_okey(sj_u64 bits) { return bits ^ ((bits >> 63) ? ~0ull : GS_SIGN); }
-SJ_HD sj_u64 gs_okey_bits(sj_u64 key) { return key ^ ((key >> 63) ? GS_SIGN : ~0ull); }
-SJ_HD bool gs_is_nan(sj_u64 bits) { return (bits & ~GS_SIGN) > GS_INF_BITS; }
+// (gs_okey, gs_okey_bits and gs_is_nan -- the order-preserving key of a double's bits -- are sj_okey.h's)
 // a double <-> its bits (a copy of the bytes: no lvalue of the other type)
 SJ_HD double gs_double(sj_u64 bits) {
     double x;

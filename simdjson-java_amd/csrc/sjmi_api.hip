@@ -137,6 +137,7 @@ struct sjmi_ctx {
     DevBuf<void> d_ws_arrow;                 // sjmi_arrow_columns_device: a packed count word per field and chunk of rows (a slot of its own)
     DevBuf<void> d_ws_time;                  // sjmi_time_columns_device: a packed count word per field and chunk of rows (a slot of its own)
     DevBuf<void> d_ws_dict;                  // sjmi_dictionary_column_device: the hash table, a slot per row, the chunk counts, the compacted dictionary column (a slot of its own)
+    DevBuf<void> d_ws_top;                   // sjmi_top_rows_device: the select's state and histograms, a word per chunk of rows, k (key, row) pairs (a slot of its own)
     std::string err;
 };
 
@@ -1123,6 +1124,26 @@ int sjmi_group_stats_device(sjmi_ctx* c, const void* d_indices, const void* d_va
     hipStream_t st = stream_of(c, stream);  // (the call keeps no state in the context: no scratch to grow)
     return fail(c, "group stats launch",
                 sjmi::groupstats_launch(d_indices, d_validity, d_types, d_values, n_rows, d_row_count, n_keys, d_stats, d_result, st))
+               ? SJMI_ERR_HIP
+               : SJMI_OK;
+}
+
+int sjmi_top_rows_device(sjmi_ctx* c, const void* d_key_types, const void* d_key_validity, const void* d_key_values, uint64_t n_rows,
+                         const void* d_row_count, uint32_t kind, uint32_t flags, uint64_t k, const void* d_types, const void* d_values,
+                         uint64_t n_cols, uint64_t col_stride, void* d_rows, void* d_out_types, void* d_out_values, void* d_result, void* stream) {
+    if (!c || !d_result || (n_rows && !d_key_values) || (k && !d_rows)) return SJMI_ERR_ARG;
+    if ((kind != SJMI_TOP_LONG && kind != SJMI_TOP_DOUBLE) || (flags & ~SJMI_TOP_SMALLEST) || k > SJMI_TOP_MAX_K) return SJMI_ERR_ARG;
+    if (n_rows >= (1ull << 32)) return SJMI_ERR_ARG;  // (a row index travels as 32 bits, and so does a bin's count)
+    if (n_cols && (col_stride < n_rows || (k && (!d_types || !d_values || !d_out_types || !d_out_values)))) return SJMI_ERR_ARG;
+    if (((uintptr_t)d_key_validity & 7) || ((uintptr_t)d_key_values & 7) || ((uintptr_t)d_row_count & 7) || ((uintptr_t)d_values & 7) ||
+        ((uintptr_t)d_rows & 7) || ((uintptr_t)d_out_values & 7) || ((uintptr_t)d_result & 7))
+        return SJMI_ERR_ARG;
+    if (n_cols && col_stride > ~0ull / 8 / n_cols) return SJMI_ERR_ARG;  // (a column set is addressable)
+    if (fail(c, "hipSetDevice", hipSetDevice(c->device))) return SJMI_ERR_HIP;
+    hipStream_t st = stream_of(c, stream);
+    if (!grow_scratch(c, c->d_ws_top, sjmi::toprows_workspace_bytes(n_rows, k), "hipMalloc(ws_top)")) return SJMI_ERR_HIP;
+    return fail(c, "top rows launch", sjmi::toprows_launch(d_key_types, d_key_validity, d_key_values, n_rows, d_row_count, kind, flags, k, d_types,
+                                                           d_values, n_cols, col_stride, d_rows, d_out_types, d_out_values, d_result, c->d_ws_top, st))
                ? SJMI_ERR_HIP
                : SJMI_OK;
 }

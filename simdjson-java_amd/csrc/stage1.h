@@ -465,4 +465,14 @@ hipError_t census_launch(const void* d_indices, const void* d_validity, const vo
 hipError_t groupstats_launch(const void* d_indices, const void* d_validity, const void* d_types, const void* d_values, uint64_t n_rows,
                              const void* d_row_count, uint64_t n_keys, void* d_stats, void* d_result, hipStream_t stream);
 
+// ---- the top k rows of a key column: ORDER BY a value, LIMIT k (toprows.hip) ----
+// scratch of one call: the select's state, six histograms of 2048 bins, a word per chunk of 1024 rows, k (key, row) pairs
+size_t toprows_workspace_bytes(uint64_t n_rows, uint64_t k);
+// k_top_clear, with n_rows != 0 k_top_range, k_top_plan (the sjmi_top_result at d_result but for kth_bits) and, with n_rows != 0 and
+// k != 0, six times k_top_hist + k_top_pick, then k_top_mark, k_top_scan, k_top_emit and k_top_sort (d_rows, the carried cells,
+// kth_bits).  d_key_types, d_key_validity and d_row_count may be NULL; d_row_count is read by the kernels
+hipError_t toprows_launch(const void* d_key_types, const void* d_key_validity, const void* d_key_values, uint64_t n_rows, const void* d_row_count,
+                          uint32_t kind, uint32_t flags, uint64_t k, const void* d_types, const void* d_values, uint64_t n_cols,
+                          uint64_t col_stride, void* d_rows, void* d_out_types, void* d_out_values, void* d_result, void* d_ws, hipStream_t stream);
+
 }  // namespace sjmi

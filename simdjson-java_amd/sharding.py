@@ -95,6 +95,8 @@ def _check_row_count(row_count, types):
 
 
 GROUP_STATS_WORDS = 10  # SJMI_GROUP_STATS_WORDS
+TOP_KINDS = {"long": 1, "double": 2}  # SJMI_TOP_LONG, SJMI_TOP_DOUBLE
+TOP_SMALLEST, TOP_MAX_K, TOP_RESULT_WORDS = 1, 2048, 9  # SJMI_TOP_SMALLEST, SJMI_TOP_MAX_K, SJMI_TOP_RESULT_WORDS
 
 
 def decode_group_stats(stats):
@@ -437,6 +439,44 @@ class BatchShard:
                                        _ptr(values, n_rows), n_rows, _ptr(row_count, row_count is not None), n_keys, _ptr(stats, n_keys),
                                        result.data_ptr(), stream)
         return stats, result
+
+    def top_rows(self, key_types, key_values, k, kind="long", largest=True, key_validity=None, types=None, values=None, n_rows=None,
+                 row_count=None, stream=0):
+        """ORDER BY one column, LIMIT k: sjmi_top_rows_device on the 1-D key column (key_types uint8 or None, key_values int64) --
+        with types a row of sel_* / exp_* or of filter()'s compacted pair; without types and with key_validity (int64 words, LSB
+        first) a data row of arrow_columns() / timestamp_columns(); with both, both must pass.  kind "long": 'l' cells (without
+        types: every valid row) as int64; "double": 'd' cells and 'l' cells converted as arrow_columns() converts them (without
+        types: every valid row as the bits of a double), NaNs counted and left out.  k at most TOP_MAX_K = 2048; largest=False
+        takes the k smallest.  types / values: a 2-D [n_cols, stride] pair of columns to carry along, or None.  n_rows (default:
+        all of key_values; at most the stride, below 2^32) and row_count as for arrow_columns().  -> (rows [k] int64: the row
+        indices in rank order, equal values by ascending row, the ties at the cut decided the same way; out_types [n_cols, k]
+        uint8 and out_values [n_cols, k] int64: the carried cells of these rows, the layout of filter()'s compacted pair; result
+        [9] int64 = live rows, n_candidates, n_null, n_other, n_nan, n_inexact, n_out, kth_bits, flags), new tensors every call;
+        only the first n_out = min(k, n_candidates) entries of a row are written.  Everything is a function of the input alone.
+        Nothing synchronises.  Call it on a step that check() has accepted: like group_stats(), it is not queued again behind a
+        step that check() had to run again."""
+        import torch
+        assert kind in TOP_KINDS, "top_rows(): kind is 'long' or 'double'"
+        assert key_values.dim() == 1 and key_values.dtype == torch.int64 and key_values.is_contiguous()
+        n_rows, k = int(key_values.numel()) if n_rows is None else int(n_rows), int(k)
+        assert 0 <= n_rows <= int(key_values.numel()) and 0 <= k <= TOP_MAX_K
+        assert key_types is None or (key_types.dim() == 1 and key_types.dtype == torch.uint8 and key_types.is_contiguous() and
+                                     int(key_types.numel()) >= n_rows)
+        assert key_validity is None or (key_validity.dtype == torch.int64 and key_validity.is_contiguous() and
+                                        int(key_validity.numel()) >= (n_rows + 63) // 64)
+        _check_row_count(row_count, key_values)
+        n_cols = stride = 0
+        if types is not None:
+            n_cols, stride, _ = _column_set(types, values, n_rows)
+        rows = torch.empty(k, dtype=torch.int64, device=self.device)
+        out_types = torch.empty((n_cols, k), dtype=torch.uint8, device=self.device)
+        out_values = torch.empty((n_cols, k), dtype=torch.int64, device=self.device)
+        result = torch.empty(TOP_RESULT_WORDS, dtype=torch.int64, device=self.device)  # sjmi_top_result (every call writes all of it)
+        self.engine.top_rows_device(_ptr(key_types, key_types is not None and n_rows), _ptr(key_validity, key_validity is not None and n_rows),
+                                    _ptr(key_values, n_rows), n_rows, _ptr(row_count, row_count is not None), TOP_KINDS[kind],
+                                    0 if largest else TOP_SMALLEST, k, _ptr(types, n_cols), _ptr(values, n_cols), n_cols, stride, _ptr(rows, k),
+                                    _ptr(out_types, n_cols * k), _ptr(out_values, n_cols * k), result.data_ptr(), stream)
+        return rows, out_types, out_values, result
 
     def group_by_string(self, key_types, key_values, val_types, val_values, dict_capacity, row_count=None, stream=0):
         """"Total and largest <value> per <key>": dictionary_column() on the 1-D key column (its string cells point into self.sb),
