@@ -368,10 +368,12 @@ struct Stage1Chain {
 // predecessor + ~3 us of cross-XCD visibility and load latency); that kernel's time followed
 // T = 0.15 ms + 7 ns * tiles -- the bubbles over the ~1000 resident workgroups.  Here both are overlapped:
 //
-//   iteration k of a wave:   C(k)    classify granule k (its first step was loaded during E(k-2)), publish its
+//   iteration k of a wave:   C(k)    classify granule k (its first step arrives transposed, see E), publish its
 //                                    AGGREGATE; in the last step, request the ticket of granule k+1 and the PREFIX in
 //                                    front of granule k-1, both waited for at their first use behind the publication
-//                            E(k-1)  expand granule k-1's masks (parked in LDS) and store its indexes
+//                            E(k-1)  request the first step of granule k+1, expand granule k-1's masks (parked in LDS) into
+//                                    the staging slots, wait for that step and transpose it, THEN store the indexes (the
+//                                    last flush): the wave never waits for a load behind its own stores
 //                            park granule k's masks / offsets in the wave's LDS slice (20 bytes per block)
 //
 // so a granule's prefix is needed one whole classification after its aggregate went out, and it comes from the
@@ -436,6 +438,9 @@ constexpr int LB_K = 1;  // SAFE mode's look-back window = 64 * LB_K granules
 #define SJMI_S1_SORT_MIN 192 // the expansion's half masks are handed out by population (sorted_round) for a round of more than this
                              // many indexes per 4 KiB step (below: the sort costs more than it saves)
 #endif
+// dwords: a round's indexes are staged at their final ADDRESS modulo this, so that every wave store instruction of its flush covers
+// whole 128-byte lines (4, whole 16-byte quads only, was the form before round 27)
+constexpr uint32_t STORE_ALIGN = 32;
 // S = 4 KiB steps per granule, LDSW = bytes of LDS per wave
 template <int S>
 struct Parked {
@@ -538,6 +543,54 @@ stage1_body(const uint8_t* __restrict__ buf, sj_u64 len, uint32_t* __restrict__ 
     uint32_t err = 0;
     StepData d;  // the step being loaded / classified (single buffer: re-used as soon as it has been transposed)
     load_step(d, buf, cur * (64u * S) + (uint32_t)lane, nblocks, left_halo);
+    // The first step of a granule is consumed AHEAD of its classification: in front of the last flush of the expansion before
+    // it, where nothing but document loads is in flight, it is waited for and transposed into its planes.  gfx950 counts vector
+    // loads and stores with one counter and the flush's trip count is not known to the compiler, so a wait for a load BEHIND
+    // the flush is s_waitcnt vmcnt(0) -- a wait for the acknowledgement of the wave's own stores, at raised priority, once per
+    // granule.  With the planes kept across the flush and the parking, the first such wait of a classification is the second
+    // step's (requested at its top, as before), behind the first step's algebra.  (Measured and dropped, profiles/r27/README.md:
+    // the second step requested here as well, in front of the flush -- it loses what the moved wait wins, as the earlier load of
+    // round 25 did.)
+    uint32_t plo0[8], phi0[8];  // the eight bit planes of step 0 of granule `cur`
+    sj_u64 halo0;
+    auto consume_first_step = [&] {
+        const uint32_t w[16] = {d.q0.x, d.q0.y, d.q0.z, d.q0.w, d.q1.x, d.q1.y, d.q1.z, d.q1.w,
+                                d.q2.x, d.q2.y, d.q2.z, d.q2.w, d.q3.x, d.q3.y, d.q3.z, d.q3.w};
+        halo0 = d.halo;
+        sj_transpose32(w, plo0, phi0);
+        asm volatile("" ::"v"(halo0) : "memory");  // (the halo arrived with the block: its wait belongs here)
+    };
+    consume_first_step();
+    // the staging slots [g0, span) of the wave's LDS slice to gbp[g0 .. span): whole quads as global_store_dwordx4, the two boundary
+    // quads element-wise (flush_round, below)
+    auto store_staged = [&](uint32_t* gbp, uint32_t g0, uint32_t span) {
+        const uint32_t* stage = ws.stage;
+        uint32_t q0 = (uint32_t)lane;
+        asm volatile("" : "+v"(q0));  // (made here: as a loop invariant of the worker loop the lane's 64-bit store offset is spilled)
+        for (uint32_t qi = q0; qi * 4 < span; qi += 64) {
+            const uint4 v = reinterpret_cast<const uint4*>(stage)[qi];
+            const uint32_t lo = qi * 4;
+            if (lo >= g0 && lo + 4 <= span) {
+                // (16 KiB granules = large inputs: the index array is a stream nobody reads before it has left the
+                //  caches anyway -- streaming stores: +1.4 % on the headline, +1.5 % on twitter x1024; small documents keep
+                //  theirs in L2 for the kernels behind this one, and the batch flavour is 3.5 % SLOWER with them:
+                //  profiles/r6/README.md)
+                if constexpr (S == 4 && !BATCH) {
+                    typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
+                    u32x4_t nv = {v.x, v.y, v.z, v.w};
+                    __builtin_nontemporal_store(nv, reinterpret_cast<u32x4_t*>(gbp) + qi);
+                } else {
+                    reinterpret_cast<uint4*>(gbp)[qi] = v;
+                }
+            } else {
+                if (lo + 0 >= g0 && lo + 0 < span) gbp[lo + 0] = v.x;
+                if (lo + 1 >= g0 && lo + 1 < span) gbp[lo + 1] = v.y;
+                if (lo + 2 >= g0 && lo + 2 < span) gbp[lo + 2] = v.z;
+                if (lo + 3 >= g0 && lo + 3 < span) gbp[lo + 3] = v.w;
+            }
+        }
+        wave_lds_fence();
+    };
 
     for (;;) {
         const bool have = cur < ngran;  // wave-uniform
@@ -583,17 +636,28 @@ stage1_body(const uint8_t* __restrict__ buf, sj_u64 len, uint32_t* __restrict__ 
             bool halo_short = false;
 #pragma unroll
             for (int s = 0; s < S; ++s) {
-                // software pipeline with ONE buffer: step s was loaded during the algebra of step s-1 (step 0 before
-                // the previous granule's expansion); as soon as it is transposed into planes, its registers take the
-                // loads of step s+1.  (Ping-pong buffers cost 18 more VGPRs = one wave per SIMD at S = 4.)
+                // software pipeline with ONE buffer: step s was loaded during the algebra of step s-1; as soon as it is
+                // transposed into planes, its registers take the loads of step s+1.  (Ping-pong buffers cost 18 more VGPRs =
+                // one wave per SIMD at S = 4.)  Step 0 arrives transposed: consume_first_step.
                 const uint32_t blk = blk0 + (uint32_t)s * 64u + (uint32_t)lane;
-                const uint32_t w[16] = {d.q0.x, d.q0.y, d.q0.z, d.q0.w, d.q1.x, d.q1.y, d.q1.z, d.q1.w,
-                                        d.q2.x, d.q2.y, d.q2.z, d.q2.w, d.q3.x, d.q3.y, d.q3.z, d.q3.w};
-                const sj_u64 halo = d.halo;
                 uint32_t plo[8], phi[8];  // the block's eight bit planes, bytes 0..31 / 32..63 (sj_block32.h)
-                sj_transpose32(w, plo, phi);
-                asm volatile("" ::"v"(halo) : "memory");  // (the halo arrived with the block: its wait belongs here, in front of the requests)
-                if (s + 1 < S) load_step(d, buf, blk0 + (uint32_t)(s + 1) * 64u + (uint32_t)lane, nblocks, left_halo);
+                sj_u64 halo;
+                if (s == 0) {
+#pragma unroll
+                    for (int k = 0; k < 8; ++k) {
+                        plo[k] = plo0[k];
+                        phi[k] = phi0[k];
+                    }
+                    halo = halo0;
+                    if (S > 1) load_step(d, buf, blk0 + 64u + (uint32_t)lane, nblocks, left_halo);
+                } else {
+                    const uint32_t w[16] = {d.q0.x, d.q0.y, d.q0.z, d.q0.w, d.q1.x, d.q1.y, d.q1.z, d.q1.w,
+                                            d.q2.x, d.q2.y, d.q2.z, d.q2.w, d.q3.x, d.q3.y, d.q3.z, d.q3.w};
+                    halo = d.halo;
+                    sj_transpose32(w, plo, phi);
+                    asm volatile("" ::"v"(halo) : "memory");  // (the halo arrived with the block: its wait belongs here, in front of the requests)
+                    if (s + 1 < S) load_step(d, buf, blk0 + (uint32_t)(s + 1) * 64u + (uint32_t)lane, nblocks, left_halo);
+                }
                 if (s == S - 1 && !safe) {
                     // Requested in the last step: late enough that granules are started in ticket order (a ticket held through
                     // a whole slow iteration delays every granule behind it), and the last step's algebra, the scans and the
@@ -699,8 +763,13 @@ stage1_body(const uint8_t* __restrict__ buf, sj_u64 len, uint32_t* __restrict__ 
         }
         uint32_t nxt = NO_TILE;
         if (have) nxt = safe ? take_ticket(my_ticket) : next_granule();  // (FAST: the wait for the ticket stands here)
-        // first step of the next granule: in flight during the expansion below (clamped, so harmless without one)
+        // first step of the next granule: in flight during the expansion below and consumed in front of its last flush (clamped,
+        // so harmless without one)
         load_step(d, buf, nxt * (64u * S) + (uint32_t)lane, nblocks, left_halo);  // (NO_TILE wraps: any block will do)
+        // The expansion's LAST flush is held back until that step has been consumed (below): the one flush of a granule that fits the
+        // staging slots, the second of a split one.  (The windowed fallback stores as it goes: measured, no gain.)
+        uint32_t* fl_gbp = nullptr;  // the line in which the round's first index lies
+        uint32_t fl_g0 = 0, fl_span = 0;
 
         // =================== E: resolve granule `prev`'s prefix, expand and store its indexes ===================
         if (prev != NO_TILE) {
@@ -773,39 +842,28 @@ stage1_body(const uint8_t* __restrict__ buf, sj_u64 len, uint32_t* __restrict__ 
                     const uint32_t WT = gend - gbase;
                     uint32_t* dst0 = out + cnt_in + gbase;
                     // One round of the fast form: steps [e0, e1) of the group, whose rcount indexes begin rbase entries into the
-                    // group, fit the staging slots, so the per-bit loops need no window test.  Entries are staged at the same
-                    // position modulo 4 as their final index, so that whole 16-byte quads of the LDS slice go out as
-                    // global_store_dwordx4 (the index array is 16-byte aligned); only the two boundary quads of the run need
-                    // element-wise stores.
-                    auto flush_round = [&](uint32_t rbase, uint32_t rcount, uint32_t g0) {
-                        const uint32_t span = g0 + rcount;
-                        uint32_t* gbp = dst0 + rbase - g0;  // 16-byte aligned
-                        for (uint32_t qi = lane; qi * 4 < span; qi += 64) {
-                            const uint4 v = reinterpret_cast<const uint4*>(stage)[qi];
-                            const uint32_t lo = qi * 4;
-                            if (lo >= g0 && lo + 4 <= span) {
-                                // (16 KiB granules = large inputs: the index array is a stream nobody reads before it has left the
-                                //  caches anyway -- streaming stores: +1.4 % on the headline, +1.5 % on twitter x1024; small documents keep
-                                //  theirs in L2 for the kernels behind this one, and the batch flavour is 3.5 % SLOWER with them:
-                                //  profiles/r6/README.md)
-                                if constexpr (S == 4 && !BATCH) {
-                                    typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
-                                    u32x4_t nv = {v.x, v.y, v.z, v.w};
-                                    __builtin_nontemporal_store(nv, reinterpret_cast<u32x4_t*>(gbp) + qi);
-                                } else {
-                                    reinterpret_cast<uint4*>(gbp)[qi] = v;
-                                }
-                            } else {
-                                if (lo + 0 >= g0 && lo + 0 < span) gbp[lo + 0] = v.x;
-                                if (lo + 1 >= g0 && lo + 1 < span) gbp[lo + 1] = v.y;
-                                if (lo + 2 >= g0 && lo + 2 < span) gbp[lo + 2] = v.z;
-                                if (lo + 3 >= g0 && lo + 3 < span) gbp[lo + 3] = v.w;
-                            }
-                        }
-                        wave_lds_fence();
+                    // group, fit the staging slots, so the per-bit loops need no window test.  Entries are staged at the position
+                    // their final ADDRESS has inside its 128-byte line (stage_offset), so that the staging slots go out as
+                    // global_store_dwordx4 whose 64 lanes cover eight whole lines: quad qi of the slots is quad qi behind a line
+                    // boundary.  Only the first and the last line of the run are partial, and only its two boundary quads need
+                    // element-wise stores.  (Staged modulo 4, as before round 27, a wave instruction straddled nine lines and
+                    // shared two of them with its neighbours: profiles/r27/README.md.)
+                    auto stage_offset = [&](uint32_t rbase) {
+                        return (uint32_t)(reinterpret_cast<uintptr_t>(dst0 + rbase) >> 2) & (uint32_t)(STORE_ALIGN - 1);
                     };
-                    auto fast_round = [&](uint32_t rbase, uint32_t rcount) {
-                        const uint32_t g0 = (uint32_t)((cnt_in + gbase + rbase) & 3ull);
+                    auto flush_round = [&](uint32_t rbase, uint32_t rcount, uint32_t g0, bool last) {
+                        const uint32_t span = g0 + rcount;
+                        uint32_t* gbp = dst0 + rbase - g0;  // line-aligned (never dereferenced in front of dst0 + rbase)
+                        if (last) {
+                            fl_gbp = gbp;
+                            fl_g0 = g0;
+                            fl_span = span;
+                            return;
+                        }
+                        store_staged(gbp, g0, span);
+                    };
+                    auto fast_round = [&](uint32_t rbase, uint32_t rcount, bool last) {
+                        const uint32_t g0 = stage_offset(rbase);
 #pragma unroll
                         for (int e = 0; e < E; ++e) {
                             const uint32_t bstart = (uint32_t)((pblk0 + (sj_u64)(g * E + e) * 64 + lane) * 64);
@@ -815,7 +873,7 @@ stage1_body(const uint8_t* __restrict__ buf, sj_u64 len, uint32_t* __restrict__ 
                                 *q++ = bstart | 32u | (uint32_t)__builtin_ctz(hi);
                         }
                         wave_lds_fence();
-                        flush_round(rbase, rcount, g0);
+                        flush_round(rbase, rcount, g0, last);
                     };
                     // The per-bit loops above run as long as the BUSIEST lane of each of their 2 * E trips has bits: 151 trips of
                     // the loop body per 16 KiB of the configs[3] documents for a mean of 48 indexes per lane (56 for 22 on
@@ -824,10 +882,10 @@ stage1_body(const uint8_t* __restrict__ buf, sj_u64 len, uint32_t* __restrict__ 
                     // buckets, every half mask with its staging slot and its block stored at its rank), then lane l takes entries
                     // l, l + 64, ...: a trip's 64 half masks have (nearly) the same number of bits, the empty ones come last and
                     // their trips are not run (tools/README.md: expansion statistics; profiles/r6/README.md has the A/B).
-                    auto sorted_round = [&](auto e0c, auto e1c, uint32_t rbase, uint32_t rcount) {
+                    auto sorted_round = [&](auto e0c, auto e1c, uint32_t rbase, uint32_t rcount, bool last) {
                         constexpr int E0 = decltype(e0c)::value, E1 = decltype(e1c)::value, NI = 2 * (E1 - E0);
                         static_assert(NI * 128 + 128 <= CAP, "the sort's tables overlay the staging slots");
-                        const uint32_t g0 = (uint32_t)((cnt_in + gbase + rbase) & 3ull);
+                        const uint32_t g0 = stage_offset(rbase);
                         uint32_t* const hist = stage + NI * 128;  // [64]: half masks by population (0 .. 32)
                         uint32_t* const bbase = hist + 64;        // [64]: first rank of a bucket, the fullest bucket first
                         uint2* const items = reinterpret_cast<uint2*>(stage);  // [NI * 64]: .x = half mask, .y = byte offset of its first staging slot | (its first byte's offset in the granule) << 16
@@ -880,22 +938,23 @@ stage1_body(const uint8_t* __restrict__ buf, sj_u64 len, uint32_t* __restrict__ 
                             }
                         }
                         wave_lds_fence();
-                        flush_round(rbase, rcount, g0);
+                        flush_round(rbase, rcount, g0, last);
                     };
                     // (a structural every ~5 bytes -- the documents of configs[3] -- makes 3,000 per 16 KiB granule: more than
                     //  the 2,304 slots, but each half of the granule fits)
                     const uint32_t split = E >= 2 ? (uint32_t)__builtin_amdgcn_readfirstlane((int)pos[E / 2]) : 0u;
                     using std::integral_constant;
                     bool staged = false;
-                    if (WT + 3 <= (uint32_t)CAP) {
-                        if (WT > (uint32_t)(SJMI_S1_SORT_MIN * E)) sorted_round(integral_constant<int, 0>{}, integral_constant<int, E>{}, 0, WT);
-                        else fast_round(0, WT);
+                    constexpr uint32_t PAD = STORE_ALIGN - 1;  // staging slots in front of a round's first index
+                    if (WT + PAD <= (uint32_t)CAP) {
+                        if (WT > (uint32_t)(SJMI_S1_SORT_MIN * E)) sorted_round(integral_constant<int, 0>{}, integral_constant<int, E>{}, 0, WT, true);
+                        else fast_round(0, WT, true);
                         staged = true;
                     }
                     if constexpr (E >= 2) {
-                        if (!staged && split + 3 <= (uint32_t)CAP && WT - split + 3 <= (uint32_t)CAP) {
-                            sorted_round(integral_constant<int, 0>{}, integral_constant<int, E / 2>{}, 0, split);
-                            sorted_round(integral_constant<int, E / 2>{}, integral_constant<int, E>{}, split, WT - split);
+                        if (!staged && split + PAD <= (uint32_t)CAP && WT - split + PAD <= (uint32_t)CAP) {
+                            sorted_round(integral_constant<int, 0>{}, integral_constant<int, E / 2>{}, 0, split, false);
+                            sorted_round(integral_constant<int, E / 2>{}, integral_constant<int, E>{}, split, WT - split, true);
                             staged = true;
                         }
                     }
@@ -930,6 +989,11 @@ stage1_body(const uint8_t* __restrict__ buf, sj_u64 len, uint32_t* __restrict__ 
                 }
             }
         }
+        // On the main path only document loads are in flight here (the first flush of a split granule and the side outputs'
+        // stores have an expansion behind them): the wait for the next granule's first step waits for nothing else.  Its planes
+        // stay in registers across the flush and the parking; the flush's stores have a whole step's algebra to be acknowledged in.
+        consume_first_step();
+        if (fl_gbp) store_staged(fl_gbp, fl_g0, fl_span);
         if (!have) break;
         // park granule `cur` until its prefix is known (next iteration)
         wave_lds_fence();
