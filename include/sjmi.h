@@ -1079,6 +1079,61 @@ int sjmi_top_rows_device(sjmi_ctx* ctx, const void* d_key_types, const void* d_k
                          uint64_t n_cols, uint64_t col_stride, void* d_rows, void* d_out_types, void* d_out_values, void* d_result,
                          void* stream);
 
+/* ---- the document of every exploded row, and that document's cells on the row, on the device -------------------------------
+ * "Commits per /actor/login", "the longest commit messages with their event's /type": sjmi_select_batch_device gives one cell per
+ * (path, document), sjmi_explode_batch_device one row per element; this call says which document a row belongs to and copies
+ * that document's cells onto the row -- pandas.json_normalize(record_path, meta), SQL's UNNEST with the outer row's columns
+ * (csrc/parents.hip, csrc/sj_parents.h).  Every operator that takes a (types, values) column set then works
+ * across the document / element boundary; string cells of both sides point into the same string buffer.
+ *
+ * ROWS.  d_row_offsets is uint64[n_docs + 1] as sjmi_explode_batch_device writes it, total = d_row_offsets[n_docs].  The live
+ * rows are min(n_rows, *d_row_count), read on the device as sjmi_key_census_device and sjmi_top_rows_device read them (NULL:
+ * n_rows).  Output slot i < live stands for row index x = i when d_rows is NULL -- the DENSE form: the rows of an explode, with
+ * d_row_count typically d_row_offsets + n_docs -- and for x = d_rows[i] (uint64) otherwise -- the SPARSE form: a filter's
+ * selection vector, or sjmi_top_rows_device's d_rows, which is in rank order and not ascending.  The sparse form assumes no order;
+ * duplicates are legal.
+ * PARENTS.  A row x < total has exactly one parent: the k with d_row_offsets[k] <= x < d_row_offsets[k + 1]; a document without
+ * rows is never a parent.  A row x >= total is an ORPHAN: d_parents[i] is all ones, d_parent_types[i] is 0 (MISSING), and every
+ * carried cell of it has type 0 and value 0.  Orphans occur in the dense form when n_rows exceeds total and in the sparse form
+ * with any index at or above total; with n_docs == 0 every live row is one.
+ * OUTPUT, each part optional (NULL).  d_parents, int64[n_rows]; d_parent_types, uint8[n_rows], 'l' for a row with a parent: the
+ * pair IS a typed long column, for LONG_* filter terms and as a key of sjmi_top_rows_device.  d_out_types[c * out_stride + i] =
+ * d_types[c * col_stride + k], and likewise d_out_values, for the n_cols DOCUMENT columns d_types / d_values (select's layout,
+ * col_stride >= n_docs cells apart): the layout of a filter's compacted pair.  With out_stride = the explode's row_capacity the
+ * out pointers may be the tail rows of a wider column set whose head rows the explode wrote.  Nothing at or behind `live` is
+ * written, and nothing outside the buffers' extents.  Type pointers may have any alignment.  The record, sjmi_parent_result,
+ * three uint64 words, always complete: n_rows = live, n_orphans, flags = 0.  n_rows == 0 and n_docs == 0 are legal.  THE WHOLE
+ * OUTPUT IS A FUNCTION OF THE INPUT ALONE.
+ * ARGUMENTS.  SJMI_ERR_ARG: NULL d_row_offsets or d_result; n_cols > SJMI_PARENT_MAX_COLS; with n_cols > 0 a NULL d_types,
+ * d_values, d_out_types or d_out_values, col_stride < n_docs or out_stride < n_rows; n_rows or n_docs >= 2^32; d_row_offsets,
+ * d_rows, d_row_count, d_values, d_parents, d_out_values or d_result not 8-byte aligned.
+ * STREAM AND STATE.  Asynchronous on `stream` (NULL = the context's), no host synchronisation, no memset node, no scratch: the
+ * call leaves nothing on the context and forgets nothing.  All buffers are device memory.
+ * KERNELS.  One lane writes the record.  DENSE: one workgroup of 256 lanes per 1024 rows.  Two waves find the parents of the
+ * chunk's first and last live row with a 64-ary search over the offsets (64 pivots, one ballot, at most 6 rounds); the documents
+ * of that span are walked 256 at a time, and a document with rows whose first row lies in the chunk marks LDS at that row -- one
+ * document begins at any row, so no two lanes write one address; a running maximum over the marks, seeded with the first row's
+ * parent, is the parent of every position; then the stores, and per carried column a load at the parent and a coalesced store.
+ * SPARSE: a lane per slot and a binary search bounded by n_docs -- latency-bound by design, meant for the rows of a top k or of a
+ * filter.  The orphans are counted with one agent-scope relaxed atomic per workgroup.  Nothing spins or waits for another
+ * workgroup.
+ * ROBUSTNESS.  The offsets are trusted to be what the explode wrote.  Every search is bounded by n_docs all the same, and a
+ * parent is compared with n_docs before it becomes a load address: wild offset words may give wrong parents, never a load or
+ * store outside a buffer or an unbounded loop.
+ * KNOWN LIMITS.  The spans of all chunks sum to at most n_docs plus the number of chunks, but one chunk behind a long run of
+ * documents without rows walks that run alone.  Out of scope: nested explodes, joins on anything but the row-to-document relation,
+ * distinct-parent counts, several offset arrays per call. */
+#define SJMI_PARENT_MAX_COLS 64u
+#define SJMI_PARENT_RESULT_WORDS 3u
+typedef struct sjmi_parent_result {
+    uint64_t n_rows, n_orphans;
+    uint32_t flags, reserved;
+} sjmi_parent_result;
+int sjmi_parent_columns_device(sjmi_ctx* ctx, const void* d_row_offsets, uint64_t n_docs, const void* d_rows, uint64_t n_rows,
+                               const void* d_row_count, const void* d_types, const void* d_values, uint64_t n_cols, uint64_t col_stride,
+                               void* d_parent_types, void* d_parents, void* d_out_types, void* d_out_values, uint64_t out_stride,
+                               void* d_result, void* stream);
+
 /* Optional: page-lock caller-owned host memory that is passed to the host-buffer entry points again and again
  * (SimdJsonParser's padded input, index array and string buffer): H2D / D2H copies of pinned memory skip the
  * driver's staging copy (3-4x faster for the ~1 MB transfers of a single-document parse).  Purely a performance

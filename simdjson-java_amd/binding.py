@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_HERE)
 _CSRC = os.path.join(_HERE, "csrc")
 _LIB = os.path.join(_HERE, "libsjmi.so")
-SOURCES = ["stage1.hip", "strings.hip", "batch.hip", "walk.hip", "coop_walk.hip", "masks.hip", "select.hip", "explode.hip", "ndjson.hip", "strcol.hip", "filter.hip", "arrowcol.hip", "timecol.hip", "dictcol.hip", "census.hip", "groupstats.hip", "toprows.hip", "sjmi_api.hip", "host/simdjson_parser.cpp"]
+SOURCES = ["stage1.hip", "strings.hip", "batch.hip", "walk.hip", "coop_walk.hip", "masks.hip", "select.hip", "explode.hip", "ndjson.hip", "strcol.hip", "filter.hip", "arrowcol.hip", "timecol.hip", "dictcol.hip", "census.hip", "groupstats.hip", "toprows.hip", "parents.hip", "sjmi_api.hip", "host/simdjson_parser.cpp"]
 
 ST_UTF8, ST_UNCLOSED, ST_UNESCAPED, ST_CAPACITY, ST_INTERNAL = 1, 2, 4, 0x100, 0x200
 PADDING = 64
@@ -182,6 +182,7 @@ ABI = {
     "sjmi_key_census_device": (I, (P, P, P, P, U64, P, U64, P, P, P)),
     "sjmi_group_stats_device": (I, (P, P, P, P, P, U64, P, U64, P, P, P)),
     "sjmi_top_rows_device": (I, (P, P, P, P, U64, P, U32, U32, U64, P, P, U64, U64, P, P, P, P, P)),
+    "sjmi_parent_columns_device": (I, (P, P, U64, P, U64, P, P, P, U64, U64, P, P, P, P, U64, P, P)),
     "sjmi_host_register": (I, (P, P, U64)),
     "sjmi_set_input_staging": (I, (P, P, U64)),
     "sjmi_host_unregister": (I, (P, P)),
@@ -605,6 +606,21 @@ class Context:
                                                d_row_count or None, kind, flags, k, d_types or None, d_values or None, n_cols, col_stride,
                                                d_rows or None, d_out_types or None, d_out_values or None, d_result or None, stream),
                     "sjmi_top_rows_device")
+
+    def parent_columns_device(self, d_row_offsets, n_docs, d_rows, n_rows, d_row_count, d_types, d_values, n_cols, col_stride,
+                              d_parent_types, d_parents, d_out_types, d_out_values, out_stride, d_result, stream=0):
+        """sjmi_parent_columns_device: the document of every exploded row, and that document's cells on the row.  d_row_offsets
+        (uint64 [n_docs + 1], as explode_batch_device writes them); d_rows (None / 0: the dense form, slot i is row i; else uint64
+        [n_rows] row indices in any order); d_row_count (None / 0: every row) = a device uint64 that holds the live rows; d_types
+        / d_values = n_cols DOCUMENT columns col_stride >= n_docs cells apart (None / 0 with n_cols 0); d_parent_types (uint8
+        [n_rows]) and d_parents (int64 [n_rows]), each None / 0 to leave it out: 'l' and the document, MISSING and -1 for a row at
+        or above d_row_offsets[n_docs]; d_out_types (uint8) / d_out_values (uint64), n_cols rows out_stride >= n_rows cells
+        apart; d_result = device sjmi_parent_result (3 x int64: live rows, n_orphans, flags in the low half of the third).
+        n_rows and n_docs < 2^32, n_cols <= 64.  Asynchronous on `stream`."""
+        self._check(lib().sjmi_parent_columns_device(self._h, d_row_offsets or None, n_docs, d_rows or None, n_rows, d_row_count or None,
+                                                     d_types or None, d_values or None, n_cols, col_stride, d_parent_types or None,
+                                                     d_parents or None, d_out_types or None, d_out_values or None, out_stride,
+                                                     d_result or None, stream), "sjmi_parent_columns_device")
 
     def ndjson_offsets(self, data):
         """sjmi_ndjson_offsets (host form) -> (doc_offsets np.uint64 [n_docs + 1], consumed, flags): the documents are the

@@ -1148,6 +1148,26 @@ int sjmi_top_rows_device(sjmi_ctx* c, const void* d_key_types, const void* d_key
                : SJMI_OK;
 }
 
+int sjmi_parent_columns_device(sjmi_ctx* c, const void* d_row_offsets, uint64_t n_docs, const void* d_rows, uint64_t n_rows,
+                               const void* d_row_count, const void* d_types, const void* d_values, uint64_t n_cols, uint64_t col_stride,
+                               void* d_parent_types, void* d_parents, void* d_out_types, void* d_out_values, uint64_t out_stride, void* d_result,
+                               void* stream) {
+    if (!c || !d_row_offsets || !d_result || n_cols > SJMI_PARENT_MAX_COLS) return SJMI_ERR_ARG;
+    if (n_rows >= (1ull << 32) || n_docs >= (1ull << 32)) return SJMI_ERR_ARG;  // (a parent + 1 fits 33 bits; one workgroup per 1024 rows)
+    if (n_cols && (!d_types || !d_values || !d_out_types || !d_out_values || col_stride < n_docs || out_stride < n_rows)) return SJMI_ERR_ARG;
+    if (((uintptr_t)d_row_offsets & 7) || ((uintptr_t)d_rows & 7) || ((uintptr_t)d_row_count & 7) || ((uintptr_t)d_values & 7) ||
+        ((uintptr_t)d_parents & 7) || ((uintptr_t)d_out_values & 7) || ((uintptr_t)d_result & 7))
+        return SJMI_ERR_ARG;
+    if (n_cols && (col_stride > ~0ull / 8 / n_cols || out_stride > ~0ull / 8 / n_cols)) return SJMI_ERR_ARG;  // (a column set is addressable)
+    if (fail(c, "hipSetDevice", hipSetDevice(c->device))) return SJMI_ERR_HIP;
+    hipStream_t st = stream_of(c, stream);  // (the call keeps no state in the context: no scratch to grow)
+    return fail(c, "parent columns launch",
+                sjmi::parents_launch(d_row_offsets, n_docs, d_rows, n_rows, d_row_count, d_types, d_values, n_cols, col_stride, d_parent_types,
+                                     d_parents, d_out_types, d_out_values, out_stride, d_result, st))
+               ? SJMI_ERR_HIP
+               : SJMI_OK;
+}
+
 int sjmi_ndjson_offsets(sjmi_ctx* c, const uint8_t* buf, uint64_t len, uint64_t* doc_offsets, uint64_t offset_capacity,
                         uint64_t* n_docs, uint64_t* consumed, uint32_t* flags) {
     if (!c || (!buf && len) || (!doc_offsets && offset_capacity) || !n_docs || !consumed || !flags) return SJMI_ERR_ARG;

@@ -475,4 +475,12 @@ hipError_t toprows_launch(const void* d_key_types, const void* d_key_validity, c
                           uint32_t kind, uint32_t flags, uint64_t k, const void* d_types, const void* d_values, uint64_t n_cols,
                           uint64_t col_stride, void* d_rows, void* d_out_types, void* d_out_values, void* d_result, void* d_ws, hipStream_t stream);
 
+// ---- the document of every exploded row, and that document's cells on the row (parents.hip) ----
+// k_parent_clear (the sjmi_parent_result at d_result) and, with n_rows != 0, k_parent_dense (d_rows NULL) or k_parent_sparse; no
+// scratch.  d_row_count, d_parent_types, d_parents and, with n_cols == 0, the column pointers may be NULL; d_row_count is read by
+// the kernels
+hipError_t parents_launch(const void* d_row_offsets, uint64_t n_docs, const void* d_rows, uint64_t n_rows, const void* d_row_count,
+                          const void* d_types, const void* d_values, uint64_t n_cols, uint64_t col_stride, void* d_parent_types, void* d_parents,
+                          void* d_out_types, void* d_out_values, uint64_t out_stride, void* d_result, hipStream_t stream);
+
 }  // namespace sjmi

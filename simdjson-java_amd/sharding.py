@@ -97,6 +97,7 @@ def _check_row_count(row_count, types):
 GROUP_STATS_WORDS = 10  # SJMI_GROUP_STATS_WORDS
 TOP_KINDS = {"long": 1, "double": 2}  # SJMI_TOP_LONG, SJMI_TOP_DOUBLE
 TOP_SMALLEST, TOP_MAX_K, TOP_RESULT_WORDS = 1, 2048, 9  # SJMI_TOP_SMALLEST, SJMI_TOP_MAX_K, SJMI_TOP_RESULT_WORDS
+PARENT_MAX_COLS, PARENT_RESULT_WORDS = 64, 3  # SJMI_PARENT_MAX_COLS, SJMI_PARENT_RESULT_WORDS
 
 
 def decode_group_stats(stats):
@@ -477,6 +478,81 @@ class BatchShard:
                                     0 if largest else TOP_SMALLEST, k, _ptr(types, n_cols), _ptr(values, n_cols), n_cols, stride, _ptr(rows, k),
                                     _ptr(out_types, n_cols * k), _ptr(out_values, n_cols * k), result.data_ptr(), stream)
         return rows, out_types, out_values, result
+
+    def parent_columns(self, row_offsets, types, values, rows=None, n_rows=None, row_count=None, with_parents=True, stream=0):
+        """The document of every exploded row, and that document's cells on the row (pandas.json_normalize's meta, SQL's UNNEST
+        with the outer row's columns): sjmi_parent_columns_device on the row offsets of explode() ([n_docs + 1] int64) and the
+        2-D [n_cols, stride] (types uint8, values int64) pair of DOCUMENT columns -- sel_types / sel_values; stride at least
+        n_docs -- or None for both to get the parents only.  rows=None is the dense form: slot i is row i, n_rows is required
+        (normally the explode's row_capacity) and row_count is normally row_offsets[n_docs:].  With rows (1-D int64: filter()'s
+        or top_rows()' rows, in any order, duplicates legal) slot i is row rows[i] and n_rows defaults to rows.numel().
+        row_count as for arrow_columns(): the live slots are min(n_rows, row_count[0]).  -> (parent_types [n_rows] uint8,
+        parents [n_rows] int64 -- one typed long column: 'l' and the document, MISSING and -1 for a row at or above
+        row_offsets[n_docs], an orphan; both None with with_parents=False --, out_types [n_cols, n_rows] uint8, out_values
+        [n_cols, n_rows] int64: the layout of filter()'s compacted pair, an orphan's cells MISSING and 0; result [3] int64 = live
+        slots, n_orphans, flags), new tensors every call; slots at or behind the live ones are not written.  Nothing
+        synchronises.  Call it on a step that check() has accepted: like filter(), it is not queued again behind a step that
+        check() had to run again."""
+        import torch
+        assert row_offsets.dim() == 1 and row_offsets.dtype == torch.int64 and row_offsets.is_contiguous() and int(row_offsets.numel()) >= 1
+        n_docs = int(row_offsets.numel()) - 1
+        if rows is None:
+            assert n_rows is not None, "parent_columns(): the dense form needs n_rows"
+            n_rows = int(n_rows)
+        else:
+            assert rows.dim() == 1 and rows.dtype == torch.int64 and rows.is_contiguous()
+            n_rows = int(rows.numel()) if n_rows is None else int(n_rows)
+            assert n_rows <= int(rows.numel())
+        assert n_rows >= 0
+        _check_row_count(row_count, row_offsets)
+        n_cols = stride = 0
+        if types is not None:
+            n_cols, stride, _ = _column_set(types, values, n_docs)
+            assert n_cols <= PARENT_MAX_COLS
+        parent_types = torch.empty(n_rows, dtype=torch.uint8, device=self.device) if with_parents else None
+        parents = torch.empty(n_rows, dtype=torch.int64, device=self.device) if with_parents else None
+        # (without a slot or without a document cell there is nothing to carry, and an empty tensor has no pointer to give: every
+        # cell of the outputs is then an orphan's)
+        carry = n_cols if n_rows and stride else 0
+        make = torch.empty if carry == n_cols else torch.zeros
+        out_types = make((n_cols, n_rows), dtype=torch.uint8, device=self.device)
+        out_values = make((n_cols, n_rows), dtype=torch.int64, device=self.device)
+        result = torch.empty(PARENT_RESULT_WORDS, dtype=torch.int64, device=self.device)  # sjmi_parent_result (every call writes all of it)
+        self.engine.parent_columns_device(row_offsets.data_ptr(), n_docs, _ptr(rows, rows is not None and n_rows), n_rows,
+                                          _ptr(row_count, row_count is not None), _ptr(types, carry), _ptr(values, carry), carry, stride,
+                                          _ptr(parent_types, with_parents and n_rows), _ptr(parents, with_parents and n_rows),
+                                          _ptr(out_types, carry), _ptr(out_values, carry), n_rows, result.data_ptr(), stream)
+        return parent_types, parents, out_types, out_values, result
+
+    def explode_with_parents(self, plan, row_capacity, doc_types, doc_values, stream=0):
+        """explode() joined with the documents' columns in ONE column set: sjmi_explode_batch_device into the first
+        plan.n_columns rows of types / values [n_columns + n_doc_cols + 1, row_capacity], then, on the same stream,
+        sjmi_parent_columns_device (dense, row count = the explode's last row offset, read on the device) into the rest: the
+        n_doc_cols DOCUMENT columns doc_types / doc_values (a 2-D [n_doc_cols, stride] pair, sel_types / sel_values) carried
+        onto the rows come next, and the parent-id column -- 'l' and the row's document -- comes last.  -> (row_offsets
+        [n_docs + 1] int64, types uint8, values int64, result [3] int64 = live rows, n_orphans, flags), tensors of its own on
+        every call: exp_* and what check() queues again are left alone.  The columns of rows at or behind row_offsets[n_docs]
+        are not written.  Nothing synchronises.  Call it on a step that check() has accepted: like filter(), it is not queued
+        again behind a step that check() had to run again."""
+        import torch
+        row_capacity = int(row_capacity)
+        n_doc_cols, stride, _ = _column_set(doc_types, doc_values, self.n_docs)
+        assert n_doc_cols <= PARENT_MAX_COLS
+        n_columns = getattr(plan, "n_columns", plan.n_paths)
+        row_offsets = torch.zeros(self.n_docs + 1, dtype=torch.int64, device=self.device)
+        types = torch.zeros((n_columns + n_doc_cols + 1, row_capacity), dtype=torch.uint8, device=self.device)
+        values = torch.zeros((n_columns + n_doc_cols + 1, row_capacity), dtype=torch.int64, device=self.device)
+        result = torch.empty(PARENT_RESULT_WORDS, dtype=torch.int64, device=self.device)  # sjmi_parent_result
+        self.engine.explode_batch_device(plan, self.tape.data_ptr(), self.tape_offsets.data_ptr(), self.doc_errors.data_ptr(),
+                                         self.sb.data_ptr(), self.n_docs, row_offsets.data_ptr(), row_capacity,
+                                         _ptr(types, row_capacity), _ptr(values, row_capacity), stream)
+        head, last = n_columns * row_capacity, (n_columns + n_doc_cols) * row_capacity  # cells in front of the carried columns / the ids
+        at = lambda t, cells: t.data_ptr() + cells * t.element_size() if row_capacity else 0
+        carry = n_doc_cols if row_capacity and stride else 0  # (no row or no document cell: nothing to carry, the cells stay MISSING)
+        self.engine.parent_columns_device(row_offsets.data_ptr(), self.n_docs, 0, row_capacity, row_offsets.data_ptr() + 8 * self.n_docs,
+                                          _ptr(doc_types, carry), _ptr(doc_values, carry), carry, stride, at(types, last), at(values, last),
+                                          at(types, head), at(values, head), row_capacity, result.data_ptr(), stream)
+        return row_offsets, types, values, result
 
     def group_by_string(self, key_types, key_values, val_types, val_values, dict_capacity, row_count=None, stream=0):
         """"Total and largest <value> per <key>": dictionary_column() on the 1-D key column (its string cells point into self.sb),
