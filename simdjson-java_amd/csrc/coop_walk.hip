@@ -120,6 +120,10 @@ constexpr uint32_t CW_TRUE = 0x65757274u, CW_FALS = 0x736c6166u, CW_NULL = 0x6c6
 // internal: a floating literal of more than 19 significant digits whose two 19-digit neighbours round to different doubles;
 // the walker writes the lower candidate and lists the literal for k_slow_doubles (the exact comparison of sj_bigdec.h)
 constexpr int CW_SLOW_DOUBLE = -2;
+// internal (k_coop_walk<true>): a container that would open level CW_LEVELS, met inside a chunk -- the chunk summaries carry a
+// minimum depth and no maximum, so a document whose chunks all END below CW_LEVELS may still get there in between; the chunk's
+// walker raises the fall-back flag and the single-wave sweep, which keeps levels 64 .. 1023 in global memory, takes the document
+constexpr int CW_CHUNK_DEEP = -3;
 
 // TapeBuilder.visitPrimitive (TapeBuilder.java:70-79) / visitRootPrimitive (:59-68) for one lane; win = the 16 bytes at idx.
 // -> 0 and (type, raw second word for numbers) or the SJMI_E_* / SJMI_WALK_NEEDS_HOST code
@@ -252,7 +256,8 @@ __device__ __forceinline__ int highest_bit_below(unsigned long long m, unsigned 
 //   k_coop_walk<true>(parallel, a wave per chunk): the walker proper, started from the chunk's entry state;
 //   k_chunk_finish   (one wave): the document's first error by position, the root words.
 // Relative levels live in the 64 lanes of the stack registers with a bias of 32; a chunk whose depth swings further, or a
-// document deeper than the stack, raises the fall-back flag and the single-wave sweep takes the document.
+// document deeper than the stack -- at a chunk's end (the scan) or inside a chunk (its walker, CW_CHUNK_DEEP) -- raises the
+// fall-back flag and the single-wave sweep takes the document.
 // structurals per chunk and chunks per group are functions of the document's structural count n alone (every kernel
 // computes them from index_offsets): short chunks while there are fewer chunks than SIMDs to put them on (a step costs a
 // lone wave ~5 us, so a 128-structural chunk = 2 steps), longer ones after that; groups of ~sqrt(chunks / 4)
@@ -719,7 +724,8 @@ k_coop_walk(const uint8_t* __restrict__ buf, const unsigned long long* __restric
                         if (cls <= K_OPEN_O) {
                             if (!empty_open) {
                                 if (h + 1 >= max_depth) err = SJMI_E_DEPTH;                  // JsonIterator.java:69-70
-                                else if (h + 1 >= level_cap) err = SJMI_WALK_NEEDS_HOST;     // deeper than the device stack
+                                // deeper than the device stack (a chunk's walker has the register levels only: the sweep decides)
+                                else if (h + 1 >= level_cap) err = CHUNKED ? CW_CHUNK_DEEP : SJMI_WALK_NEEDS_HOST;
                             }
                         } else if (cls != K_QUOTE) {
                             err = cw_primitive(buf, win, p, i == from, doc_end, &ptype, &praw);
@@ -792,6 +798,10 @@ k_coop_walk(const uint8_t* __restrict__ buf, const unsigned long long* __restric
             if (pq_live && pq_tpos < room) T[pq_tpos] = tape_word('"', string_base + pq_off);  // the last step's strings
             if (CHUNKED) {  // the document's verdict is assembled by k_chunk_finish from the chunks' first errors
                 if (lane == 0) {
+                    if (code == CW_CHUNK_DEEP) {  // not this chunk's error: the sweep decides (k_chunk_finish looks at the flag first)
+                        atomicOr(cw.fallback, 1u);
+                        code = 0;
+                    }
                     cw.err_pos[k] = code ? err_at : 0xFFFFFFFFu;
                     cw.err_code[k] = code;
                 }
@@ -1584,6 +1594,8 @@ k_group_replay(const unsigned long long* __restrict__ index_offsets, ChunkWs cw)
         s.bad = false;
         s.min_after = 0x7FFF;
         scan_range<false>(s, cw.sum, k0, k1, lane, [&](uint64_t k, const ScanState& at) { store_in(cw.in, k, at, lane); });
+        // a chunk of the group ends deeper than the stack registers (k_top_scan sees the groups' ends only)
+        if (s.bad && lane == 0) atomicOr(cw.fallback, 1u);
     }
 }
 
@@ -1594,7 +1606,14 @@ k_chunk_finish(const uint8_t* __restrict__ buf, const uint32_t* __restrict__ idx
                ChunkWs cw, SingleFinish fin, uint32_t with_tail) {
     __shared__ uint32_t wa[SJ_BIG_WORDS], wb[SJ_BIG_WORDS];
     if (*cw.fallback != 0) {  // the single-wave sweep writes the document's result
-        if (with_tail && fin.pack && threadIdx.x == 0) fin.pack->fallback = 1;  // (optimistic tail: the caller queues that sweep)
+        if (threadIdx.x == 0) {
+            // (the chunk walkers may have run -- CW_CHUNK_DEEP -- and listed literals: the sweep lists its own)
+            *fin.slow.count = 0;
+            if (with_tail && fin.pack) {  // optimistic tail: the caller queues that sweep -- behind a look at THIS call's stage-1 record
+                fin.pack->s1 = *fin.s1;
+                fin.pack->fallback = 1;
+            }
+        }
         return;
     }
     const int lane = threadIdx.x & 63;

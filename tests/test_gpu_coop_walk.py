@@ -194,9 +194,11 @@ def test_large_documents_chunk_parallel(ctx):
 
 
 def test_chunk_and_group_size_boundaries(ctx):
-    """Structural counts around every switch of the chunk-parallel path: 1,024 (single-wave sweep below), multiples of the
-    128- and 512-structural chunks, 262,144 (chunk length 128 -> 512), squares of the group size; and documents whose BOUND
-    asks for chunks (more than 4 KiB) while they hold a handful of structurals (the summary pass hands them back)."""
+    """Structural counts around switches of the chunk-parallel path: multiples of the 128- and 512-structural chunks, 262,144
+    (chunk length 128 -> 512), squares of the group size; and documents whose BOUND asks for chunks (1,536 bytes and more; from
+    16,384 bytes on without the sweep queued behind them) while they hold a handful of structurals (at most 512: the summary
+    pass hands them back to the single-wave sweep).  The counts around 512 itself and the two byte bounds:
+    tests/test_gpu_single_doc_layouts.py."""
     def with_structurals(s):
         # "[0,0,...,0]" has 2k + 3 structurals; one "[]," in front adds 3
         even = s % 2 == 0
