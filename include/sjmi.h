@@ -1188,8 +1188,15 @@ int sjmi_set_auto_safe(sjmi_ctx* ctx, int on);
 int sjmi_set_profiling(sjmi_ctx* ctx, int on);
 /* performance-ablation switches for sjmi_stage1_device (1 = no index stores, 2 = no look-back): results are
  * INVALID while any is set (experiments only); test hooks with valid results: 16 = fast-mode launches report
- * SJMI_ST_INTERNAL, 32 = launch only 8 worker workgroups (as if most of the GPU were busy with other work). */
+ * SJMI_ST_INTERNAL, 32 = launch only 8 worker workgroups (as if most of the GPU were busy with other work), 0x800 = every
+ * granule by ticket, the first one of a wave included (as if another context were launching: what a stage-1 launch does by
+ * itself while another context of the process still has one running). */
 int sjmi_debug_set_flags(sjmi_ctx* ctx, uint32_t flags);
+/* Read-only test hook: out[0 .. 3] = stage-1 launches this context has queued; those of them that took every granule by
+ * ticket (another context of the process was busy, or debug flag 0x800); repeats in SAFE mode after a tripped spin bound (the
+ * host forms' own, and sjmi_set_auto_safe's); SAFE mode now, 0 or 1 (sjmi_set_tile_mode, or latched).  Plain fields of the
+ * context: call it from the thread that uses the context. */
+int sjmi_debug_counters(sjmi_ctx* ctx, uint64_t* out);
 int sjmi_kernel_time(sjmi_ctx* ctx, double* sum_ms, uint32_t* launches);
 
 #ifdef __cplusplus

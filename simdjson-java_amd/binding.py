@@ -192,6 +192,7 @@ ABI = {
     "sjmi_set_auto_safe": (I, (P, I)),
     "sjmi_set_profiling": (I, (P, I)),
     "sjmi_debug_set_flags": (I, (P, U32)),
+    "sjmi_debug_counters": (I, (P, P)),
     "sjmi_kernel_time": (I, (P, P, P)),
 }
 EXPORTS = list(ABI)
@@ -672,6 +673,12 @@ class Context:
 
     def debug_set_flags(self, flags):
         self._check(lib().sjmi_debug_set_flags(self._h, flags), "sjmi_debug_set_flags")
+
+    def debug_counters(self):
+        """-> [stage-1 launches queued, those with every granule by ticket, repeats in SAFE mode, SAFE mode now (0 / 1)]"""
+        out = (C.c_uint64 * 4)()
+        self._check(lib().sjmi_debug_counters(self._h, C.addressof(out)), "sjmi_debug_counters")
+        return [int(v) for v in out]
 
     def set_profiling(self, on):
         self._check(lib().sjmi_set_profiling(self._h, 1 if on else 0), "sjmi_set_profiling")

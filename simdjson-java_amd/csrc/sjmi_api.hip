@@ -123,6 +123,7 @@ struct sjmi_ctx {
     bool auto_safe = false;    // sjmi_set_auto_safe: the *_device stage-1 entry point synchronises, checks and re-runs in SAFE mode
     hipEvent_t busy_event = nullptr;  // recorded behind this context's last stage-1 launch (is it still running?)
     std::atomic<bool> launched{false};
+    uint64_t n_launches = 0, n_ticketed = 0, n_safe_reruns = 0;  // sjmi_debug_counters (written by the calling thread only)
     bool profiling = false;  // bracket every stage-1 kernel with HIP events (bench.py roofline)
     std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
     size_t events_used = 0;
@@ -166,6 +167,13 @@ bool another_context_busy(const sjmi_ctx* self) {
 }
 uint32_t launch_flags(const sjmi_ctx* c) {
     return c->dbg | (c->ticket_mode ? sjmi::FLAG_SAFE : 0u) | (another_context_busy(c) ? sjmi::FLAG_ALL_TICKETS : 0u);
+}
+// the flags of a stage-1 launch that is queued now, counted for sjmi_debug_counters
+uint32_t counted_launch_flags(sjmi_ctx* c) {
+    const uint32_t f = launch_flags(c);
+    ++c->n_launches;
+    if (f & sjmi::FLAG_ALL_TICKETS) ++c->n_ticketed;
+    return f;
 }
 // called right behind a stage-1 launch: a library-owned event on the launch stream is what other contexts poll (never a
 // stream they do not own, which may be gone by then); under the registry lock, like the poll and like sjmi_destroy
@@ -270,6 +278,7 @@ int retry_in_safe_mode(sjmi_ctx* c, const uint32_t& status, Attempt attempt) {
         if (rc != SJMI_OK) return rc;
         if (!(status & SJMI_ST_INTERNAL) || c->ticket_mode) break;
         c->ticket_mode = true;
+        ++c->n_safe_reruns;
     }
     return SJMI_OK;
 }
@@ -293,7 +302,7 @@ void* parity_out(sjmi_ctx* c, const void* d_buf, uint64_t len) {
 // sentinel): the block parities of bytes this context has not indexed
 hipError_t parity_launch(sjmi_ctx* c, const uint8_t* d_buf, uint64_t len, hipStream_t st, const sjmi::Stage1Extras& ex) {
     const hipError_t e = sjmi::stage1_launch(d_buf, len, nullptr, 0, c->d_ws_par, stage1_steps(c, len), st, nullptr, nullptr,
-                                             (launch_flags(c) & ~sjmi::DBG_NO_LOOKBACK) | sjmi::DBG_NO_WRITE, ex);
+                                             (counted_launch_flags(c) & ~sjmi::DBG_NO_LOOKBACK) | sjmi::DBG_NO_WRITE, ex);
     if (e == hipSuccess) note_launch(c, st);
     return e;
 }
@@ -545,7 +554,7 @@ static int stage1_device_impl(sjmi_ctx* c, const void* d_buf, uint64_t len, void
         ++c->events_used;
     }
     if (fail(c, "launch", sjmi::stage1_launch((const uint8_t*)d_buf, len, (uint32_t*)d_indexes, index_capacity, ws, steps,
-                                              st, ev0, ev1, launch_flags(c) | o.shard_flags, ex)))
+                                              st, ev0, ev1, counted_launch_flags(c) | o.shard_flags, ex)))
         return SJMI_ERR_HIP;
     note_launch(c, st);
     if (!fast && fail(c, "D2D(result)", hipMemcpyAsync(d_result, ws + sjmi::WS_RESULT_OFFSET, sizeof(sjmi_stage1_result),
@@ -565,6 +574,7 @@ static int stage1_device_impl(sjmi_ctx* c, const void* d_buf, uint64_t len, void
             return SJMI_ERR_HIP;
         if (r.status & SJMI_ST_INTERNAL) {
             c->ticket_mode = true;
+            ++c->n_safe_reruns;
             return stage1_device_impl(c, d_buf, len, d_indexes, index_capacity, d_result, stream, opts);
         }
     }
@@ -1284,7 +1294,8 @@ int sjmi_stage1_batch(sjmi_ctx* c, const uint8_t* buf, uint64_t total_len, const
     ex1.blkpar = parity_out(c, c->d_in, total_len);
     int rc = retry_in_safe_mode(c, c->h_res->status, [&] {
         if (fail(c, "launch", sjmi::stage1_launch(c->d_in, total_len, c->d_idx, dev_cap, c->d_ws, stage1_steps(c, total_len), c->stream,
-                                                  nullptr, nullptr, launch_flags(c), ex1)) ||
+                                                  nullptr, nullptr, counted_launch_flags(c), ex1)) ||
+            (note_launch(c, c->stream), false) ||  // (other contexts of the process see this launch like any other)
             fail(c, "split", sjmi::split_docs_launch(c->d_idx, (const sjmi::Stage1Result*)d_res, c->d_docoff, n_docs, d_io,
                                                      c->stream)) ||
             fail(c, "D2H(result)", hipMemcpyAsync(c->h_res, d_res, sizeof(sjmi_stage1_result), hipMemcpyDeviceToHost, c->stream)) ||
@@ -1704,7 +1715,7 @@ static int parse_batch_pipeline(sjmi_ctx* c, const BatchCall& b, PipeMode mode) 
             ex.blkw = c->d_blkw;
             ex.result_out = b.stage1();
             if (fail(c, "repair: plain pass", sjmi::stage1_launch(c->d_copy, b.total_len, b.d_indexes, b.index_capacity, c->d_ws_par, steps, st,
-                                                                  nullptr, nullptr, launch_flags(c), ex)))
+                                                                  nullptr, nullptr, counted_launch_flags(c), ex)))
                 return SJMI_ERR_HIP;
             note_launch(c, st);
             rc = batch_plain_stage(c, b, st, 1, c->d_copy, c->d_blkpar2, b.d_buf, batch_flags_of(c->d_ws_par), skip_b, b.d_doc_status, true,
@@ -1948,6 +1959,15 @@ int sjmi_debug_set_flags(sjmi_ctx* c, uint32_t flags) {
     return SJMI_OK;
 }
 
+int sjmi_debug_counters(sjmi_ctx* c, uint64_t* out) {
+    if (!c || !out) return SJMI_ERR_ARG;
+    out[0] = c->n_launches;
+    out[1] = c->n_ticketed;
+    out[2] = c->n_safe_reruns;
+    out[3] = c->ticket_mode ? 1 : 0;
+    return SJMI_OK;
+}
+
 int sjmi_set_profiling(sjmi_ctx* c, int on) {
     if (!c) return SJMI_ERR_ARG;
     c->profiling = on != 0;
@@ -2033,6 +2053,7 @@ int sjmi_stream_push(sjmi_stream* s, const uint8_t* chunk, uint64_t len, int is_
             return SJMI_ERR_HIP;
         if ((r.status & SJMI_ST_INTERNAL) && !c->ticket_mode) {
             c->ticket_mode = true;  // fast-mode liveness assumption failed: latch the safe mode and run again
+            ++c->n_safe_reruns;
             continue;
         }
         if (!(r.status & SJMI_ST_HALO)) break;
