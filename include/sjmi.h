@@ -315,7 +315,9 @@ int sjmi_unescape_batch_device(sjmi_ctx* ctx, const void* d_buf, uint64_t total_
  * of more than 19 significant digits at a rounding boundary (exact big-integer comparison with the midpoint, DoubleParser.
  * java:205-330).  Handed back only: max_depth > 1024 and a document that uses it, more than 65,536 such boundary literals
  * in one launch, a single document of more than 2^31 - 256 structurals.  d_result: sjmi_walk_result, bit 0 of flags =
- * tape_capacity exceeded (offsets valid, tapes not written).  d_buf needs 64 readable bytes after the batch (the
+ * tape_capacity exceeded: tape_words and tape_offsets are valid and complete, nothing at or behind d_tape[tape_capacity] is
+ * written, and the tapes are unspecified -- except where sjmi_parse_batch_device* laid them out before the walk (below): there
+ * every well-formed document whose slot ends at or below tape_capacity has its tape.  d_buf needs 64 readable bytes after the batch (the
  * reference's padding, SimdJsonParser.java:42-48).  Asynchronous on `stream`. */
 #define SJMI_WALK_NEEDS_HOST (-1)
 typedef struct sjmi_walk_result {
