@@ -10,7 +10,9 @@ another, each under its own time limit; the first child that dies by a signal or
 In each child the seam layouts of tests/tok_stream_layouts.py go through (a) the three calls -- three times, identical -- and at
 maxDepth 4 and 63, (b) the optimistic entry on an accepted batch (tapes laid out before the walk), (c) the same batch plus one
 document that fails stage 1 (the repair stage: its blanked document is an empty one inside a run), (d) the exact entry.  Per document:
-the oracle's error code, a kept document's tape word for word, the slot of a failing one; a canary behind the tape's capacity."""
+the oracle's error code, a kept document's tape word for word, the slot of a failing one; a canary behind the tape's capacity.
+(e) Every sequence of up to five tokens and the single-token edits of tests/grammar_sweep.py (75,242 documents, shuffled by the run
+size) through the three calls and the optimistic entry, compared as tests/test_gpu_grammar_sweep.py compares them."""
 import os
 import subprocess
 import sys
@@ -107,9 +109,13 @@ def child():
         _check("exact entry", docs_c, wants_c, err, lambda k: tape[int(to[k]):int(to[k + 1])], strings)
         assert_failing_slots(docs_c, err, to, tapes_laid_out(None, docs_c, err, to))
         assert rejected_b is False, "the layout batch was rejected by the plain pass: (b) did not test the accepted path"
+        # (e) every sequence of up to five tokens and the single-token edits of long documents (tests/grammar_sweep.py), shuffled by
+        # the run size: which error each document gets, through the three calls and the optimistic entry
+        from tests.test_gpu_grammar_sweep import forced_run_sweep
+        swept = forced_run_sweep(ctx, seed=run)
     finally:
         ctx.close()
-    print("TOK_STREAM_RUNS_OK", run, len(docs))
+    print("TOK_STREAM_RUNS_OK", run, len(docs), swept)
 
 
 def test_multi_document_runs_against_the_oracle():

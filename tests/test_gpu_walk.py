@@ -61,9 +61,8 @@ def gpu_walk(ctx, docs, max_depth=1024, packed=None, pad=0):
     total = int(d_ures[0].item())
     strings = bytes(d_sb[:total].cpu().numpy())
     tapes = [tape[to[k]:to[k + 1]] if errors[k] == 0 else None for k in range(n)]
-    for k in range(n):
-        if errors[k] != 0:
-            assert to[k + 1] == to[k]
+    empty = np.diff(to)[:n] == 0  # (a failing document has no tape: as one comparison, the sweeps bring 600,000 documents)
+    assert empty[errors != 0].all(), np.nonzero((errors != 0) & ~empty)[0][:5]
     return tapes, strings, errors
 
 

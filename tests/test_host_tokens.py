@@ -16,9 +16,9 @@ import pytest
 
 from oracle import oracle as O
 from tests.conftest import ROOT
+from tests.grammar_sweep import T9 as TOKENS  # (the GPU sweeps of tests/test_gpu_grammar_sweep.py start from the same nine)
 
 SIM_DIR = os.path.join(ROOT, "tests", "host_sim")
-TOKENS = [b"[", b"{", b"]", b"}", b'"s"', b"1", b"true", b",", b":"]
 
 
 @pytest.fixture(scope="module")
