@@ -20,6 +20,8 @@ INT64_MIN, INT64_MAX = -(1 << 63), (1 << 63) - 1
 POISON = (0x7FF8DEADBEEF0001, 0xFFFFFFFFFFFFFFFF, 0x8000000000000000, 0x7FF0000000000000, 0x0123456789ABCDEF)  # behind non-numbers
 NAN_BITS = (0x7FF8000000000000, 0xFFF8000000000000, 0x7FF0000000000001, 0xFFFFFFFFFFFFFFFF, 0x7FFFFFFFFFFFFFFF, 0xFFF0000000000001)
 OTHER_TYPES = b'"tfn[{\0x'
+SCALES = (2.0 ** -1074, 2.0 ** -1040, 1.0, 2.0 ** 970)  # of value_column's kind "scaled"
+SCALE_IDS = ("2^-1074", "2^-1040", "1", "2^970")
 U = 2.0 ** -53
 
 
@@ -60,11 +62,14 @@ def keys_column(n_rows, n_keys, seed, kind="uniform"):
     return indices, pack_bits(bits), bits
 
 
-def value_column(n_rows, seed, kind="mixed"):
+def value_column(n_rows, seed, kind="mixed", scale=1.0):
     """-> (types uint8, values uint64), ONE (type, value) column.
     mixed: 40 % 'l' cells -- small ones, the whole int64 range, INT64_MIN and INT64_MAX, and a run of 70 of each --, 30 % 'd' cells of
         both signs with magnitudes from 1e-300 to 1e100 and +-0.0 among them, 30 % other type bytes whose value words are POISON;
     exact: the same classes, the doubles integers below 2^20 in magnitude (every partial sum of fewer than 2^20 of them is exact);
+    scaled: exact, every double times `scale`, a power of two: m * scale with |m| < 2^20.  While m * scale is representable for every
+        |m| < 2^50 -- from 2^-1074, where every cell and every sum is subnormal, up to 2^970 -- every partial sum of fewer than 2^30
+        cells is exact in any order, so sum_double must be EQUAL to math.fsum;
     all_long: only 'l', the whole range;  half_double: 'l' and 'd' half and half."""
     rng = np.random.default_rng(seed ^ 0x5EED)
     pick = rng.random(n_rows)
@@ -84,7 +89,7 @@ def value_column(n_rows, seed, kind="mixed"):
     longs[small] = rng.integers(-1000, 1000, int(small.sum()))
     edge = rng.random(n_rows) < 0.05
     longs[edge] = rng.choice(np.array([INT64_MIN, INT64_MAX], dtype=np.int64), int(edge.sum()))
-    if kind == "exact":
+    if kind in ("exact", "scaled"):
         longs = rng.integers(-(1 << 40), 1 << 40, n_rows, dtype=np.int64)
     if n_rows >= 400 and kind == "mixed":  # runs of the extremes: more of them than a wave has lanes
         types[100:170], longs[100:170] = ord("l"), INT64_MAX
@@ -92,8 +97,11 @@ def value_column(n_rows, seed, kind="mixed"):
         is_l, is_d = types == ord("l"), types == ord("d")
     values[is_l] = longs[is_l].view(np.uint64)
     # the doubles
-    if kind == "exact":
+    if kind in ("exact", "scaled"):
         doubles = rng.integers(-(1 << 20) + 1, 1 << 20, n_rows).astype(np.float64)
+        if kind == "scaled":
+            power = int(math.log2(scale))  # (ldexp: exact, whatever floating-point mode numpy's multiply runs in)
+            doubles = np.array([math.ldexp(m, power) for m in doubles.tolist()], dtype=np.float64)
     else:
         doubles = np.where(rng.random(n_rows) < 0.5, -1.0, 1.0) * rng.random(n_rows) * 10.0 ** rng.integers(-300, 101, n_rows)
         zero = rng.random(n_rows) < 0.1

@@ -110,6 +110,25 @@ def test_an_exact_column_in_one_key_is_summed_exactly(ctx, n_keys):
     assert int(b[1][1]) == indices.size > int(a[1][1])
 
 
+@pytest.mark.parametrize("scale", GC.SCALES, ids=GC.SCALE_IDS)
+@pytest.mark.parametrize("n_keys", [1, LDS_KEYS, LDS_KEYS + 1], ids=["one_key", "lds", "global"])
+def test_scaled_columns_go_through_the_f64_atomics_exactly(ctx, n_keys, scale):
+    """doubles m * scale, |m| < 2^20 (value_column's kind "scaled"): at 2^-1074 every cell and every partial sum is subnormal, at
+    2^-1040 the sums cross into the normal range, at 2^970 they stay below the overflow.  Every partial sum in every order is
+    exact (tests/test_wave_patterns.py), so sum_double EQUALS math.fsum, with no tolerance: an LDS add, a flush or an L2 add that
+    flushed a subnormal operand or result to zero would show.  One key and 512 keys: the LDS atomic and its flush; 513 keys: the
+    wave butterfly and the L2 atomic; one_bin: thousands of adds on one word, uniform: few.  Twice, equal word for word"""
+    for n_rows, kind in ((64 * 1024 + 1, "one_bin"), (5 * 1024, "uniform")):
+        indices, words, bits = GC.keys_column(n_rows, n_keys, 3, kind)
+        types, values = GC.value_column(n_rows, 3, "scaled", scale=scale)
+        want = GC.expected_large(indices, bits, types, values, n_keys, n_rows)
+        a = check(ctx, indices, words, bits, types, values, n_keys, what=(scale, kind, n_keys, "first"), exact_sum=True, want=want)
+        b = check(ctx, indices, words, bits, types, values, n_keys, what=(scale, kind, n_keys, "second"), exact_sum=True, want=want, types_shift=3)
+        assert (a[0] == b[0]).all() and (a[1] == b[1]).all()
+        sums = a[0][:, 5].view(np.float64)
+        assert scale != GC.SCALES[0] or ((np.abs(sums) < 2.0 ** -1022).all() and (sums != 0).any())  # (subnormal sums, and kept)
+
+
 def test_the_128_bit_sum(ctx):
     n = 1025
     big, small = np.full(n, GC.INT64_MAX, dtype=np.int64), np.full(n, GC.INT64_MIN, dtype=np.int64)

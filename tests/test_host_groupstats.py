@@ -122,6 +122,20 @@ def test_all_rows_in_one_key_and_a_null_validity(lib, lds_keys, n_keys_of):
     check(lib, indices, words, bits, types, values, n_keys, what="one key, with validity")
 
 
+@pytest.mark.parametrize("scale", GC.SCALES, ids=GC.SCALE_IDS)
+def test_scaled_columns_are_summed_exactly(lib, lds_keys, scale):
+    """doubles m * scale, |m| < 2^20: subnormal cells and sums at 2^-1074, sums that cross into the normal range at 2^-1040, sums
+    next to the overflow at 2^970 -- every partial sum is exact, so sum_double EQUALS math.fsum.  The sequential form of what
+    tests/test_gpu_groupstats.py runs through the device's f64 atomics: a failure there and not here is the device's"""
+    for n_rows, kind in ((64 * 1024 + 1, "one_bin"), (5 * 1024, "uniform")):
+        types, values = GC.value_column(n_rows, 3, "scaled", scale=scale)
+        for n_keys in (1, lds_keys, lds_keys + 1):
+            indices, words, bits = GC.keys_column(n_rows, n_keys, 3, kind)
+            stats, _ = check(lib, indices, words, bits, types, values, n_keys, what=(scale, n_rows, kind, n_keys), exact_sum=True)
+            sums = stats[:, 5].view(np.float64)
+            assert scale != GC.SCALES[0] or ((np.abs(sums) < 2.0 ** -1022).all() and (sums != 0).any())  # (subnormal sums, and kept)
+
+
 def test_the_128_bit_sum(lib, lds_keys):
     """1025 x INT64_MAX, 1025 x INT64_MIN and a mix that cancels, on both paths"""
     n = 1025
