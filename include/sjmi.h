@@ -1065,8 +1065,9 @@ int sjmi_group_stats_device(sjmi_ctx* ctx, const void* d_indices, const void* d_
  * ascending) -- a strict total order -- and gathers the carried cells.  Nothing spins or waits for another workgroup; the scratch
  * is read across kernel boundaries only.
  * KNOWN LIMITS.  k <= SJMI_TOP_MAX_K: the final sort is one workgroup's.  n_rows < 2^32: a row index travels as 32 bits inside
- * the kernels, and a histogram bin is 32 bits.  Every digit pass reads the key column again.  Out of scope: a full sort, an order
- * across longs and doubles as real numbers, string keys, several sort columns, top k per group. */
+ * the kernels, and a histogram bin is 32 bits.  Every digit pass reads the key column again.  A full sort, and an order by
+ * several columns, is sjmi_sort_rows_device below.  Out of scope: an order across longs and doubles as real numbers, string keys,
+ * top k per group. */
 #define SJMI_TOP_LONG 1u
 #define SJMI_TOP_DOUBLE 2u
 #define SJMI_TOP_SMALLEST 1u               /* flags: the k smallest, smallest first */
@@ -1080,6 +1081,72 @@ int sjmi_top_rows_device(sjmi_ctx* ctx, const void* d_key_types, const void* d_k
                          const void* d_row_count, uint32_t kind, uint32_t flags, uint64_t k, const void* d_types, const void* d_values,
                          uint64_t n_cols, uint64_t col_stride, void* d_rows, void* d_out_types, void* d_out_values, void* d_result,
                          void* stream);
+
+/* ---- all rows ordered by a column: a stable sort, chainable over several keys, on the device ------------------------------
+ * "The exploded statuses ordered by created_at", "by (lang, retweet_count descending)", "in key order for a merge": ALL live rows
+ * ordered by the value of ONE key column, with the cells of any number of carried columns, where sjmi_top_rows_device stops at
+ * k = 2048 (csrc/sortrows.hip, csrc/sj_sortrows.h).  The sort is STABLE: equal keys keep their input order, so an
+ * order by several columns is a chain of these calls, last key first, each taking the d_rows of the one before as its d_rows_in;
+ * a sort of a filter's selection is the same call with the selection vector as d_rows_in.
+ *
+ * INPUTS.  The key column, n_source_rows rows: d_key_values, d_key_types, d_key_validity as sjmi_top_rows_device takes them (types
+ * or validity or both may be NULL).  The call orders POSITIONS [0, live), live = min(n_rows, *d_row_count), the count read on the
+ * device exactly as sjmi_top_rows_device reads it (NULL: n_rows).  Position i stands for source row d_rows_in[i] (uint64[n_rows],
+ * 8-byte aligned), or for row i when d_rows_in is NULL (then n_rows <= n_source_rows).  A position whose entry is at or above
+ * n_source_rows is a BAD position: it is never dereferenced, it is counted in n_bad, and it is ordered with the NULLs.  Positions
+ * at or above live are not read.  A row is read in the order validity word, type byte, value word, each only behind the test in
+ * front of it: the value word behind a type byte that makes no candidate is never read.  d_rows must not alias d_rows_in.
+ * MEANING.  The classes are those of sjmi_top_rows_device -- CANDIDATE, NaN, OTHER, NULL --, and SJMI_SORT_LONG / SJMI_SORT_DOUBLE
+ * mean what SJMI_TOP_LONG / SJMI_TOP_DOUBLE mean, the conversion of 'l' cells under DOUBLE and n_inexact included.  Doubles are
+ * ordered by IEEE totalOrder on the non-NaN values, -0.0 < +0.0.
+ * OUTPUT.  All live positions come out: the candidates first, by ascending value (descending under SJMI_SORT_DESCENDING), then the
+ * NaN positions, then OTHER, then NULL together with the BAD positions.  Inside every class, and among equal values, positions
+ * are ASCENDING -- under SJMI_SORT_DESCENDING too: the key is complemented, the tie rule does not change.  d_rows, uint64[n_rows]:
+ * d_rows[j], j < live, is the source row at output place j; a BAD position stores its entry unchanged.  d_out_types[c *
+ * out_stride + j] / d_out_values[c * out_stride + j] are that row's cell in carried column c (d_types / d_values, n_cols columns
+ * col_stride >= n_source_rows cells apart; n_cols may be 0), type byte 0 and value 0 for a BAD position.  Entries at or behind
+ * live are not written, and nothing before or behind the buffers is touched.  The record, sjmi_sort_result, nine uint64 words,
+ * always complete: n_rows = live, n_candidates, n_null (without the BAD positions), n_other, n_nan, n_inexact, n_bad, n_passes =
+ * the digit passes that moved data, 0 to 8, flags = SJMI_SORT_BAD_ROW iff n_bad > 0.  n_candidates + n_null + n_other + n_nan +
+ * n_bad == n_rows.  THE WHOLE OUTPUT IS A FUNCTION OF THE INPUT ALONE.
+ * THE EMPTY CASES.  n_rows == 0, live == 0, a column without candidates and n_cols == 0 are legal; no kernel is launched with an
+ * empty grid.
+ * ARGUMENTS.  SJMI_ERR_ARG: NULL d_result; an unknown kind; a flag other than SJMI_SORT_DESCENDING; n_source_rows or n_rows >=
+ * 2^32; NULL d_rows_in with n_rows > n_source_rows; NULL d_key_values with n_source_rows > 0 and n_rows > 0; NULL d_rows with
+ * n_rows > 0; with n_cols > 0: col_stride < n_source_rows, out_stride < n_rows, or with n_rows > 0 a NULL d_types, d_values,
+ * d_out_types or d_out_values; d_key_validity, d_key_values, d_rows_in, d_row_count, d_values, d_rows, d_out_values or d_result
+ * not 8-byte aligned.
+ * STREAM AND STATE.  Asynchronous on `stream` (NULL = the context's), no host synchronisation, no memset node.  The context owns a
+ * scratch slot of its own for this call (24 bytes per position for the two pair buffers, 2 KiB per 4096 positions, 16 bytes per
+ * 1024 positions, 2 KiB); when it has to grow, the device is drained first.  Calls on one context that share it must be ordered
+ * by the caller, as for sjmi_filter_columns_device.  The call leaves nothing else on the context and forgets nothing.  All
+ * buffers are device memory.
+ * KERNELS.  A stable least-significant-digit radix sort of (64-bit order-preserving key, 32-bit position) pairs: a pass over the
+ * positions for the counts and the candidates' minimum and maximum key -- the bits above the highest bit in which they differ are
+ * common to all candidates and are skipped: n_passes = ceil((that bit + 1) / 8) --; the filter's three-pass scheme with four
+ * counts per 1024 positions puts the candidates into a pair buffer in position order and every other position at its final place
+ * behind them; per 8-bit digit, lowest first, a count of the 256 digit values per tile of 4096 pairs, 256 workgroups that scan one
+ * value's counts over the tiles each, and a scatter through LDS into the other buffer; then a gather, a lane per output place.  A pair's rank
+ * inside its tile is a function of the data: eight ballots give a lane the lanes of its wave with its digit value, every wave
+ * walks a run of consecutive pairs in order, and the waves' counts are scanned in wave order -- no atomic hands out a slot.
+ * Nothing spins or waits for another workgroup; the scratch is read across kernel boundaries only.
+ * KNOWN LIMITS.  n_source_rows and n_rows < 2^32: a position travels as 32 bits.  A tile's pairs are put in output order in LDS
+ * before they are stored, so a value's run of a tile is stored side by side; with 256 values in use a run is 16 pairs.
+ * Thirty-one launches per call whatever the size.  Out of scope: string keys, an order across
+ * longs and doubles as real numbers, a segmented sort / top k per group, a Java handle. */
+#define SJMI_SORT_LONG 1u
+#define SJMI_SORT_DOUBLE 2u
+#define SJMI_SORT_DESCENDING 1u            /* flags: the candidates by descending value (ties still by ascending position) */
+#define SJMI_SORT_BAD_ROW 1u               /* result flags: an entry of d_rows_in at or above n_source_rows was met */
+#define SJMI_SORT_RESULT_WORDS 9u
+typedef struct sjmi_sort_result {
+    uint64_t n_rows, n_candidates, n_null, n_other, n_nan, n_inexact, n_bad, n_passes;
+    uint32_t flags, reserved;
+} sjmi_sort_result;
+int sjmi_sort_rows_device(sjmi_ctx* ctx, const void* d_key_types, const void* d_key_validity, const void* d_key_values,
+                          uint64_t n_source_rows, const void* d_rows_in, uint64_t n_rows, const void* d_row_count, uint32_t kind,
+                          uint32_t flags, const void* d_types, const void* d_values, uint64_t n_cols, uint64_t col_stride, void* d_rows,
+                          void* d_out_types, void* d_out_values, uint64_t out_stride, void* d_result, void* stream);
 
 /* ---- the document of every exploded row, and that document's cells on the row, on the device -------------------------------
  * "Commits per /actor/login", "the longest commit messages with their event's /type": sjmi_select_batch_device gives one cell per

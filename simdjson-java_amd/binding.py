@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_HERE)
 _CSRC = os.path.join(_HERE, "csrc")
 _LIB = os.path.join(_HERE, "libsjmi.so")
-SOURCES = ["stage1.hip", "strings.hip", "batch.hip", "walk.hip", "coop_walk.hip", "masks.hip", "select.hip", "explode.hip", "ndjson.hip", "strcol.hip", "filter.hip", "arrowcol.hip", "timecol.hip", "dictcol.hip", "census.hip", "groupstats.hip", "toprows.hip", "parents.hip", "sjmi_api.hip", "host/simdjson_parser.cpp"]
+SOURCES = ["stage1.hip", "strings.hip", "batch.hip", "walk.hip", "coop_walk.hip", "masks.hip", "select.hip", "explode.hip", "ndjson.hip", "strcol.hip", "filter.hip", "arrowcol.hip", "timecol.hip", "dictcol.hip", "census.hip", "groupstats.hip", "toprows.hip", "sortrows.hip", "parents.hip", "sjmi_api.hip", "host/simdjson_parser.cpp"]
 
 ST_UTF8, ST_UNCLOSED, ST_UNESCAPED, ST_CAPACITY, ST_INTERNAL = 1, 2, 4, 0x100, 0x200
 PADDING = 64
@@ -182,6 +182,7 @@ ABI = {
     "sjmi_key_census_device": (I, (P, P, P, P, U64, P, U64, P, P, P)),
     "sjmi_group_stats_device": (I, (P, P, P, P, P, U64, P, U64, P, P, P)),
     "sjmi_top_rows_device": (I, (P, P, P, P, U64, P, U32, U32, U64, P, P, U64, U64, P, P, P, P, P)),
+    "sjmi_sort_rows_device": (I, (P, P, P, P, U64, P, U64, P, U32, U32, P, P, U64, U64, P, P, P, U64, P, P)),
     "sjmi_parent_columns_device": (I, (P, P, U64, P, U64, P, P, P, U64, U64, P, P, P, P, U64, P, P)),
     "sjmi_host_register": (I, (P, P, U64)),
     "sjmi_set_input_staging": (I, (P, P, U64)),
@@ -607,6 +608,22 @@ class Context:
                                                d_row_count or None, kind, flags, k, d_types or None, d_values or None, n_cols, col_stride,
                                                d_rows or None, d_out_types or None, d_out_values or None, d_result or None, stream),
                     "sjmi_top_rows_device")
+
+    def sort_rows_device(self, d_key_types, d_key_validity, d_key_values, n_source_rows, d_rows_in, n_rows, d_row_count, kind, flags,
+                         d_types, d_values, n_cols, col_stride, d_rows, d_out_types, d_out_values, out_stride, d_result, stream=0):
+        """sjmi_sort_rows_device: ALL live positions ordered by the value of ONE key column, a stable sort (equal values keep
+        their input order: chain the calls, last key first, for several keys).  The key column of n_source_rows rows as
+        top_rows_device takes it; d_rows_in (None / 0: position i is row i; else uint64 [n_rows] source rows, an entry at or above
+        n_source_rows a BAD position that is ordered with the nulls); d_row_count (None / 0: every position) = a device uint64
+        that holds the live positions; kind = SORT_LONG or SORT_DOUBLE, flags = 0 or SORT_DESCENDING; d_types / d_values = n_cols
+        carried columns col_stride >= n_source_rows cells apart (None / 0 with n_cols 0); d_rows (uint64 [n_rows], not
+        d_rows_in), d_out_types (uint8) / d_out_values (uint64), n_cols rows out_stride >= n_rows cells apart; d_result = device
+        sjmi_sort_result (9 x int64: live positions, n_candidates, n_null, n_other, n_nan, n_inexact, n_bad, n_passes, flags in
+        the low half of the ninth).  Both row counts < 2^32.  Asynchronous on `stream`."""
+        self._check(lib().sjmi_sort_rows_device(self._h, d_key_types or None, d_key_validity or None, d_key_values or None, n_source_rows,
+                                                d_rows_in or None, n_rows, d_row_count or None, kind, flags, d_types or None, d_values or None,
+                                                n_cols, col_stride, d_rows or None, d_out_types or None, d_out_values or None, out_stride,
+                                                d_result or None, stream), "sjmi_sort_rows_device")
 
     def parent_columns_device(self, d_row_offsets, n_docs, d_rows, n_rows, d_row_count, d_types, d_values, n_cols, col_stride,
                               d_parent_types, d_parents, d_out_types, d_out_values, out_stride, d_result, stream=0):

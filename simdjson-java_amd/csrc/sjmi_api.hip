@@ -139,6 +139,7 @@ struct sjmi_ctx {
     DevBuf<void> d_ws_time;                  // sjmi_time_columns_device: a packed count word per field and chunk of rows (a slot of its own)
     DevBuf<void> d_ws_dict;                  // sjmi_dictionary_column_device: the hash table, a slot per row, the chunk counts, the compacted dictionary column (a slot of its own)
     DevBuf<void> d_ws_top;                   // sjmi_top_rows_device: the select's state and histograms, a word per chunk of rows, k (key, row) pairs (a slot of its own)
+    DevBuf<void> d_ws_sort;                  // sjmi_sort_rows_device: the state, the chunk and tile counts, two buffers of n_rows (key, position) pairs (a slot of its own)
     std::string err;
 };
 
@@ -1154,6 +1155,30 @@ int sjmi_top_rows_device(sjmi_ctx* c, const void* d_key_types, const void* d_key
     if (!grow_scratch(c, c->d_ws_top, sjmi::toprows_workspace_bytes(n_rows, k), "hipMalloc(ws_top)")) return SJMI_ERR_HIP;
     return fail(c, "top rows launch", sjmi::toprows_launch(d_key_types, d_key_validity, d_key_values, n_rows, d_row_count, kind, flags, k, d_types,
                                                            d_values, n_cols, col_stride, d_rows, d_out_types, d_out_values, d_result, c->d_ws_top, st))
+               ? SJMI_ERR_HIP
+               : SJMI_OK;
+}
+
+int sjmi_sort_rows_device(sjmi_ctx* c, const void* d_key_types, const void* d_key_validity, const void* d_key_values, uint64_t n_source_rows,
+                          const void* d_rows_in, uint64_t n_rows, const void* d_row_count, uint32_t kind, uint32_t flags, const void* d_types,
+                          const void* d_values, uint64_t n_cols, uint64_t col_stride, void* d_rows, void* d_out_types, void* d_out_values,
+                          uint64_t out_stride, void* d_result, void* stream) {
+    if (!c || !d_result || (n_source_rows && n_rows && !d_key_values) || (n_rows && !d_rows)) return SJMI_ERR_ARG;
+    if ((kind != SJMI_SORT_LONG && kind != SJMI_SORT_DOUBLE) || (flags & ~SJMI_SORT_DESCENDING)) return SJMI_ERR_ARG;
+    if (n_rows >= (1ull << 32) || n_source_rows >= (1ull << 32)) return SJMI_ERR_ARG;  // (a position travels as 32 bits, and so does a count)
+    if (!d_rows_in && n_rows > n_source_rows) return SJMI_ERR_ARG;
+    if (n_cols && (col_stride < n_source_rows || out_stride < n_rows || (n_rows && (!d_types || !d_values || !d_out_types || !d_out_values))))
+        return SJMI_ERR_ARG;
+    if (((uintptr_t)d_key_validity & 7) || ((uintptr_t)d_key_values & 7) || ((uintptr_t)d_rows_in & 7) || ((uintptr_t)d_row_count & 7) ||
+        ((uintptr_t)d_values & 7) || ((uintptr_t)d_rows & 7) || ((uintptr_t)d_out_values & 7) || ((uintptr_t)d_result & 7))
+        return SJMI_ERR_ARG;
+    if (n_cols && (col_stride > ~0ull / 8 / n_cols || out_stride > ~0ull / 8 / n_cols)) return SJMI_ERR_ARG;  // (a column set is addressable)
+    if (fail(c, "hipSetDevice", hipSetDevice(c->device))) return SJMI_ERR_HIP;
+    hipStream_t st = stream_of(c, stream);
+    if (!grow_scratch(c, c->d_ws_sort, sjmi::sortrows_workspace_bytes(n_rows), "hipMalloc(ws_sort)")) return SJMI_ERR_HIP;
+    return fail(c, "sort rows launch",
+                sjmi::sortrows_launch(d_key_types, d_key_validity, d_key_values, n_source_rows, d_rows_in, n_rows, d_row_count, kind, flags, d_types,
+                                      d_values, n_cols, col_stride, d_rows, d_out_types, d_out_values, out_stride, d_result, c->d_ws_sort, st))
                ? SJMI_ERR_HIP
                : SJMI_OK;
 }

@@ -475,6 +475,18 @@ hipError_t toprows_launch(const void* d_key_types, const void* d_key_validity, c
                           uint32_t kind, uint32_t flags, uint64_t k, const void* d_types, const void* d_values, uint64_t n_cols,
                           uint64_t col_stride, void* d_rows, void* d_out_types, void* d_out_values, void* d_result, void* d_ws, hipStream_t stream);
 
+// ---- all rows ordered by a key column: a stable radix sort (sortrows.hip) ----
+// scratch of one call: the state, two words per chunk of 1024 positions, 256 words per tile of 4096 pairs, 256 totals, two buffers
+// of n_rows (key, 32-bit position) pairs
+size_t sortrows_workspace_bytes(uint64_t n_rows);
+// k_sort_clear, with n_rows != 0 k_sort_range, k_sort_plan (the sjmi_sort_result at d_result) and, with n_rows != 0, k_sort_count,
+// k_sort_scan, k_sort_emit, eight times k_sort_hist + k_sort_digit_scan + k_sort_scatter, and k_sort_gather (d_rows, the carried
+// cells).  d_key_types, d_key_validity, d_rows_in and d_row_count may be NULL; d_row_count is read by the kernels
+hipError_t sortrows_launch(const void* d_key_types, const void* d_key_validity, const void* d_key_values, uint64_t n_source_rows,
+                           const void* d_rows_in, uint64_t n_rows, const void* d_row_count, uint32_t kind, uint32_t flags, const void* d_types,
+                           const void* d_values, uint64_t n_cols, uint64_t col_stride, void* d_rows, void* d_out_types, void* d_out_values,
+                           uint64_t out_stride, void* d_result, void* d_ws, hipStream_t stream);
+
 // ---- the document of every exploded row, and that document's cells on the row (parents.hip) ----
 // k_parent_clear (the sjmi_parent_result at d_result) and, with n_rows != 0, k_parent_dense (d_rows NULL) or k_parent_sparse; no
 // scratch.  d_row_count, d_parent_types, d_parents and, with n_cols == 0, the column pointers may be NULL; d_row_count is read by

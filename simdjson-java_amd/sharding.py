@@ -88,6 +88,20 @@ def _column_set(types, values, n_rows):
     return n_cols, stride, n_rows
 
 
+def _key_column(key_types, key_values, key_validity, n_rows):
+    """the 1-D key column of top_rows() / sort_rows() (types uint8 or None, values int64, validity int64 words or None) with at
+    least n_rows rows (default: all of key_values) -> n_rows"""
+    import torch
+    assert key_values.dim() == 1 and key_values.dtype == torch.int64 and key_values.is_contiguous()
+    n_rows = int(key_values.numel()) if n_rows is None else int(n_rows)
+    assert 0 <= n_rows <= int(key_values.numel())
+    assert key_types is None or (key_types.dim() == 1 and key_types.dtype == torch.uint8 and key_types.is_contiguous() and
+                                 int(key_types.numel()) >= n_rows)
+    assert key_validity is None or (key_validity.dtype == torch.int64 and key_validity.is_contiguous() and
+                                    int(key_validity.numel()) >= (n_rows + 63) // 64)
+    return n_rows
+
+
 def _check_row_count(row_count, types):
     import torch
     if row_count is not None:
@@ -97,6 +111,7 @@ def _check_row_count(row_count, types):
 GROUP_STATS_WORDS = 10  # SJMI_GROUP_STATS_WORDS
 TOP_KINDS = {"long": 1, "double": 2}  # SJMI_TOP_LONG, SJMI_TOP_DOUBLE
 TOP_SMALLEST, TOP_MAX_K, TOP_RESULT_WORDS = 1, 2048, 9  # SJMI_TOP_SMALLEST, SJMI_TOP_MAX_K, SJMI_TOP_RESULT_WORDS
+SORT_DESCENDING, SORT_BAD_ROW, SORT_RESULT_WORDS = 1, 1, 9  # SJMI_SORT_DESCENDING, SJMI_SORT_BAD_ROW, SJMI_SORT_RESULT_WORDS (the kinds: TOP_KINDS)
 PARENT_MAX_COLS, PARENT_RESULT_WORDS = 64, 3  # SJMI_PARENT_MAX_COLS, SJMI_PARENT_RESULT_WORDS
 
 
@@ -458,13 +473,8 @@ class BatchShard:
         step that check() had to run again."""
         import torch
         assert kind in TOP_KINDS, "top_rows(): kind is 'long' or 'double'"
-        assert key_values.dim() == 1 and key_values.dtype == torch.int64 and key_values.is_contiguous()
-        n_rows, k = int(key_values.numel()) if n_rows is None else int(n_rows), int(k)
-        assert 0 <= n_rows <= int(key_values.numel()) and 0 <= k <= TOP_MAX_K
-        assert key_types is None or (key_types.dim() == 1 and key_types.dtype == torch.uint8 and key_types.is_contiguous() and
-                                     int(key_types.numel()) >= n_rows)
-        assert key_validity is None or (key_validity.dtype == torch.int64 and key_validity.is_contiguous() and
-                                        int(key_validity.numel()) >= (n_rows + 63) // 64)
+        n_rows, k = _key_column(key_types, key_values, key_validity, n_rows), int(k)
+        assert 0 <= k <= TOP_MAX_K
         _check_row_count(row_count, key_values)
         n_cols = stride = 0
         if types is not None:
@@ -478,6 +488,58 @@ class BatchShard:
                                     0 if largest else TOP_SMALLEST, k, _ptr(types, n_cols), _ptr(values, n_cols), n_cols, stride, _ptr(rows, k),
                                     _ptr(out_types, n_cols * k), _ptr(out_values, n_cols * k), result.data_ptr(), stream)
         return rows, out_types, out_values, result
+
+    def sort_rows(self, keys, types=None, values=None, rows=None, n_rows=None, row_count=None, stream=0):
+        """ORDER BY one or several columns, all rows: a chain of sjmi_sort_rows_device calls, a stable sort each, from the LAST key
+        to the first.  keys: a list of (key_types, key_values, kind, descending[, key_validity]), most significant first -- each
+        a 1-D key column as top_rows() takes it, all with the same number of source rows, kind "long" or "double".  rows=None:
+        position i is source row i and n_rows defaults to the source rows; with rows (1-D int64: filter()'s selection vector, in
+        any order, duplicates legal) position i is row rows[i] and n_rows defaults to rows.numel(); an entry outside the source
+        rows is a BAD position, counted and ordered with the nulls.  row_count as for arrow_columns(): the live positions are
+        min(n_rows, row_count[0]).  types / values: a 2-D [n_cols, stride] pair of columns to carry along (stride at least the
+        source rows), or None; they are gathered by the last call only.  -> (rows [n_rows] int64: the source row at every
+        output place -- the candidates by value, then NaN, OTHER, NULL and BAD positions, equal ones in input order --;
+        out_types [n_cols, n_rows] uint8 and out_values [n_cols, n_rows] int64: the carried cells of these rows, the layout of
+        filter()'s compacted pair; records [len(keys), 9] int64: records[i] is the sjmi_sort_result of keys[i] = live positions,
+        n_candidates, n_null, n_other, n_nan, n_inexact, n_bad, n_passes, flags), new tensors every call; entries at or behind
+        the live positions are not written.  The calls exchange two row buffers of the shard's own making; `rows` is only read.
+        Everything is a function of the input alone.  Nothing synchronises.  Call it on a step that check() has accepted: like
+        top_rows(), it is not queued again behind a step that check() had to run again."""
+        import torch
+        assert len(keys) >= 1, "sort_rows(): at least one key"
+        n_source = int(keys[0][1].numel())
+        for key in keys:
+            assert len(key) in (4, 5) and key[2] in TOP_KINDS, "sort_rows(): a key is (types, values, kind, descending[, validity])"
+            assert _key_column(key[0], key[1], key[4] if len(key) == 5 else None, None) == n_source
+        if rows is None:
+            n_rows = n_source if n_rows is None else int(n_rows)
+            assert 0 <= n_rows <= n_source
+        else:
+            assert rows.dim() == 1 and rows.dtype == torch.int64 and rows.is_contiguous()
+            n_rows = int(rows.numel()) if n_rows is None else int(n_rows)
+            assert 0 <= n_rows <= int(rows.numel())
+        _check_row_count(row_count, keys[0][1])
+        n_cols = stride = 0
+        if types is not None:
+            n_cols, stride, _ = _column_set(types, values, n_source)
+        buffers = [torch.empty(n_rows, dtype=torch.int64, device=self.device) for _ in range(min(2, len(keys)))]
+        out_types = torch.empty((n_cols, n_rows), dtype=torch.uint8, device=self.device)
+        out_values = torch.empty((n_cols, n_rows), dtype=torch.int64, device=self.device)
+        records = torch.empty((len(keys), SORT_RESULT_WORDS), dtype=torch.int64, device=self.device)  # (every call writes all of its own)
+        source = rows
+        for call, at in enumerate(range(len(keys) - 1, -1, -1)):
+            key_types, key_values, kind, descending = keys[at][:4]
+            key_validity = keys[at][4] if len(keys[at]) == 5 else None
+            carry = n_cols if at == 0 else 0  # (the carried cells follow the final order only)
+            out = buffers[call % 2]
+            self.engine.sort_rows_device(_ptr(key_types, key_types is not None and n_source), _ptr(key_validity, key_validity is not None and n_source),
+                                         _ptr(key_values, n_source), n_source, _ptr(source, source is not None and n_rows), n_rows,
+                                         _ptr(row_count, row_count is not None), TOP_KINDS[kind], SORT_DESCENDING if descending else 0,
+                                         _ptr(types, carry), _ptr(values, carry), carry, stride if carry else 0, _ptr(out, n_rows),
+                                         _ptr(out_types, carry * n_rows), _ptr(out_values, carry * n_rows), n_rows if carry else 0,
+                                         records[at].data_ptr(), stream)
+            source = out
+        return source, out_types, out_values, records
 
     def parent_columns(self, row_offsets, types, values, rows=None, n_rows=None, row_count=None, with_parents=True, stream=0):
         """The document of every exploded row, and that document's cells on the row (pandas.json_normalize's meta, SQL's UNNEST
