@@ -1203,6 +1203,95 @@ int sjmi_parent_columns_device(sjmi_ctx* ctx, const void* d_row_offsets, uint64_
                                void* d_parent_types, void* d_parents, void* d_out_types, void* d_out_values, uint64_t out_stride,
                                void* d_result, void* stream);
 
+/* ---- two row sets joined on a long key: inner, left, semi, anti, on the device -----------------------------------------------
+ * "Every event with the columns of its actor's row in the users file", "every status whose /retweeted_status/user/id is mentioned
+ * somewhere in the batch, with the mention": an equi-join of a LEFT (probe) row set with a RIGHT (build) row set on one integer
+ * key a side (csrc/joinrows.hip, csrc/sj_joinrows.h).
+ *
+ * A SIDE, sjmi_join_side, is read from HOST memory during the call (as the terms of sjmi_filter_plan_compile are); the pointers
+ * in it are device memory: the key column of n_source_rows rows as sjmi_sort_rows_device takes it (d_key_types or d_key_validity
+ * or both may be NULL), and n_cols carried columns d_types / d_values, col_stride >= n_source_rows cells apart (NULL with n_cols
+ * == 0).
+ * THE LEFT SIDE.  Positions [0, live_left), live_left = min(n_left, *d_left_count), the count read on the device (NULL: n_left).
+ * Position i stands for source row d_left_rows_in[i] (uint64[n_left]), or for row i when d_left_rows_in is NULL (then n_left <=
+ * n_source_rows).  A position is classified exactly as sjmi_sort_rows_device classifies it under SJMI_SORT_LONG -- CANDIDATE, NULL,
+ * OTHER (a 'd' cell is OTHER), BAD (an entry at or above n_source_rows: never dereferenced) --, its cell read in the same order:
+ * validity word, type byte, value word, each only behind the test in front of it.
+ * THE RIGHT SIDE has been ordered by the caller with sjmi_sort_rows_device, kind SJMI_SORT_LONG, ascending: d_right_order is that
+ * call's d_rows, d_right_sort_result its record IN DEVICE MEMORY, n_right its n_rows.  The join reads n_candidates from the
+ * record on the device; the BUILD SET is the first n_build = min(n_right, n_candidates) entries of d_right_order, and nothing
+ * behind them is read.  A right side is therefore sorted once and probed by many left batches, and may be a filter's selection or
+ * stand behind a device row count, because the sort took both.  WILD INPUT: an entry of the build set at or above
+ * right->n_source_rows is never dereferenced; such an entry, an entry whose cell is not a CANDIDATE (both counted in n_right_bad)
+ * and an adjacent pair of build keys that descends each set SJMI_JOIN_BAD_ORDER.  The pairs are then unspecified; every load and
+ * store still stays inside its buffer.
+ * THE RELATION.  m(i) = the number of build places whose key equals the key of candidate position i, 0 for every other class.
+ * Position i emits e(i) pairs: SJMI_JOIN_INNER m(i); SJMI_JOIN_LEFT max(m(i), 1); SJMI_JOIN_SEMI m(i) > 0; SJMI_JOIN_ANTI m(i) ==
+ * 0.  For LEFT and ANTI that is every live position, NULL, OTHER and BAD ones included: SQL's rule for a null key.
+ * OUTPUT.  Pairs come out by ascending left position, inside one position by ascending build place -- the sort is stable, so
+ * among equal keys by ascending right position.  Pair j < min(n_pairs, pair_capacity): d_left_rows[j] = the source row of its left
+ * position (a BAD entry unchanged); d_right_rows[j] = the matching right source row, SJMI_JOIN_NO_ROW for the unmatched pair of
+ * LEFT and for every ANTI pair (d_right_rows may be NULL under SEMI and ANTI; under SEMI it is the first match); the carried cells
+ * d_left_out_* / d_right_out_*[c * out_stride + j], type 0 and value 0 where the row is BAD or NO_ROW.  Nothing at or behind
+ * min(n_pairs, pair_capacity) is written, and nothing outside the buffers.  d_pair_offsets, optional, uint64[n_left + 1]: off[i]
+ * = the pairs in front of position i, i <= live_left, the TRUE count, not clipped by the capacity; entries behind live_left are
+ * not written.  It has the layout of an explode's row_offsets: sjmi_parent_columns_device reads it as "left position = document,
+ * pair = row".  The record, sjmi_join_result, nine uint64 words, always complete: n_left = live_left, n_build, n_pairs (the true
+ * total: both sides are below 2^32, it cannot wrap), n_matched = the positions with m > 0, n_null, n_other, n_bad over the left,
+ * n_right_bad, flags = SJMI_JOIN_OVERFLOW iff n_pairs > pair_capacity, SJMI_JOIN_BAD_ROW iff n_bad > 0, SJMI_JOIN_BAD_ORDER.  THE
+ * WHOLE OUTPUT IS A FUNCTION OF THE INPUT ALONE: no atomic decides a place.
+ * ARGUMENTS.  SJMI_ERR_ARG: NULL left, right or d_result; an unknown how; n_left, n_right or a side's n_source_rows >= 2^32;
+ * pair_capacity >= SJMI_JOIN_MAX_PAIR_CAPACITY; NULL d_left_rows_in with n_left > left->n_source_rows; a NULL key values pointer
+ * of a side with source rows and positions; NULL d_right_sort_result or d_right_order with n_right != 0; NULL d_left_rows with
+ * pair_capacity != 0; NULL d_right_rows under INNER or LEFT with pair_capacity != 0; with carried columns on a side: col_stride
+ * < n_source_rows, out_stride < pair_capacity, or with pair_capacity != 0 a NULL column or output pointer; right carried columns
+ * under SEMI or ANTI; a uint64 pointer (key validity, key values, carried values, d_left_rows_in, d_left_count, d_right_order,
+ * d_right_sort_result, d_left_rows, d_right_rows, both out values, d_pair_offsets, d_result) not 8-byte aligned.
+ * STREAM AND STATE.  Asynchronous on `stream` (NULL = the context's), no host synchronisation, no memset node.  The context owns a
+ * scratch slot of its own for this call (8 bytes per build place, 16 bytes per left position, 8 bytes per 1024 left positions);
+ * when it has to grow, the device is drained first.  Calls on one context that share it must be ordered by the caller.  The call
+ * leaves nothing else on the context and forgets nothing.
+ * KERNELS.  The build keys are gathered once into a dense sorted array (and checked: bad places, descending neighbours); every
+ * left position is classified and finds the lower bound of its key there through 1024 pivots that its workgroup keeps in LDS,
+ * and the upper bound by galloping from the lower one (a unique key: three loads; at most 33 + 33 steps); the filter's
+ * three-pass scheme turns e(i) into the pair offsets; the pairs are written by
+ * one workgroup per 1024 OUTPUT pairs, which finds the owners of its pairs with the load-balanced search of
+ * sjmi_parent_columns_device's dense form on the offsets -- so one position with a million matches is a thousand output chunks of
+ * equal cost.  Nothing spins or waits for another workgroup; the scratch is read across kernel boundaries only; the atomics
+ * (agent scope, relaxed, results unused) touch the record only.
+ * KNOWN LIMITS.  The caller sizes pair_capacity; on SJMI_JOIN_OVERFLOW it reads n_pairs and calls again, as with
+ * sjmi_filter_columns_device.  The emit's grid is sized by pair_capacity, not by n_pairs.  A probe is a chain of dependent loads
+ * a position.  Out of scope: double, string and composite keys, right and full outer joins, a merge path for a sorted left side, a
+ * hash-table build, paging through the pairs, a Java handle. */
+#define SJMI_JOIN_INNER 0u
+#define SJMI_JOIN_LEFT 1u
+#define SJMI_JOIN_SEMI 2u
+#define SJMI_JOIN_ANTI 3u
+#define SJMI_JOIN_OVERFLOW 1u              /* result flags: n_pairs > pair_capacity */
+#define SJMI_JOIN_BAD_ROW 2u               /* result flags: an entry of d_left_rows_in at or above the left source rows was met */
+#define SJMI_JOIN_BAD_ORDER 4u             /* result flags: the build set is not what an ascending LONG sort of the right side wrote */
+#define SJMI_JOIN_NO_ROW 0xFFFFFFFFFFFFFFFFull
+#define SJMI_JOIN_RESULT_WORDS 9u
+#define SJMI_JOIN_MAX_PAIR_CAPACITY (1ull << 40)
+typedef struct sjmi_join_side {
+    const void* d_key_types;     /* uint8, any alignment, or NULL (every valid row is a long) */
+    const void* d_key_validity;  /* uint64 words or NULL */
+    const void* d_key_values;    /* uint64 */
+    uint64_t n_source_rows;      /* rows of the key column and of the carried columns */
+    const void* d_types;         /* carried columns [n_cols * col_stride], or NULL with n_cols == 0 */
+    const void* d_values;
+    uint64_t n_cols, col_stride;
+} sjmi_join_side;
+typedef struct sjmi_join_result {
+    uint64_t n_left, n_build, n_pairs, n_matched, n_null, n_other, n_bad, n_right_bad;
+    uint32_t flags, reserved;
+} sjmi_join_result;
+int sjmi_join_rows_device(sjmi_ctx* ctx, const sjmi_join_side* left, const void* d_left_rows_in, uint64_t n_left, const void* d_left_count,
+                          const sjmi_join_side* right, const void* d_right_order, uint64_t n_right, const void* d_right_sort_result,
+                          uint32_t how, uint64_t pair_capacity, void* d_left_rows, void* d_right_rows, void* d_left_out_types,
+                          void* d_left_out_values, void* d_right_out_types, void* d_right_out_values, uint64_t out_stride,
+                          void* d_pair_offsets, void* d_result, void* stream);
+
 /* Optional: page-lock caller-owned host memory that is passed to the host-buffer entry points again and again
  * (SimdJsonParser's padded input, index array and string buffer): H2D / D2H copies of pinned memory skip the
  * driver's staging copy (3-4x faster for the ~1 MB transfers of a single-document parse).  Purely a performance

@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_HERE)
 _CSRC = os.path.join(_HERE, "csrc")
 _LIB = os.path.join(_HERE, "libsjmi.so")
-SOURCES = ["stage1.hip", "strings.hip", "batch.hip", "walk.hip", "coop_walk.hip", "masks.hip", "select.hip", "explode.hip", "ndjson.hip", "strcol.hip", "filter.hip", "arrowcol.hip", "timecol.hip", "dictcol.hip", "census.hip", "groupstats.hip", "toprows.hip", "sortrows.hip", "parents.hip", "sjmi_api.hip", "host/simdjson_parser.cpp"]
+SOURCES = ["stage1.hip", "strings.hip", "batch.hip", "walk.hip", "coop_walk.hip", "masks.hip", "select.hip", "explode.hip", "ndjson.hip", "strcol.hip", "filter.hip", "arrowcol.hip", "timecol.hip", "dictcol.hip", "census.hip", "groupstats.hip", "toprows.hip", "sortrows.hip", "parents.hip", "joinrows.hip", "sjmi_api.hip", "host/simdjson_parser.cpp"]
 
 ST_UTF8, ST_UNCLOSED, ST_UNESCAPED, ST_CAPACITY, ST_INTERNAL = 1, 2, 4, 0x100, 0x200
 PADDING = 64
@@ -184,6 +184,7 @@ ABI = {
     "sjmi_top_rows_device": (I, (P, P, P, P, U64, P, U32, U32, U64, P, P, U64, U64, P, P, P, P, P)),
     "sjmi_sort_rows_device": (I, (P, P, P, P, U64, P, U64, P, U32, U32, P, P, U64, U64, P, P, P, U64, P, P)),
     "sjmi_parent_columns_device": (I, (P, P, U64, P, U64, P, P, P, U64, U64, P, P, P, P, U64, P, P)),
+    "sjmi_join_rows_device": (I, (P, P, P, U64, P, P, P, U64, P, U32, U64, P, P, P, P, P, P, U64, P, P, P)),
     "sjmi_host_register": (I, (P, P, U64)),
     "sjmi_set_input_staging": (I, (P, P, U64)),
     "sjmi_host_unregister": (I, (P, P)),
@@ -254,6 +255,22 @@ def _fields(fields, dtype, what, whats, flag_bits):
             bits |= flag_bits[f]
         enc[k] = (int(column), whats[name], bits, 0)
     return enc
+
+
+JOIN_HOWS = {"inner": 0, "left": 1, "semi": 2, "anti": 3}  # SJMI_JOIN_<HOW>
+JOIN_INNER, JOIN_LEFT, JOIN_SEMI, JOIN_ANTI = 0, 1, 2, 3
+JOIN_OVERFLOW, JOIN_BAD_ROW, JOIN_BAD_ORDER = 1, 2, 4    # SJMI_JOIN_<FLAG>: the flags of a sjmi_join_result
+JOIN_NO_ROW, JOIN_RESULT_WORDS = 0xFFFFFFFFFFFFFFFF, 9  # SJMI_JOIN_NO_ROW (-1 as an int64), SJMI_JOIN_RESULT_WORDS
+JOIN_SIDE = np.dtype([("d_key_types", "<u8"), ("d_key_validity", "<u8"), ("d_key_values", "<u8"), ("n_source_rows", "<u8"),
+                      ("d_types", "<u8"), ("d_values", "<u8"), ("n_cols", "<u8"), ("col_stride", "<u8")])  # sjmi_join_side
+
+
+def join_side(d_key_types, d_key_validity, d_key_values, n_source_rows, d_types=0, d_values=0, n_cols=0, col_stride=0):
+    """one side of Context.join_rows_device as the C struct (a numpy record in host memory): the key column of n_source_rows rows
+    as sort_rows_device takes it, and n_cols carried columns col_stride cells apart (None / 0 with n_cols 0)"""
+    side = np.zeros(1, dtype=JOIN_SIDE)
+    side[0] = (d_key_types or 0, d_key_validity or 0, d_key_values or 0, n_source_rows, d_types or 0, d_values or 0, n_cols, col_stride)
+    return side
 
 
 ARROW_KINDS = {"int64": 1, "float64": 2, "bool": 3}     # SJMI_ARROW_<KIND>
@@ -624,6 +641,25 @@ class Context:
                                                 d_rows_in or None, n_rows, d_row_count or None, kind, flags, d_types or None, d_values or None,
                                                 n_cols, col_stride, d_rows or None, d_out_types or None, d_out_values or None, out_stride,
                                                 d_result or None, stream), "sjmi_sort_rows_device")
+
+    def join_rows_device(self, left, d_left_rows_in, n_left, d_left_count, right, d_right_order, n_right, d_right_sort_result, how,
+                         pair_capacity, d_left_rows, d_right_rows, d_left_out_types, d_left_out_values, d_right_out_types,
+                         d_right_out_values, out_stride, d_pair_offsets, d_result, stream=0):
+        """sjmi_join_rows_device: the LEFT positions joined with a sorted RIGHT side on a long key.  left / right: the arguments of
+        join_side() as a tuple (d_key_types, d_key_validity, d_key_values, n_source_rows[, d_types, d_values, n_cols,
+        col_stride]).  d_left_rows_in (None / 0: position i is row i) and d_left_count (None / 0: every position) as
+        sort_rows_device takes them; d_right_order / n_right / d_right_sort_result = d_rows, n_rows and the DEVICE record of a
+        sort_rows_device call (SORT_LONG, ascending) on the right key; how = JOIN_INNER / LEFT / SEMI / ANTI; d_left_rows,
+        d_right_rows (uint64 [pair_capacity]; JOIN_NO_ROW without a match; None / 0 allowed under SEMI and ANTI); the carried cells
+        of both sides, n_cols rows out_stride >= pair_capacity cells apart; d_pair_offsets (None / 0, or uint64 [n_left + 1]);
+        d_result = device sjmi_join_result (9 x int64: live left positions, n_build, n_pairs, n_matched, n_null, n_other, n_bad,
+        n_right_bad, flags in the low half of the ninth).  Asynchronous on `stream`."""
+        l, r = join_side(*left), join_side(*right)
+        self._check(lib().sjmi_join_rows_device(self._h, l.ctypes.data, d_left_rows_in or None, n_left, d_left_count or None, r.ctypes.data,
+                                                d_right_order or None, n_right, d_right_sort_result or None, how, pair_capacity,
+                                                d_left_rows or None, d_right_rows or None, d_left_out_types or None, d_left_out_values or None,
+                                                d_right_out_types or None, d_right_out_values or None, out_stride, d_pair_offsets or None,
+                                                d_result or None, stream), "sjmi_join_rows_device")
 
     def parent_columns_device(self, d_row_offsets, n_docs, d_rows, n_rows, d_row_count, d_types, d_values, n_cols, col_stride,
                               d_parent_types, d_parents, d_out_types, d_out_values, out_stride, d_result, stream=0):

@@ -139,6 +139,7 @@ struct sjmi_ctx {
     DevBuf<void> d_ws_time;                  // sjmi_time_columns_device: a packed count word per field and chunk of rows (a slot of its own)
     DevBuf<void> d_ws_dict;                  // sjmi_dictionary_column_device: the hash table, a slot per row, the chunk counts, the compacted dictionary column (a slot of its own)
     DevBuf<void> d_ws_top;                   // sjmi_top_rows_device: the select's state and histograms, a word per chunk of rows, k (key, row) pairs (a slot of its own)
+    DevBuf<void> d_ws_join;                  // sjmi_join_rows_device: the dense build keys, the chunk sums, the pair offsets, lo and e of every left position (a slot of its own)
     DevBuf<void> d_ws_sort;                  // sjmi_sort_rows_device: the state, the chunk and tile counts, two buffers of n_rows (key, position) pairs (a slot of its own)
     std::string err;
 };
@@ -1179,6 +1180,46 @@ int sjmi_sort_rows_device(sjmi_ctx* c, const void* d_key_types, const void* d_ke
     return fail(c, "sort rows launch",
                 sjmi::sortrows_launch(d_key_types, d_key_validity, d_key_values, n_source_rows, d_rows_in, n_rows, d_row_count, kind, flags, d_types,
                                       d_values, n_cols, col_stride, d_rows, d_out_types, d_out_values, out_stride, d_result, c->d_ws_sort, st))
+               ? SJMI_ERR_HIP
+               : SJMI_OK;
+}
+
+// the argument rules of one side of a join: `positions` = n_left / n_right, rows_in = whether the positions are entries of a row vector
+static bool join_side_ok(const sjmi_join_side* s, uint64_t positions, bool rows_in, uint64_t pair_capacity, uint64_t out_stride,
+                         const void* d_out_types, const void* d_out_values) {
+    if (s->n_source_rows >= (1ull << 32) || positions >= (1ull << 32)) return false;  // (a position travels as 32 bits, and so does a count)
+    if (s->n_source_rows && positions && !s->d_key_values) return false;
+    if (!rows_in && positions > s->n_source_rows) return false;
+    if (s->n_cols && (s->col_stride < s->n_source_rows || out_stride < pair_capacity ||
+                      (pair_capacity && (!s->d_types || !s->d_values || !d_out_types || !d_out_values))))
+        return false;
+    if (s->n_cols && (s->col_stride > ~0ull / 8 / s->n_cols || out_stride > ~0ull / 8 / s->n_cols)) return false;  // (a column set is addressable)
+    return !(((uintptr_t)s->d_key_validity & 7) || ((uintptr_t)s->d_key_values & 7) || ((uintptr_t)s->d_values & 7) || ((uintptr_t)d_out_values & 7));
+}
+
+int sjmi_join_rows_device(sjmi_ctx* c, const sjmi_join_side* left, const void* d_left_rows_in, uint64_t n_left, const void* d_left_count,
+                          const sjmi_join_side* right, const void* d_right_order, uint64_t n_right, const void* d_right_sort_result,
+                          uint32_t how, uint64_t pair_capacity, void* d_left_rows, void* d_right_rows, void* d_left_out_types,
+                          void* d_left_out_values, void* d_right_out_types, void* d_right_out_values, uint64_t out_stride,
+                          void* d_pair_offsets, void* d_result, void* stream) {
+    if (!c || !left || !right || !d_result || how > SJMI_JOIN_ANTI || pair_capacity >= SJMI_JOIN_MAX_PAIR_CAPACITY) return SJMI_ERR_ARG;
+    const bool keeps_right = how == SJMI_JOIN_INNER || how == SJMI_JOIN_LEFT;
+    if (!join_side_ok(left, n_left, d_left_rows_in != nullptr, pair_capacity, out_stride, d_left_out_types, d_left_out_values) ||
+        !join_side_ok(right, n_right, true, pair_capacity, out_stride, d_right_out_types, d_right_out_values))
+        return SJMI_ERR_ARG;
+    if (n_right && (!d_right_order || !d_right_sort_result)) return SJMI_ERR_ARG;
+    if (pair_capacity && (!d_left_rows || (keeps_right && !d_right_rows))) return SJMI_ERR_ARG;
+    if (right->n_cols && !keeps_right) return SJMI_ERR_ARG;  // (a SEMI or ANTI pair has no right row to carry)
+    if (((uintptr_t)d_left_rows_in & 7) || ((uintptr_t)d_left_count & 7) || ((uintptr_t)d_right_order & 7) || ((uintptr_t)d_right_sort_result & 7) ||
+        ((uintptr_t)d_left_rows & 7) || ((uintptr_t)d_right_rows & 7) || ((uintptr_t)d_pair_offsets & 7) || ((uintptr_t)d_result & 7))
+        return SJMI_ERR_ARG;
+    if (fail(c, "hipSetDevice", hipSetDevice(c->device))) return SJMI_ERR_HIP;
+    hipStream_t st = stream_of(c, stream);
+    if (!grow_scratch(c, c->d_ws_join, sjmi::joinrows_workspace_bytes(n_left, n_right), "hipMalloc(ws_join)")) return SJMI_ERR_HIP;
+    return fail(c, "join rows launch",
+                sjmi::joinrows_launch(*left, d_left_rows_in, n_left, d_left_count, *right, d_right_order, n_right, d_right_sort_result, how,
+                                      pair_capacity, d_left_rows, d_right_rows, d_left_out_types, d_left_out_values, d_right_out_types,
+                                      d_right_out_values, out_stride, d_pair_offsets, d_result, c->d_ws_join, st))
                ? SJMI_ERR_HIP
                : SJMI_OK;
 }

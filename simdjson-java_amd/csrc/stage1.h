@@ -495,4 +495,18 @@ hipError_t parents_launch(const void* d_row_offsets, uint64_t n_docs, const void
                           const void* d_types, const void* d_values, uint64_t n_cols, uint64_t col_stride, void* d_parent_types, void* d_parents,
                           void* d_out_types, void* d_out_values, uint64_t out_stride, void* d_result, hipStream_t stream);
 
+// ---- two row sets joined on a long key: inner, left, semi, anti (joinrows.hip) ----
+// scratch of one call: n_right build keys, a word per chunk of 1024 left positions, n_left + 1 pair offsets, n_left 32-bit lower
+// bounds and n_left 32-bit pair counts
+size_t joinrows_workspace_bytes(uint64_t n_left, uint64_t n_right);
+// k_join_clear (the sjmi_join_result at d_result), with n_right != 0 k_join_keys, with n_left != 0 k_join_count, k_join_scan and
+// k_join_offsets, and with n_left != 0 and pair_capacity != 0 k_join_emit.  The sides are host structs; d_left_rows_in, d_left_count,
+// d_right_rows (SEMI, ANTI) and d_pair_offsets may be NULL; d_left_count and the n_candidates of d_right_sort_result are read by
+// the kernels
+hipError_t joinrows_launch(const sjmi_join_side& left, const void* d_left_rows_in, uint64_t n_left, const void* d_left_count,
+                           const sjmi_join_side& right, const void* d_right_order, uint64_t n_right, const void* d_right_sort_result,
+                           uint32_t how, uint64_t pair_capacity, void* d_left_rows, void* d_right_rows, void* d_left_out_types,
+                           void* d_left_out_values, void* d_right_out_types, void* d_right_out_values, uint64_t out_stride,
+                           void* d_pair_offsets, void* d_result, void* d_ws, hipStream_t stream);
+
 }  // namespace sjmi

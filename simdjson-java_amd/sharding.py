@@ -113,6 +113,8 @@ TOP_KINDS = {"long": 1, "double": 2}  # SJMI_TOP_LONG, SJMI_TOP_DOUBLE
 TOP_SMALLEST, TOP_MAX_K, TOP_RESULT_WORDS = 1, 2048, 9  # SJMI_TOP_SMALLEST, SJMI_TOP_MAX_K, SJMI_TOP_RESULT_WORDS
 SORT_DESCENDING, SORT_BAD_ROW, SORT_RESULT_WORDS = 1, 1, 9  # SJMI_SORT_DESCENDING, SJMI_SORT_BAD_ROW, SJMI_SORT_RESULT_WORDS (the kinds: TOP_KINDS)
 PARENT_MAX_COLS, PARENT_RESULT_WORDS = 64, 3  # SJMI_PARENT_MAX_COLS, SJMI_PARENT_RESULT_WORDS
+JOIN_HOWS = {"inner": 0, "left": 1, "semi": 2, "anti": 3}  # SJMI_JOIN_INNER, SJMI_JOIN_LEFT, SJMI_JOIN_SEMI, SJMI_JOIN_ANTI
+JOIN_OVERFLOW, JOIN_BAD_ROW, JOIN_BAD_ORDER, JOIN_RESULT_WORDS = 1, 2, 4, 9  # SJMI_JOIN_<FLAG>, SJMI_JOIN_RESULT_WORDS
 
 
 def decode_group_stats(stats):
@@ -540,6 +542,92 @@ class BatchShard:
                                          records[at].data_ptr(), stream)
             source = out
         return source, out_types, out_values, records
+
+    def join_rows(self, left_key, right_key, how="inner", left=None, right=None, left_rows=None, n_left=None, left_count=None,
+                  right_rows=None, n_right=None, right_count=None, right_sorted=None, pair_capacity=None, with_offsets=False, stream=0):
+        """JOIN two row sets ON one long key a side: sjmi_join_rows_device, behind one sjmi_sort_rows_device (LONG, ascending, no
+        carried columns) on the right key unless right_sorted is given.  left_key / right_key: (types, values[, validity]), a
+        1-D key column each as top_rows() takes it (types or validity may be None).  how: "inner", "left" (every live left
+        position at least once, an unmatched one with right row -1), "semi" (the left positions with a match, once) or "anti"
+        (those without, NULL, OTHER and BAD keys included).  left / right: a 2-D [n_cols, stride] (types, values) pair of
+        columns of the side's source rows to carry onto the pairs, or None; right must be None under "semi" and "anti".
+        left_rows / n_left / left_count and right_rows / n_right / right_count: the positions of a side as sort_rows() takes
+        rows / n_rows / row_count -- a filter's selection and its n_kept, an explode's last row offset.  right_sorted = the last
+        element of an earlier call's result on the same right side: the sort is skipped -- build once, probe many -- and the
+        right_* arguments are not read.  pair_capacity: the pairs the outputs hold (required).  -> (left_rows [pair_capacity]
+        int64 and right_rows [pair_capacity] int64 (None under "semi" and "anti"): the source rows of every pair, by ascending
+        left position and, inside one, ascending right position; left_types / left_values [n_left_cols, pair_capacity] and
+        right_types / right_values [n_right_cols, pair_capacity]: the carried cells, MISSING and 0 without a row; pair_offsets
+        [n_left + 1] int64 with with_offsets=True, else None: the pairs in front of every left position, explode's row_offsets
+        with "left position = document" for parent_columns(); record [9] int64 = live left positions, n_build, n_pairs,
+        n_matched, n_null, n_other, n_bad, n_right_bad, flags (JOIN_OVERFLOW: n_pairs > pair_capacity, call again with more);
+        right_sorted), new tensors every call; only the first min(n_pairs, pair_capacity) pairs are written.  Everything is a
+        function of the input alone.  Nothing synchronises.  Call it on a step that check() has accepted: like sort_rows(), it
+        is not queued again behind a step that check() had to run again."""
+        import torch
+        assert how in JOIN_HOWS, "join_rows(): how is 'inner', 'left', 'semi' or 'anti'"
+        assert pair_capacity is not None and int(pair_capacity) >= 0, "join_rows(): pair_capacity is required"
+        pair_capacity = int(pair_capacity)
+        keeps_right = how in ("inner", "left")
+        assert right is None or keeps_right, "join_rows(): a semi or anti join carries no right columns"
+
+        def side(key, rows, n, count):
+            assert len(key) in (2, 3), "join_rows(): a key is (types, values[, validity])"
+            validity = key[2] if len(key) == 3 else None
+            n_source = _key_column(key[0], key[1], validity, None)
+            if rows is None:
+                n = n_source if n is None else int(n)
+                assert 0 <= n <= n_source
+            else:
+                assert rows.dim() == 1 and rows.dtype == torch.int64 and rows.is_contiguous()
+                n = int(rows.numel()) if n is None else int(n)
+                assert 0 <= n <= int(rows.numel())
+            _check_row_count(count, key[1])
+            return key[0], validity, key[1], n_source, n
+
+        def carried(columns, n_source):
+            if columns is None:
+                return None, None, 0, 0
+            n_cols, stride, _ = _column_set(columns[0], columns[1], n_source)
+            return columns[0], columns[1], n_cols, stride
+
+        l_types, l_validity, l_values, l_source, n_left = side(left_key, left_rows, n_left, left_count)
+        lc_types, lc_values, l_cols, l_stride = carried(left, l_source)
+        if right_sorted is None:
+            r_types, r_validity, r_values, r_source, n_right = side(right_key, right_rows, n_right, right_count)
+            order = torch.empty(n_right, dtype=torch.int64, device=self.device)
+            sort_record = torch.empty(SORT_RESULT_WORDS, dtype=torch.int64, device=self.device)
+            self.engine.sort_rows_device(_ptr(r_types, r_types is not None and r_source), _ptr(r_validity, r_validity is not None and r_source),
+                                         _ptr(r_values, r_source), r_source, _ptr(right_rows, right_rows is not None and n_right), n_right,
+                                         _ptr(right_count, right_count is not None), TOP_KINDS["long"], 0, 0, 0, 0, 0, _ptr(order, n_right), 0, 0,
+                                         0, sort_record.data_ptr(), stream)
+            right_sorted = (order, sort_record)
+        else:
+            r_types, r_validity, r_values, r_source, _ = side(right_key, None, None, None)
+            order, sort_record = right_sorted
+            assert order.dim() == 1 and order.dtype == torch.int64 and order.is_contiguous()
+            assert sort_record.dtype == torch.int64 and sort_record.is_contiguous() and int(sort_record.numel()) == SORT_RESULT_WORDS
+            n_right = int(order.numel())
+        rc_types, rc_values, r_cols, r_stride = carried(right, r_source)
+        out_left = torch.empty(pair_capacity, dtype=torch.int64, device=self.device)
+        out_right = torch.empty(pair_capacity, dtype=torch.int64, device=self.device) if keeps_right else None
+        left_types = torch.empty((l_cols, pair_capacity), dtype=torch.uint8, device=self.device)
+        left_values = torch.empty((l_cols, pair_capacity), dtype=torch.int64, device=self.device)
+        right_types = torch.empty((r_cols, pair_capacity), dtype=torch.uint8, device=self.device)
+        right_values = torch.empty((r_cols, pair_capacity), dtype=torch.int64, device=self.device)
+        pair_offsets = torch.empty(n_left + 1, dtype=torch.int64, device=self.device) if with_offsets else None
+        record = torch.empty(JOIN_RESULT_WORDS, dtype=torch.int64, device=self.device)  # sjmi_join_result (every call writes all of it)
+        self.engine.join_rows_device(
+            (_ptr(l_types, l_types is not None and l_source), _ptr(l_validity, l_validity is not None and l_source), _ptr(l_values, l_source),
+             l_source, _ptr(lc_types, l_cols), _ptr(lc_values, l_cols), l_cols, l_stride),
+            _ptr(left_rows, left_rows is not None and n_left), n_left, _ptr(left_count, left_count is not None),
+            (_ptr(r_types, r_types is not None and r_source), _ptr(r_validity, r_validity is not None and r_source), _ptr(r_values, r_source),
+             r_source, _ptr(rc_types, r_cols), _ptr(rc_values, r_cols), r_cols, r_stride),
+            _ptr(order, n_right), n_right, _ptr(sort_record, n_right), JOIN_HOWS[how], pair_capacity, _ptr(out_left, pair_capacity),
+            _ptr(out_right, keeps_right and pair_capacity), _ptr(left_types, l_cols * pair_capacity), _ptr(left_values, l_cols * pair_capacity),
+            _ptr(right_types, r_cols * pair_capacity), _ptr(right_values, r_cols * pair_capacity), pair_capacity if l_cols or r_cols else 0,
+            _ptr(pair_offsets, with_offsets), record.data_ptr(), stream)
+        return out_left, out_right, left_types, left_values, right_types, right_values, pair_offsets, record, right_sorted
 
     def parent_columns(self, row_offsets, types, values, rows=None, n_rows=None, row_count=None, with_parents=True, stream=0):
         """The document of every exploded row, and that document's cells on the row (pandas.json_normalize's meta, SQL's UNNEST
